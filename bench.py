@@ -1,6 +1,7 @@
 """Headline benchmark: valid mel frames / s of one Daft-Exprt training step (forward + loss + backward) on MI355X.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     # + what the last timed step returned, as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], SURVEY.md §8d "C2"): 48 utterances per GPU, 50-120 symbols, 2-12 frames per symbol
@@ -62,6 +63,38 @@ def cpu_baseline(hp, n_threads, config, n_speakers):
                       f'dropout on, pitch predictor on, 1 warm-up + {len(timed)} timed steps, {step:.2f} s/step'}
 
 
+DUMP_SAMPLE = 1 << 22          # elements of the parameter / gradient samples: 2 x 16.8 MB, the whole dump stays below 64 MB
+
+
+def dump_outputs(out_dir, model, total, terms, grad_norm, sample=DUMP_SAMPLE):
+    """``--dump-outputs DIR``: what the last timed step handed its caller, one float32 ``DIR/<name>.npy`` each.
+
+      loss              ()       the total loss (mean over micro-batches)
+      loss_terms        (M, 7)   per micro-batch, in LossTerms.KEYS order
+      grad_norm         ()       the global gradient norm the fused Adam clipped with
+      params_sample     (S,)     the parameters after the update   } the same S positions (seeded, sorted) of all parameters
+      grads_sample      (S,)     their ``.grad`` (x loss scale     }  flattened and concatenated in ``named_parameters()``
+                                 in fp16 mode)                     }  order, so two builds are compared element for element
+    """
+    import numpy as np
+    from ubisoft_laforge_daft_exprt_amd.loss import LossTerms
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([p.grad.detach().reshape(-1).float() for p in params])
+    n = flat_p.numel()
+    idx = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, min(sample, n), replace=False))).to(flat_p.device)
+    arrays = {'loss': total.detach().float().cpu().numpy(),
+              'loss_terms': np.array([[t[k] for k in LossTerms.KEYS] for t in terms], dtype=np.float32),
+              'grad_norm': grad_norm.detach().float().cpu().numpy(),
+              'params_sample': flat_p[idx].cpu().numpy(),
+              'grads_sample': flat_g[idx].cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return arrays
+
+
 def spawn_ranks(n):
     """``python bench.py --gpus N`` without a launcher: start N ranks as fresh child processes (one per GPU, RCCL over xGMI)
     BEFORE anything in this process touches the GPU, relay their output, exit with their code.  The reference spawns its ranks
@@ -93,7 +126,12 @@ def main():
     ap.add_argument('--no-dropout', action='store_true', help='diagnostic only: the headline metric is measured with dropout on')
     ap.add_argument('--cuts', default='auto', help="backward phases of the trainer: 'auto' (3 cuts when N > 1, none on one GPU) or 0..3")
     ap.add_argument('--no-extras', action='store_true', help='skip the sustained run, the f32-mode step and the C4 inference batch that follow the timed region')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step returned (loss, loss terms, gradient norm, seeded samples of the updated parameters '
+                         'and their gradients) to DIR/<name>.npy, float32; rank 0 only')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         spawn_ranks(args.gpus)
@@ -173,9 +211,9 @@ def main():
                 _orig_finish()                    # waits for the bucketed all-reduces
                 ev_red[timed_idx].record()
             trainer.reducer.finish = finish
-        total, _terms, _norm = trainer.train_step([dev_batch])
+        total, terms, norm = trainer.train_step([dev_batch])
         trainer.reducer.finish = _orig_finish
-        return total
+        return total, terms, norm
 
     for it in range(args.warmup):
         step(it)
@@ -194,7 +232,7 @@ def main():
             trainer.use_graphs = False
             _lib.set_timer(records)
         th = time.perf_counter()
-        last = step(args.warmup + it, it)
+        last, last_terms, last_norm = step(args.warmup + it, it)
         host_s += time.perf_counter() - th
     _lib.set_timer(None)
     trainer.use_graphs = not args.no_graph
@@ -211,6 +249,9 @@ def main():
     else:
         total_frames = float(frames)
     assert torch.isfinite(last).item(), 'non-finite loss in the timed region'
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the sustained run below updates the same parameters and gradient buckets
+        dump_outputs(args.dump_outputs, model, last, last_terms, last_norm)
     exposed_ms = sum(a.elapsed_time(b) for a, b in zip(ev_bwd, ev_red)) / args.steps   # compute-stream time spent waiting in reducer.finish()
     if world > 1:
         te = torch.tensor([exposed_ms], device=dev, dtype=torch.float64)
