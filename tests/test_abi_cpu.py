@@ -59,6 +59,28 @@ def test_no_cpu_fallback_and_reference_errors():
         model.parse_batch('cpu', inputs)
 
 
+def test_launch_plan_has_no_switches():
+    """Which kernels a step launches depends on shape and precision only: the package reads no environment variable but the diagnostic
+    library path, the extra compiler flags of a diagnostic build and the forced collectives of the bench / rehearsal, and its HIP sources
+    test no macro but the fp16 twin build and the two stamp builds."""
+    import re
+    import ubisoft_laforge_daft_exprt_amd as pkg
+    root = os.path.dirname(pkg.__file__)
+    csrc = os.path.join(root, 'csrc')
+    paths = [os.path.join(root, f) for f in sorted(os.listdir(root)) if f.endswith('.py')]
+    paths += [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h', '.cpp', '.c'))]
+    env, macros = set(), set()
+    for path in paths:
+        text = open(path).read()
+        for m in re.finditer(r'\b(?:environ|getenv)\b', text):
+            read = re.match(r'(?:environ(?:\.get\(|\[)|getenv\()\s*[\'"](\w+)[\'"]', text[m.start():])
+            env.add(read.group(1) if read else f'<not a literal name: {os.path.basename(path)}:{text.count(chr(10), 0, m.start()) + 1}>')
+        for cond in re.findall(r'^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$', text, flags=re.M):
+            macros |= set(re.findall(r'\b[A-Za-z_]\w*\b', cond.split('//')[0])) - {'defined'}
+    assert env == {'DX_LIB_PATH', 'DX_EXTRA_HIPCC_FLAGS', 'DX_FORCE_COLLECTIVES'}, sorted(env)
+    assert macros <= {'DX_F16', 'DX_FFPAIR_STAMPS', 'DX_WG_STAMPS', '__cplusplus', '__HIPCC__'}, sorted(macros)
+
+
 def test_duration_rounding_is_bit_exact_against_reference_kats():
     import json
     from ubisoft_laforge_daft_exprt_amd.durations import duration_to_integer, get_int_durations

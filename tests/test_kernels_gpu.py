@@ -201,7 +201,7 @@ def test_bf16_hidden_storage(ops):
 @pytest.mark.parametrize('Cin,Cout,taps', [(128, 1024, 3), (128, 384, 1), (128, 128, 1), (80, 1024, 3), (128, 80, 1)])
 def test_weight_stationary_conv_path(ops, Cin, Cout, taps):
     """bf16 layers with Cin <= 128 and >= 64 token tiles run the persistent weight-stationary kernel: check it against the tiled
-    kernel (DX_CONV_WS is read once per process, so the reference here is PyTorch) for every epilogue variant."""
+    kernel (the launch plan has no switch to force the tiled kernel, so the reference here is PyTorch) for every epilogue variant."""
     ops.set_precision('bf16')
     try:
         B, N = 9, 1000                                       # 9 x 8 = 72 token tiles, ragged last tile

@@ -1,7 +1,7 @@
-"""Diagnostic builds for timing ablations: ONE source of the library recompiled with extra flags and linked with the other, unchanged
+"""Diagnostic builds: ONE source of the library recompiled with extra flags and linked with the other, unchanged
 objects into tools/ab/lib_<name>.so (git-ignored; travels to the GPU box).  Select it with DX_LIB_PATH=tools/ab/lib_<name>.so.
 
-    python tools/ablation_build.py <name> <source.hip> <flags...>        e.g.  attn_noexp dx_attention.hip -DDX_ATTN_ABL=1
+    python tools/ablation_build.py <name> <source.hip> <flags...>        e.g.  gemm_o2 dx_gemm.hip -O2
 """
 import os, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -12,7 +12,7 @@ from ubisoft_laforge_daft_exprt_amd.synth import CONFIGS, synthetic_batch
 def main():
     csrc = os.path.join(REPO, 'ubisoft_laforge_daft_exprt_amd', 'csrc')
     so = os.path.join(tempfile.mkdtemp(), 'libffp_diag.so')
-    subprocess.run(['hipcc', '-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-shared', '-DDX_FFPAIR_STAMPS', '-w', '-DDX_FP_ABL=' + os.environ.get('DX_FP_ABL', '0'),
+    subprocess.run(['hipcc', '-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-shared', '-DDX_FFPAIR_STAMPS', '-w',
                     os.path.join(csrc, 'dx_ffpair.hip'), os.path.join(csrc, 'dx_runtime.hip'), '-o', so], check=True)
     dll = ctypes.CDLL(so)
     dev = 'cuda'

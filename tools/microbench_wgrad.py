@@ -1,6 +1,6 @@
 """The batched wide weight gradient (csrc/dx_gemm.hip: wgrad_bf16_kernel<3, true, true, 4>) alone, on the eight k = 3 jobs of the four
 frame-level decoder blocks of the C2 workload (conv2: dY 128 wide, X = hidden 1024 wide; conv1: dY = hidden gradient, X 128 wide).
-Use with DX_LIB_PATH=tools/ab/lib_<name>.so for ablation builds (tools/ablation_build.py <name> dx_gemm.hip -DDX_WG_ABL=n)."""
+Use with DX_LIB_PATH=tools/ab/lib_<name>.so for diagnostic builds (tools/ablation_build.py <name> dx_gemm.hip <flags...>)."""
 import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

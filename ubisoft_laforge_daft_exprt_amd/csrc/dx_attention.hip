@@ -512,27 +512,6 @@ __device__ __forceinline__ void store4(dx_h16* p, float a, float b, float c, flo
   *reinterpret_cast<bf16x4*>(p) = h;
 }
 #define DX_MFMA_BF16(A, B, C) DX_MFMA_H16((A), (B), (C))
-// Timing ablations (tools/ablation_build.py; results are then numerically wrong on purpose): DX_ATTN_ABL = 1: no exp2 (p = s);
-// 2: key / query tiles are staged once and reused (no LDS stores, barriers or global loads in the loop); 3: the first products
-// (S, dP) are skipped; 4: the second products (O, dV, dK, dQ) are skipped.
-#ifndef DX_ATTN_ABL
-#define DX_ATTN_ABL 0
-#endif
-#if DX_ATTN_ABL == 1
-#define DX_EXP2(X) (X)
-#else
-#define DX_EXP2(X) __builtin_amdgcn_exp2f(X)
-#endif
-#if DX_ATTN_ABL == 3
-#define DX_MFMA_1ST(A, B, C) (C)
-#else
-#define DX_MFMA_1ST(A, B, C) DX_MFMA_H16((A), (B), (C))
-#endif
-#if DX_ATTN_ABL == 4
-#define DX_MFMA_2ND(A, B, C) (C)
-#else
-#define DX_MFMA_2ND(A, B, C) DX_MFMA_H16((A), (B), (C))
-#endif
 __device__ __forceinline__ float dx_max2(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, INFINITY); }   // no NaNs here: scores are finite or -inf
 // (fmaxf() makes hipcc canonicalise every operand first - a v_max_f32 x, x, x each, 16 per key tile.  An inline-asm v_max3_f32 on the
 // MFMA results avoids that but is WRONG: the compiler's hazard recogniser does not look inside inline asm, so the asm read the
@@ -579,15 +558,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_
   DX_TILE_LOAD(QT, vreg, base, a.ld, 2 * a.D + h * HD, 0, a.N)
   for (int kt0 = 0; kt0 < ntiles; ++kt0) {
     const int kbase = kt0 * 64;
-    if (DX_ATTN_ABL != 2 || kt0 == 0) {
     __syncthreads();
     DX_TILE_STORE(QT, kreg, Ks)
     DX_TILE_STORE(QT, vreg, Vs)
     __syncthreads();
-    if (kt0 + 1 < ntiles && DX_ATTN_ABL != 2) {
+    if (kt0 + 1 < ntiles) {
       DX_TILE_LOAD(QT, kreg, base, a.ld, a.D + h * HD, kbase + 64, a.N)
       DX_TILE_LOAD(QT, vreg, base, a.ld, 2 * a.D + h * HD, kbase + 64, a.N)
-    }
     }
     f32x4 st[4];
     float mx = -INFINITY;
@@ -596,7 +573,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_
     for (int kt = 0; kt < 4; ++kt) {
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) acc = DX_MFMA_1ST(row_frag(Ks, kt * 16 + r, ks, g), qf[ks], acc);
+      for (int ks = 0; ks < 2; ++ks) acc = DX_MFMA_BF16(row_frag(Ks, kt * 16 + r, ks, g), qf[ks], acc);
       if (tail_tile) {                                  // only the last key tile of a row can hold padding keys
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -619,7 +596,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_
       float pk[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        pk[e] = DX_EXP2(st[kt][e] - m_new);
+        pk[e] = __builtin_amdgcn_exp2f(st[kt][e] - m_new);
         ls += pk[e];
       }
       // dropped probabilities become 0; the 1/(1-p) factor of the kept ones is applied once to O at the end
@@ -643,8 +620,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       f32x4 acc = o[dt];
-      acc = DX_MFMA_2ND(tr_pair(Vs, 0 + g * 4, 16 + g * 4, dt * 16, lane), p01, acc);
-      acc = DX_MFMA_2ND(tr_pair(Vs, 32 + g * 4, 48 + g * 4, dt * 16, lane), p23, acc);
+      acc = DX_MFMA_BF16(tr_pair(Vs, 0 + g * 4, 16 + g * 4, dt * 16, lane), p01, acc);
+      acc = DX_MFMA_BF16(tr_pair(Vs, 32 + g * 4, 48 + g * 4, dt * 16, lane), p23, acc);
       o[dt] = acc;
     }
   }
@@ -760,7 +737,7 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
     for (int kt = 0; kt < 4; ++kt) {
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) acc = DX_MFMA_1ST(row_frag(Ks, kt * 16 + r, ks, g), qf[ks], acc);
+      for (int ks = 0; ks < 2; ++ks) acc = DX_MFMA_BF16(row_frag(Ks, kt * 16 + r, ks, g), qf[ks], acc);
       if (tail_tile) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -779,7 +756,7 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
       float pk[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        pk[e] = DX_EXP2(st[kt][e] - m_new);
+        pk[e] = __builtin_amdgcn_exp2f(st[kt][e] - m_new);
         ls += pk[e];
       }
       if (a.thresh) dx_keep4(dx_rand64(a.seed, drow | (uint64_t)((kbase + kt * 16 + g * 4) >> 2)), thresh_v, pk, 0.f);
@@ -802,8 +779,8 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       f32x4 acc = o[dt];
-      acc = DX_MFMA_2ND(tr_pair(Vs, 0 + g * 4, 16 + g * 4, dt * 16, lane), p01, acc);
-      acc = DX_MFMA_2ND(tr_pair(Vs, 32 + g * 4, 48 + g * 4, dt * 16, lane), p23, acc);
+      acc = DX_MFMA_BF16(tr_pair(Vs, 0 + g * 4, 16 + g * 4, dt * 16, lane), p01, acc);
+      acc = DX_MFMA_BF16(tr_pair(Vs, 32 + g * 4, 48 + g * 4, dt * 16, lane), p23, acc);
       o[dt] = acc;
     }
   }
@@ -1089,14 +1066,12 @@ __global__ __launch_bounds__(256, (sizeof(QT) == 2 && sizeof(CT) == 2) ? 3 : 2) 
   if (tid < 64 && tid < a.N) { lse_r = a.lse[(size_t)bh * a.N + tid]; delta_r = a.delta[(size_t)bh * a.N + tid]; }
   for (int qt0 = 0; qt0 < ntiles; ++qt0) {
     const int qbase = qt0 * 64;
-    if (DX_ATTN_ABL != 2 || qt0 == 0) {
     __syncthreads();
     DX_TILE_STORE(QT, qreg, Qs)
     DX_TILE_STORE(CT, greg, Gs)
     if (tid < 64) { lse_s[tid] = -lse_r; delta_s[tid] = delta_r; }     // (-lse: see the S' accumulator below)
     __syncthreads();
-    }
-    if (qt0 + 1 < ntiles && DX_ATTN_ABL != 2) {
+    if (qt0 + 1 < ntiles) {
       DX_TILE_LOAD(QT, qreg, base, a.ld, h * HD, qbase + 64, a.N)
       DX_TILE_LOAD(CT, greg, gbase, a.ldc, h * HD, qbase + 64, a.N)
       const int qn = qbase + 64 + tid;
@@ -1126,12 +1101,12 @@ __global__ __launch_bounds__(256, (sizeof(QT) == 2 && sizeof(CT) == 2) ? 3 : 2) 
         f32x4 s = *reinterpret_cast<const f32x4*>(&lse_s[qt * 16 + g * 4]), dp = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          s = DX_MFMA_1ST(row_frag(Qs, qt * 16 + r, ks, g), kf[ks], s);
-          dp = DX_MFMA_1ST(row_frag(Gs, qt * 16 + r, ks, g), vf[ks], dp);
+          s = DX_MFMA_BF16(row_frag(Qs, qt * 16 + r, ks, g), kf[ks], s);
+          dp = DX_MFMA_BF16(row_frag(Gs, qt * 16 + r, ks, g), vf[ks], dp);
         }
         float p[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) p[e] = DX_EXP2(s[e]);
+        for (int e = 0; e < 4; ++e) p[e] = __builtin_amdgcn_exp2f(s[e]);
         if (tail_k || tail_q) {                             // wave-uniform: padding keys / queries exist only in the last tiles
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -1159,8 +1134,8 @@ __global__ __launch_bounds__(256, (sizeof(QT) == 2 && sizeof(CT) == 2) ? 3 : 2) 
       const bf16x8 pp = pack_pair(pd[0], pd[1]), dd = pack_pair(ds[0], ds[1]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        dv[dt] = DX_MFMA_2ND(tr_pair(Gs, half * 32 + g * 4, half * 32 + 16 + g * 4, dt * 16, lane), pp, dv[dt]);
-        dk[dt] = DX_MFMA_2ND(tr_pair(Qs, half * 32 + g * 4, half * 32 + 16 + g * 4, dt * 16, lane), dd, dk[dt]);
+        dv[dt] = DX_MFMA_BF16(tr_pair(Gs, half * 32 + g * 4, half * 32 + 16 + g * 4, dt * 16, lane), pp, dv[dt]);
+        dk[dt] = DX_MFMA_BF16(tr_pair(Qs, half * 32 + g * 4, half * 32 + 16 + g * 4, dt * 16, lane), dd, dk[dt]);
       }
     }
   }
@@ -1174,9 +1149,6 @@ __global__ __launch_bounds__(256, (sizeof(QT) == 2 && sizeof(CT) == 2) ? 3 : 2) 
   }
 }
 #undef DX_MFMA_BF16
-#undef DX_MFMA_1ST
-#undef DX_MFMA_2ND
-#undef DX_EXP2
 #undef DX_TILE_LOAD
 #undef DX_TILE_STORE
 
@@ -1228,8 +1200,7 @@ int dx_attention_fwd(const void* qkvv, int ld, const int* lens, void* ctxv, int 
   DX_REQUIRE(!ctx_bf16 || (bf16 && (ldc % 8) == 0), "dx_attention_fwd: a 16-bit context needs the 16-bit operand mode and ldc %% 8 == 0");
   DX_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "dx_attention_fwd: dropout p out of range");
   AttnArgs a{qkv, ld, lens, ctx, ldc, lse, B, N, H, D, seed, (uint32_t)lrintf(p_drop * 65536.f), 1.f / (1.f - p_drop), seed_offset, order, 0};
-  static const int xmap_env = getenv("DX_ATTN_XCD") ? atoi(getenv("DX_ATTN_XCD")) : 1;
-  a.xcd_map = xmap_env && ((H * B) % 8 == 0);
+  a.xcd_map = (H * B) % 8 == 0;
   hipStream_t s = (hipStream_t)stream;
   dx_prof_begin(DX_PROF_ATTN_FWD, s);
   const dim3 grid(dx_cdiv(N, 64), H, B);
@@ -1288,8 +1259,7 @@ int dx_attention_bwd(const void* qkvv, int ld, const void* ctxv, const void* dct
   if (!bf16)                                       // the bf16 dQ kernel computes delta on the fly and leaves it for dK/dV
     hipLaunchKernelGGL(attn_delta_kernel, dim3((int)std::min<long>((items + 3) / 4, 8192)), dim3(256), 0, s, dctx, ctx, ldc, delta, B, N, H);
   AttnBwdArgs a{qkv, ld, dctx, ldc, lse, delta, lens, dqkv, ldg, B, N, H, D, seed, (uint32_t)lrintf(p_drop * 65536.f), 1.f / (1.f - p_drop), ctx, delta, seed_offset, order, 0};
-  static const int xmap_env = getenv("DX_ATTN_XCD") ? atoi(getenv("DX_ATTN_XCD")) : 1;
-  a.xcd_map = xmap_env && ((H * B) % 8 == 0);
+  a.xcd_map = (H * B) % 8 == 0;
   dx_prof_begin(DX_PROF_ATTN_BWD, s);
   if (bf16) {
     const dim3 grid(dx_cdiv(N, 64), H, B);

@@ -95,8 +95,6 @@ struct FFPairArgs {
   // optional ReLU-sign words (forward: written; backward: read INSTEAD of aux): one dword per lane, slice and 16-channel block, bit k of it =
   // "hidden value (column tile j = NJ-1 - k/4, channel 3 - k%4 of the lane's four) was > 0"; [B * tiles][F / 128][4 waves][2][64 lanes]
   unsigned* hmask;
-  int slice_skew;                    // 1: workgroup w starts its walk over the hidden slices at slice w % nslices (see the kernel)
-  int dz_lds;                        // 1 (block backward with the LayerNorm prologue): dz2 waits for the epilogue in LDS behind the images instead of in Y (see the prologue)
   unsigned long long* stamps;        // diagnostic builds (-DDX_FFPAIR_STAMPS, tools/ffpair_stamps.py) only: [workgroup][role][16] s_memtime values
 };
 
@@ -125,13 +123,6 @@ __device__ __forceinline__ int fp_wave_sum_i(int v) {
   return v;
 }
 
-// Timing ablations for tools/ffpair_stamps.py (diagnostic builds only; results are then numerically wrong on purpose):
-//   DX_FP_ABL = 1: weight fragments are fetched once and reused;  2: B fragments are read from LDS once per slice and reused;
-//   3: the producer epilogue is skipped;  4: 1 + 2 + no copy-out: bare MFMA steps.  (asm volatile keeps the reused values alive so nothing upstream is dead-code eliminated.)
-#ifndef DX_FP_ABL
-#define DX_FP_ABL 0
-#endif
-
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 #define FP_MMA(W, X, C) C = DX_MFMA_H16(__builtin_bit_cast(bf16x8, W), __builtin_bit_cast(bf16x8, X), C);
@@ -150,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
   // 512 B/token written and 512 B/token read back in the two HBM-bound, matrix-idle ends of the kernel.  The rows that fit behind the three
   // images (126-token tiles: 112 of 126 rows = 56 KB, 157 KB of LDS in all; 62-token tiles: all rows) wait there instead; the rest go through Y.
   constexpr int DZ_ROWS = NJ == 8 ? 112 : FP_TOK;
-  float* const dzs = (a.lnp_w && a.dz_lds) ? reinterpret_cast<float*>(smem + 3 * FP_IMG) : nullptr;
+  float* const dzs = a.lnp_w ? reinterpret_cast<float*>(smem + 3 * FP_IMG) : nullptr;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -170,18 +161,13 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
   const int w_i = role == 0 ? 4 * 512 : (a.F >> 5) * 512;                          // between the two row blocks
   const int w_slice = role == 0 ? 8 * 4 * 512 : 4 * 512;                           // between slices
   const int total_steps = nslices * 12;
-  // Slice ORDER: iteration `it` of a workgroup handles hidden slice (it + skew) % nslices, skew = its block index.  Every workgroup of a launch
-  // streams the same 1.5 MB of weights; started together and walking the slices in the same order they all ask the XCD's L2 for the
-  // SAME kilobytes at the same time, i.e. for the one or two L2 channels those addresses live in: the fragment stream ran at ~7 TB/s chip-wide
-  // whatever the tile size (126-token tiles: 384 MB per launch in 56 us; 62-token tiles: 768 MB in 93 us).  Skewed, the 32 workgroups of an XCD
-  // are spread over all nslices x 12 steps of the stream.  (A sum over slices in another order: fp32 rounding only; the order is a function of the
-  // block index, so results stay reproducible run to run.)
-  const int skew = a.slice_skew ? (int)((blockIdx.x >> 3) % (unsigned)nslices) : 0;   // (blockIdx & 7 = the XCD: neighbours ON an XCD must differ)
-  auto slice_of = [&](int it) { const int f = it + skew; return f >= nslices ? f - nslices : f; };
+  // Slice order: iteration `it` of every workgroup handles hidden slice `it`.  Every workgroup of a launch streams the same 1.5 MB of weights,
+  // so started together they all ask the XCD's L2 for the same kilobytes at the same time (the fragment stream ran at ~7 TB/s chip-wide
+  // whatever the tile size: 126-token tiles 384 MB per launch in 56 us, 62-token tiles 768 MB in 93 us).  Skewing the walk by the block
+  // index, so that the 32 workgroups of an XCD spread over all nslices x 12 steps of the stream, measured neutral (56.5 vs 56.6 us).
   auto w_ptr = [&](int gs) {                          // global step index (iteration order) -> fragment (i = 0) address; past the end: re-read the last
     gs = min(gs, total_steps - 1);
-    const int it_ = gs / 12, s = gs - it_ * 12;
-    const int f = slice_of(it_);
+    const int f = fp_opaque(gs / 12), s = gs - f * 12;    // (opaque: otherwise the 62-token kernels hold two more VGPRs)
     return wbase + (size_t)f * w_slice + (s >> 2) * w_tap + (s & 3) * 512;
   };
   // ring of RING steps: a step is 2 * NJ MFMAs per wave (NJ = 8: 256 cycles, four steps ahead = ~1 k cycles of cover for an L2 round trip; NJ = 4:
@@ -479,9 +465,8 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
   }
 #define FP_STEP(CUR, NXT, IMG, GS0, S, AUXPF, FRESH, CO, IMGC, F0C)                                                  \
   {                                                                                                                  \
-    if (DX_FP_ABL != 2 && DX_FP_ABL != 4) { if ((S) + 1 < 12) FP_RD8(NXT, IMG, (S) + 1) }                                              \
-    else { _Pragma("unroll") for (int j = 0; j < NJ; ++j) NXT[j] = CUR[j]; }                                         \
-    if ((CO) && DX_FP_ABL != 4 && (S) < NJ && ((S) & 1) == 0) FP_CO_RD((S) >> 1, IMGC)                                                 \
+    if ((S) + 1 < 12) FP_RD8(NXT, IMG, (S) + 1)                                                                      \
+    if ((CO) && (S) < NJ && ((S) & 1) == 0) FP_CO_RD((S) >> 1, IMGC)                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                                               \
     const f32x4 w0 = wr[(S) % RING][0], w1 = wr[(S) % RING][1];                                                      \
     if ((FRESH) && (S) == 0) {                                  /* a producer slice starts from the bias as the C operand */ \
@@ -491,8 +476,8 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
       _Pragma("unroll") for (int j = 0; j < NJ; ++j) { FP_MMA(w0, CUR[j], acc[0][j]) }                               \
       _Pragma("unroll") for (int j = 0; j < NJ; ++j) { FP_MMA(w1, CUR[j], acc[1][j]) }                               \
     }                                                                                                                \
-    if (DX_FP_ABL != 1 && DX_FP_ABL != 4) FP_WLOAD((S) % RING, (GS0) + (S) + RING)                                                     \
-    if ((CO) && DX_FP_ABL != 4 && (S) < NJ && ((S) & 1) == 1) FP_CO_ST((S) >> 1, F0C)                                                  \
+    FP_WLOAD((S) % RING, (GS0) + (S) + RING)                                                                         \
+    if ((CO) && (S) < NJ && ((S) & 1) == 1) FP_CO_ST((S) >> 1, F0C)                                                  \
     if ((S) == 8) { AUXPF }                                                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                                               \
   }
@@ -520,7 +505,7 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
     // bias + ReLU (forward) or the sign mask (backward), bf16, into slice image f & 1
 #define FP_PRODUCE(F_, COFLAG)                                                                                       \
     {                                                                                                                \
-      const int f0 = slice_of(F_) << 7;                                                                              \
+      const int f0 = (F_) << 7;                                                                                      \
       /* the bias is the C operand of the slice's first MFMAs: no add in the epilogue */                             \
       const f32x4 bv0 = a.bias_a ? *reinterpret_cast<const f32x4*>(a.bias_a + f0 + 32 * wq + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};      \
       const f32x4 bv1 = a.bias_a ? *reinterpret_cast<const f32x4*>(a.bias_a + f0 + 32 * wq + 16 + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f}; \
@@ -540,12 +525,11 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
               av[i][j] = *reinterpret_cast<const bf16x4*>(a.aux + ((size_t)b * a.N + n) * a.ld_aux + f0 + 32 * wq + 16 * i + 4 * g2_); \
             }                                                                                                        \
           }                                                                                                          \
-        }, true, COFLAG, ((((F_) - 1) & 1) ? Hs1 : Hs0), slice_of((F_) - 1) << 7)                                    \
+        }, true, COFLAG, ((((F_) - 1) & 1) ? Hs1 : Hs0), ((F_) - 1) * 128)                                           \
       unsigned char* const out = ((F_) & 1) ? Hs1 : Hs0;                                                             \
       const int r_ = fp_opaque(r);                                                                                   \
       const int g_ = fp_opaque(g);                                                                                   \
-      if (DX_FP_ABL == 3) { _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j) asm volatile("" :: "v"(acc[i][j])); } \
-      else _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                           \
+      _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                \
         const int c = 32 * wq + 16 * i + 4 * g_;                                                                     \
         unsigned char* const orow = out + (c >> 6) * (FP_HR * 128) + fp_lds_off(r_, (c & 63) >> 3) + ((g_ & 1) << 3); \
         unsigned sw_ = 0u;                                          /* forward: the sign word being built */        \
@@ -601,7 +585,7 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
       const unsigned char* const imgc = ((nslices - 1) & 1) ? Hs1 : Hs0;
       f32x4 cpv;
 #pragma unroll
-      for (int k = 0; k < NJ / 2; ++k) { FP_CO_RD(k, imgc) FP_CO_ST(k, slice_of(nslices - 1) << 7) }
+      for (int k = 0; k < NJ / 2; ++k) { FP_CO_RD(k, imgc) FP_CO_ST(k, (nslices - 1) << 7) }
     }
     __syncthreads();
     FP_STAMP(3 + nslices)
@@ -617,14 +601,14 @@ __global__ __launch_bounds__(512, 2) void ff_pair_kernel(const FFPairArgs a) {
     FP_STAMP(3)
     for (int it = 1; it <= nslices; ++it) {
       if (it == 4) FP_STAMP(12)
-      const int f = it - 1;                              // iteration whose slice is consumed; its hidden channels start at slice_of(f) * 128
+      const int f = it - 1;                              // iteration whose slice is consumed; its hidden channels start at f * 128
       const unsigned char* const img = (f & 1) ? Hs1 : Hs0;
       // The consumers copy their half of the finished slice out BEFORE their matrix steps (4 pieces per thread; the producers'
       // half rides along on their matrix steps).  Both roles of a
       // SIMD advance through their MFMAs at the same rate, so starting together they also finish together and the producer's
       // epilogue ran with the matrix pipe idle; this head start for the producer (a "stagger", MI355X_MICROARCH.md "Two waves per
       // SIMD" item 9) puts its epilogue beside the consumer's last MFMAs instead.
-      FP_COPY_OUT_CONS(img, slice_of(f) << 7)
+      FP_COPY_OUT_CONS(img, f << 7)
       FP_SLICE_STEPS(img, f * 12, , false, false, img, 0)
       if (it == 4) FP_STAMP(13)
       __syncthreads();
@@ -942,9 +926,7 @@ static int ff_pair_launch(const void* X, int ldx, const void* Wa, const void* Wb
 #endif
   // LDS: the three images, + (block backward with the LayerNorm prologue) the dz2 rows that wait for the epilogue
   constexpr int DZ8 = 112 * 512, DZ4 = FP<4>::TOK * 512;
-  static const int dz_env = getenv("DX_FF_DZ_LDS") ? atoi(getenv("DX_FF_DZ_LDS")) : 1;
-  a.dz_lds = dz_env && a.lnp_w != nullptr;
-  const int lds8 = 3 * FP<8>::IMG + (a.dz_lds ? DZ8 : 0), lds4 = 3 * FP<4>::IMG + (a.dz_lds ? DZ4 : 0);
+  const int lds8 = 3 * FP<8>::IMG + (a.lnp_w ? DZ8 : 0), lds4 = 3 * FP<4>::IMG + (a.lnp_w ? DZ4 : 0);
   static bool configured = false;
   if (!configured) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_pair_kernel<true, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * FP<8>::IMG + DZ8);
@@ -955,15 +937,12 @@ static int ff_pair_launch(const void* X, int ldx, const void* Wa, const void* Wb
     hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_pair_kernel<false, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * FP<4>::IMG);
     configured = true;
   }
-  // tile width: 62-token tiles with two workgroups per CU (NJ = 4) or 126-token tiles with one (NJ = 8); DX_FF_NJ overrides (diagnostics)
+  // tile width: 62-token tiles with two workgroups per CU (NJ = 4) or 126-token tiles with one (NJ = 8)
   a.hmask = hmask;
-  static const int skew_env = getenv("DX_FF_SKEW") ? atoi(getenv("DX_FF_SKEW")) : 0;     // measured neutral (56.5 vs 56.6 us): off
-  a.slice_skew = skew_env;
-  static const int nj_env = getenv("DX_FF_NJ") ? atoi(getenv("DX_FF_NJ")) : 0;
   // Tile width by shape: 126-token tiles where they fill the chip (frame axis: ~250 live tiles at C2); 62-token tiles for short batches
   // (symbol axis: 48 utterances of <= 120 symbols are 48 tiles of 126 but 96 of 62: twice the CUs, half the serial slice loop per workgroup).
   // Forward and backward see the same (B, N) and therefore make the same choice (the sign words are laid out per tile).
-  const int nj = nj_env == 8 || nj_env == 4 ? nj_env : (B * dx_cdiv(N, FP<8>::TOK) >= 96 ? 8 : 4);
+  const int nj = B * dx_cdiv(N, FP<8>::TOK) >= 96 ? 8 : 4;
   hipStream_t s = (hipStream_t)stream;
   dx_prof_begin(DX_PROF_CONV_GEMM, s);
   if (nj == 8) {

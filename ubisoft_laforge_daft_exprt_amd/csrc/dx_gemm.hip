@@ -1009,9 +1009,7 @@ void launch_conv_dk(const ConvGemmArgs& a, hipStream_t s) {
   }
   dim3 grid(a.B * dx_cdiv(a.N, 128), a.CoutP / TILE);
   ConvGemmArgs b = a;
-  static const int swz_env = getenv("DX_DK_SWIZZLE") ? atoi(getenv("DX_DK_SWIZZLE")) : 1;
-  b.xcd_swizzle = (swz_env && grid.y > 1 && (grid.y <= 4 || grid.y % 4 == 0)) ? (swz_env == 1 ? 4 : swz_env) : 0;   // DX_DK_SWIZZLE = 8: all blocks of a tile together (diagnostic)
-  if (b.xcd_swizzle && grid.y % b.xcd_swizzle != 0 && grid.y > (unsigned)b.xcd_swizzle) b.xcd_swizzle = 4;
+  b.xcd_swizzle = (grid.y > 1 && (grid.y <= 4 || grid.y % 4 == 0)) ? 4 : 0;
   if (b.xcd_swizzle) grid.x = dx_roundup(grid.x, 8);
   hipLaunchKernelGGL((conv_dk_kernel<TAPS, XH>), grid, dim3(512), smem, s, b);
 }
@@ -1352,9 +1350,6 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
   };
   while (c < total && !live()) advance();
   if constexpr (!DMA) if (c < total) DX_WG_LOAD(b, nc);
-#ifndef DX_WG_ABL
-#define DX_WG_ABL 0      // timing ablations (tools/ablation_build.py): 1 no MFMA, 2 no global loads in the loop, 4 tiles staged once
-#endif
   if constexpr (DMA) {
     // ---- LDS-DMA ring -------------------------------------------------------------------------------------------------------------
     // Measured on the serial form (tools/microbench_wgrad.py, ablation builds, eight k = 3 jobs of the frame-level decoder): 277 us as it
@@ -1456,10 +1451,7 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            if (DX_WG_ABL & 1) asm volatile("" :: "v"(df[i]), "v"(xf[j]));
-            else acc[t][i][j] = DX_MFMA_H16(df[i], xf[j], acc[t][i][j]);
-          }
+          for (int j = 0; j < 2; ++j) acc[t][i][j] = DX_MFMA_H16(df[i], xf[j], acc[t][i][j]);
       }
       if (bias_wave) {
 #pragma unroll
@@ -1535,7 +1527,7 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
     while (done < issued) {
       const int img = done & (DMA_NIMG - 1);
       if (c < total) {                       // image (done + 3) & 3 was last read before the barrier of the previous iteration
-        if (!(DX_WG_ABL & 2)) issue((done + DMA_NIMG - 1) & (DMA_NIMG - 1), b, nc);
+        issue((done + DMA_NIMG - 1) & (DMA_NIMG - 1), b, nc);
         ++issued;
         advance();
         while (c < total && !live_s()) advance();
@@ -1547,7 +1539,7 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
 #ifdef DX_WG_STAMPS
       const unsigned long long tv0 = WG_NOW();
 #endif
-      if (more && !(DX_WG_ABL & 2)) wait_dma(issued - done - 2);
+      if (more) wait_dma(issued - done - 2);
 #ifdef DX_WG_STAMPS
       const unsigned long long tb0 = WG_NOW();
       t_vm += tb0 - tv0;
@@ -1637,10 +1629,7 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            if (DX_WG_ABL & 1) asm volatile("" :: "v"(df[i]), "v"(xf[j]));
-            else acc[t][i][j] = DX_MFMA_H16(df[i], xf[j], acc[t][i][j]);
-          }
+          for (int j = 0; j < 2; ++j) acc[t][i][j] = DX_MFMA_H16(df[i], xf[j], acc[t][i][j]);
       }
     };
     bool have = c < total;                 // a chunk is in the staging registers
@@ -1683,10 +1672,10 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
 #ifdef DX_WG_STAMPS
           { const unsigned long long tv0 = WG_NOW(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); t_vm += WG_NOW() - tv0; }
 #endif
-          if (!(DX_WG_ABL & 4)) DX_WG_STORE(IMG - img);
+          DX_WG_STORE(IMG - img);
           advance();
           while (c < total && !live()) advance();
-          if (!(DX_WG_ABL & 2)) if (c < total) DX_WG_LOAD(b, nc);
+          if (c < total) DX_WG_LOAD(b, nc);
         }
         multiply(F[ks & 1]);
       }
@@ -1695,17 +1684,13 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
     }
     WG_STAMP(2, WG_NOW()) WG_STAMP(4, t_vm) WG_STAMP(5, t_bar) WG_STAMP(6, n_chunks)
   } else {
-  [[maybe_unused]] bool first_chunk = true;
   while (c < total) {
-    if (!(DX_WG_ABL & 4) || first_chunk) {
-      __syncthreads();
-      DX_WG_STORE(0);
-      __syncthreads();
-    }
-    first_chunk = false;
+    __syncthreads();
+    DX_WG_STORE(0);
+    __syncthreads();
     advance();
     while (c < total && !live()) advance();
-    if (!(DX_WG_ABL & 2)) if (c < total) DX_WG_LOAD(b, nc);
+    if (c < total) DX_WG_LOAD(b, nc);
     if (do_bias) {
       const int r0b = (tid >> 6) * (WB_BK / (NT / 64));
       const dx_h16* col = Ds + r0b * WB_LD;
@@ -1729,10 +1714,7 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            if (DX_WG_ABL & 1) asm volatile("" :: "v"(df[i]), "v"(xf[j]));
-            else acc[t][i][j] = DX_MFMA_H16(df[i], xf[j], acc[t][i][j]);
-          }
+          for (int j = 0; j < 2; ++j) acc[t][i][j] = DX_MFMA_H16(df[i], xf[j], acc[t][i][j]);
       }
     }
   }
@@ -1989,7 +1971,7 @@ int launch_conv(const ConvGemmArgs& a, hipStream_t s) {
   // 64-token tiles fill the chip better (measured 405 -> 354 us on the FF conv2); in bf16 mode the 128-token tile stays ahead
   // (62 vs 79 us) because the weight tile is re-staged half as often.
   // (bf16, k = 1, few workgroups - the phoneme-level Linear layers: 64-token tiles measured 9.6 -> 7.7 us; bf16 k = 3 stays at 128)
-  static const long small_below = getenv("DX_CONV_SMALL_BELOW") ? atol(getenv("DX_CONV_SMALL_BELOW")) : ((sizeof(T) == 4 || TAPS == 1) ? 1024 : 0);
+  constexpr long small_below = (sizeof(T) == 4 || TAPS == 1) ? 1024 : 0;
   const bool small = (long)a.B * dx_cdiv(a.N, TILE) * (a.CoutP / TILE) < small_below;
   if constexpr (sizeof(T) == 2) {
     if (a.x_bf16) { if (small) launch_conv_inst<T, TAPS, 64, true>(a, s); else launch_conv_inst<T, TAPS, 128, true>(a, s); return DX_OK; }
@@ -2097,15 +2079,13 @@ int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, voi
                  relu_aux, ld_aux, accumulate, lens, mask_rows, out_scale, skip_halo, x_bf16, y_bf16, aux_bf16, rows_exist};
   hipStream_t s = (hipStream_t)stream;
   dx_prof_begin(DX_PROF_CONV_GEMM, s);
-  static const int use_ws = getenv("DX_CONV_WS") ? atoi(getenv("DX_CONV_WS")) : 1;
-  static const int use_dk = getenv("DX_CONV_DK") ? atoi(getenv("DX_CONV_DK")) : 1;
-  static const int ws_min_tiles = getenv("DX_CONV_WS_MIN_TILES") ? atoi(getenv("DX_CONV_WS_MIN_TILES")) : 64;
+  constexpr int ws_min_tiles = 64;
   // deep-K layers: weights straight from the fragment-major pack into registers, live tiles numbered first
-  static const int dk_min_cin = getenv("DX_CONV_DK_MIN_CIN") ? atoi(getenv("DX_CONV_DK_MIN_CIN")) : 256;
-  if (bf16 && use_dk && d[1] >= dk_min_cin && (Cin % 64) == 0 && (long)B * N * ldx < (1L << 31)) {
+  constexpr int dk_min_cin = 256;
+  if (bf16 && d[1] >= dk_min_cin && (Cin % 64) == 0 && (long)B * N * ldx < (1L << 31)) {
     if (x_bf16) { if (taps == 3) launch_conv_dk<3, true>(a, s); else launch_conv_dk<1, true>(a, s); }
     else { if (taps == 3) launch_conv_dk<3, false>(a, s); else launch_conv_dk<1, false>(a, s); }
-  } else if (bf16 && use_ws && d[1] == 128 && (long)B * dx_cdiv(N, 128) >= ws_min_tiles) {      // short-K layers: weight-stationary persistent kernel
+  } else if (bf16 && d[1] == 128 && (long)B * dx_cdiv(N, 128) >= ws_min_tiles) {      // short-K layers: weight-stationary persistent kernel
     if (x_bf16) { if (taps == 3) launch_conv_ws<3, true>(a, s); else launch_conv_ws<1, true>(a, s); }
     else { if (taps == 3) launch_conv_ws<3, false>(a, s); else launch_conv_ws<1, false>(a, s); }
   } else if (bf16) { if (taps == 3) launch_conv<dx_h16, 3>(a, s); else launch_conv<dx_h16, 1>(a, s); }
@@ -2128,18 +2108,17 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
     DX_REQUIRE(B > 0 && N > 0 && Cin > 0 && Cout > 0 && (taps == 1 || taps == 3), "dx_conv_wgrad: bad dims");
     DX_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0, "dx_conv_wgrad: pointers must be 16-byte aligned");
     DX_REQUIRE(skip_halo < 0 || lens, "dx_conv_wgrad: skip_halo needs lens");
-    static const int use_wide = getenv("DX_WGRAD_WIDE") ? atoi(getenv("DX_WGRAD_WIDE")) : 1;
     // 512-thread workgroups with 128 input channels each: measured better only where the output is large enough that few token
     // slices are needed anyway (prenet 1024 x 1024: 308 -> 239 us); the 128-wide layers stay on the narrow form (59 vs 67 us)
-    const bool wide = use_wide && (Cin % 128) == 0 && dx_cdiv(Cout, TILE) * dx_cdiv(Cin, 64) >= 64;
+    const bool wide = (Cin % 128) == 0 && dx_cdiv(Cout, TILE) * dx_cdiv(Cin, 64) >= 64;
     const int tiles = dx_cdiv(Cout, TILE) * dx_cdiv(Cin, wide ? 128 : 64);
     const int total_chunks = B * dx_cdiv(N, wb_bk(taps, dy_bf16 != 0, x_bf16 != 0));
     // split-K partials are fp32 atomics (~1.3 TB/s chip-wide), so the split is sized by atomic traffic, not by "as many as fit";
     // per-kernel rocprof sweeps (r01-g build): k = 3 layers 192 / 256 / 320 / 384 blocks -> 50.0 / 47.6 / 48.8 / 50.2 us,
     // k = 1 layers 96 / 128 / 160 / 192 / 256 / 384 -> 24.9 / 20.9 / 19.5 / 18.8 / 19.5 / 22.1 us
-    static const int target_blocks = getenv("DX_WGRAD_BLOCKS") ? atoi(getenv("DX_WGRAD_BLOCKS")) : 256;
-    static const int target_wide = getenv("DX_WGRAD_BLOCKS_WIDE") ? atoi(getenv("DX_WGRAD_BLOCKS_WIDE")) : 256;   // one per CU
-    static const int target_k1 = getenv("DX_WGRAD_BLOCKS_K1") ? atoi(getenv("DX_WGRAD_BLOCKS_K1")) : 192;
+    constexpr int target_blocks = 256;
+    constexpr int target_wide = 256;   // one per CU
+    constexpr int target_k1 = 192;
     const int ksplit = std::max(1, std::min(total_chunks, dx_cdiv(wide ? target_wide : (taps == 1 ? target_k1 : target_blocks), tiles)));
     WgradBatchArgs a{};
     a.job[0] = WgradJobDev{dY, X, G, dbias, lens, ldy, ldx, B, N, Cin, Cout, skip_halo, 0};
@@ -2204,13 +2183,12 @@ int dx_conv_wgrad_batched(const void* jobs_, int njobs, int taps, int dy_bf16, i
   }
   // One 512-thread workgroup per CU and round; a launch of many layers runs several rounds (24 layers: 768 workgroups at the same 4-way
   // split), so the atomic epilogues of the early finishers run under the chunk loops of the next round instead of at the end of a launch.
-  static const int per_round = getenv("DX_WGRAD_BLOCKS_BATCH") ? atoi(getenv("DX_WGRAD_BLOCKS_BATCH")) : 256;
+  constexpr int per_round = 256;
   const int rounds = std::max(1, (tile_jobs * 4 + per_round / 2) / per_round);
   a.ksplit = std::max(1, std::min(min_chunks, rounds * per_round / tile_jobs));
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(tiles, njobs, a.ksplit);
-  static const int grp_env = getenv("DX_WGRAD_XCD_GROUP") ? atoi(getenv("DX_WGRAD_XCD_GROUP")) : 1;
-  a.xcd_group = grp_env && tiles == 8 && (njobs * a.ksplit) % 8 == 0;
+  a.xcd_group = tiles == 8 && (njobs * a.ksplit) % 8 == 0;
 #ifdef DX_WG_STAMPS
   a.stamps = g_wgrad_stamps;
 #endif

@@ -474,19 +474,12 @@ __global__ __launch_bounds__(256) void scalar_conv_wgrad_kernel(const float* __r
   // that form returned wrong low results -- the even channels >= 64 of the middle tap, a random subset per launch, 1e-2 of the sum --
   // whenever an MFMA kernel of another stream shared the CUs (round 2's "lost update"; reproduced and bisected to this instruction form
   // in round 3: tools/experiment_fork_wgrad.py).  Alone on the chip, or in this form, the kernel is exact.
-#ifndef DX_SCW_PACKED
-#define DX_SCW_PACKED 0
-#endif
 #pragma unroll 4
   for (int n = n_begin + grp; n < n_end; n += 8) {
     f32x4 g = *reinterpret_cast<const f32x4*>(dout + ((size_t)b * N + n) * ldd + q * 4);
     const int i = n - n_begin;
     g *= rsc[i];
     ab += g;
-#if DX_SCW_PACKED
-#pragma unroll
-    for (int t = 0; t < 3; ++t) { a0[t] += g * xs[0][i + t]; a1[t] += g * xs[1][i + t]; }
-#else
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const float x0 = xs[0][i + t], x1 = xs[1][i + t];
@@ -499,7 +492,6 @@ __global__ __launch_bounds__(256) void scalar_conv_wgrad_kernel(const float* __r
         a0[t][e] = acc0; a1[t][e] = acc1;
       }
     }
-#endif
   }
   // the eight row groups fold in LDS first: every atomic lands on one of ~1 k addresses and same-address atomics serialise
   __shared__ float fold[8][7][D];
@@ -804,30 +796,24 @@ int dx_ln_bwd(const void* dyv, const void* zv, const float* mean, const float* r
   DX_REQUIRE((film == nullptr) == (dfilm == nullptr), "dx_ln_bwd: film and dfilm must come together");
   // every block ends in one atomic per channel on the SAME 2 C addresses (dw, dbias): same-address atomics serialise (~15 ns each), so the
   // block count is a trade between memory parallelism in the row loop and the length of that atomic chain
-  static const int rpb_env = getenv("DX_LN_BWD_RPB") ? atoi(getenv("DX_LN_BWD_RPB")) : 0;
-  static const int big_env = getenv("DX_LN_BWD_BIG") ? atoi(getenv("DX_LN_BWD_BIG")) : 1;
   // sixteen-wave blocks for C = 128 once there are rows enough to fill the chip with them (C = 1024 would need 64 KB of LDS per block: slower).
   // Measured at C2 (frame axis, 43 k rows): C = 128: 4 waves x 64 rows 25.4 us, 16 waves x 256 rows 23.6, 16 x 192 21.4; C = 1024: 4 x 64 94 us, 4 x 96 78
-  const bool big = big_env && C == 128 && (long)B * N >= 16384;
-  static const int rpb_1024 = getenv("DX_LN_BWD_RPB_1024") ? atoi(getenv("DX_LN_BWD_RPB_1024")) : 32;   // 96 / 48 / 32 / 24 rows: 6.363 / 6.350 / 6.345 / 6.351 ms per step
-  static const int rpb_small = getenv("DX_LN_BWD_RPB_SMALL") ? atoi(getenv("DX_LN_BWD_RPB_SMALL")) : 64;
-  const int rpb = rpb_env > 0 ? rpb_env : (big ? 192 : (C == 1024 ? rpb_1024 : rpb_small));
+  const bool big = C == 128 && (long)B * N >= 16384;
+  constexpr int rpb_1024 = 32;   // 96 / 48 / 32 / 24 rows: 6.363 / 6.350 / 6.345 / 6.351 ms per step
+  const int rpb = big ? 192 : (C == 1024 ? rpb_1024 : 64);
   LnBwdArgs k{dy, z, mean, rstd, w, bias, film, ld_film, lens, halo, dz, da, (dx_h16*)dg_bf16_copy, dw, dbias, dfilm, ld_dfilm, B, N, rpb, relu_mask,
               seed_pre, (uint32_t)lrintf(p_pre * 65536.f), 1.f / (1.f - p_pre),
               seed_post, (uint32_t)lrintf(p_post * 65536.f), 1.f / (1.f - p_post), seed_offset};
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(dx_cdiv(N, rpb), B);
   dx_prof_begin(DX_PROF_ROWS, s);
-#define DX_LN_BWD(CC, IO) do { \
-    if (big) { \
-      if (film) hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, true, 16>), grid, dim3(1024), 0, s, k); \
-      else hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, false, 16>), grid, dim3(1024), 0, s, k); \
-    } else { \
-      if (film) hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, true, 4>), grid, dim3(256), 0, s, k); \
-      else hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, false, 4>), grid, dim3(256), 0, s, k); } } while (0)
-  if (C == 128) DX_LN_BWD(128, float);
-  else if (io_bf16) DX_LN_BWD(1024, dx_h16);
-  else DX_LN_BWD(1024, float);
+#define DX_LN_BWD(CC, IO, WAVES) do { \
+    if (film) hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, true, WAVES>), grid, dim3(64 * WAVES), 0, s, k); \
+    else hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, false, WAVES>), grid, dim3(64 * WAVES), 0, s, k); } while (0)
+  if (big) DX_LN_BWD(128, float, 16);
+  else if (C == 128) DX_LN_BWD(128, float, 4);
+  else if (io_bf16) DX_LN_BWD(1024, dx_h16, 4);
+  else DX_LN_BWD(1024, float, 4);
 #undef DX_LN_BWD
   dx_prof_end(DX_PROF_ROWS, s);
   DX_LAUNCH_CHECK("dx_ln_bwd");
@@ -879,10 +865,9 @@ int dx_scalar_conv_wgrad(const float* dout, int ldd, const float* rowscale, cons
   DX_REQUIRE(dout && s0 && lens && dw0 && db0, "dx_scalar_conv_wgrad: null pointer");
   DX_REQUIRE(D == 128 && ldd >= 0, "dx_scalar_conv_wgrad: hidden dim must be 128");  // ldd == 0: one row broadcast
   DX_REQUIRE(!s1 || (dw1 && db1), "dx_scalar_conv_wgrad: second stream needs its gradient buffers");
-  static const int rpb_env = getenv("DX_SCW_RPB") ? atoi(getenv("DX_SCW_RPB")) : 0;
   // every block ends in 7 x 128 atomics on the same ~900 addresses, and same-address atomics cost ~70 ns each when all blocks finish together:
   // the launch time is proportional to the number of blocks (32 / 64 / 128 / 256 rows per block: 95 / 51 / 30 / 20 us on the frame axis)
-  const int rpb = rpb_env > 0 ? std::min(rpb_env, 256) : 256;
+  constexpr int rpb = 256;
   hipLaunchKernelGGL(scalar_conv_wgrad_kernel, dim3(dx_cdiv(N, rpb), B), dim3(256), 0, (hipStream_t)stream,
                      dout, ldd, rowscale, s0, s1, lens, dw0, db0, dw1, db1, B, N, rpb);
   DX_LAUNCH_CHECK("dx_scalar_conv_wgrad");

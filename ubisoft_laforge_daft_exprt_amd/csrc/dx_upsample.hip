@@ -463,10 +463,9 @@ int dx_upsample_fwd(const float* xs, const float* mu, const float* sigma, const 
   UpArgs a{xs, mu, sigma, lens, weights, xup, B, L, T};
   hipStream_t s = (hipStream_t)stream;
   dx_prof_begin(DX_PROF_UPSAMPLE, s);
-  static const int force_tt = getenv("DX_UP_FWD_TT") ? atoi(getenv("DX_UP_FWD_TT")) : 16;   // 64 / 32 / 16-frame tiles: 39.5 / 30.9 / 26.6 us
-  if (force_tt == 64 && fwd_smem<64>(L) <= LDS_BUDGET) launch_fwd<64>(a, s);
-  else if (force_tt != 16 && fwd_smem<32>(L) <= LDS_BUDGET) launch_fwd<32>(a, s);
-  else { DX_REQUIRE(fwd_smem<16>(L) <= LDS_BUDGET, "dx_upsample_fwd: L=%d too long for the LDS weight tile", L); launch_fwd<16>(a, s); }
+  // 16-frame tiles (64 / 32 / 16 frames measured 39.5 / 30.9 / 26.6 us)
+  DX_REQUIRE(fwd_smem<16>(L) <= LDS_BUDGET, "dx_upsample_fwd: L=%d too long for the LDS weight tile", L);
+  launch_fwd<16>(a, s);
   dx_prof_end(DX_PROF_UPSAMPLE, s);
   DX_LAUNCH_CHECK("dx_upsample_fwd");
   return DX_OK;
@@ -479,9 +478,7 @@ int dx_upsample_bwd(const float* dxup, const float* xs, const float* mu, const f
   UpBwdArgs a{dxup, xs, mu, sigma, weights, lens, dxs, dsigma, B, L, T};
   hipStream_t s = (hipStream_t)stream;
   // 32-frame tiles: 65 KB of LDS at L = 120, two workgroups per CU (64-frame tiles: 112 KB, one per CU, 153 vs 99 us)
-  static const int force_tt = getenv("DX_UP_TT") ? atoi(getenv("DX_UP_TT")) : 32;
-  if (force_tt == 64 && bwd_smem<64>(L) <= LDS_BUDGET) launch_bwd<64>(a, s);
-  else if (force_tt != 16 && bwd_smem<32>(L) <= LDS_BUDGET) launch_bwd<32>(a, s);
+  if (bwd_smem<32>(L) <= LDS_BUDGET) launch_bwd<32>(a, s);
   else { DX_REQUIRE(bwd_smem<16>(L) <= LDS_BUDGET, "dx_upsample_bwd: L=%d too long for the LDS tiles", L); launch_bwd<16>(a, s); }
   DX_LAUNCH_CHECK("dx_upsample_bwd");
   return DX_OK;
@@ -496,8 +493,8 @@ int dx_upsample_sym_bwd(const float* dxs_in, const float* dsigma, const float* x
   const long rows = (long)B * L;
   // every block ends in 129 atomics on the same 129 addresses (dwr, dbr): ~70 ns each when the blocks finish together, so the launch time
   // follows the block count on one side and the rows per wave on the other (1024 / 256 / 128 / 64 blocks: 40 / 20 / 24 / 37 us)
-  static const int nblk_env = getenv("DX_SYM_BLOCKS") ? atoi(getenv("DX_SYM_BLOCKS")) : 256;
-  hipLaunchKernelGGL(upsample_sym_bwd_kernel, dim3((int)std::min<long>((rows + 3) / 4, nblk_env)), dim3(256), 0, (hipStream_t)stream, a);
+  constexpr long nblk = 256;
+  hipLaunchKernelGGL(upsample_sym_bwd_kernel, dim3((int)std::min<long>((rows + 3) / 4, nblk)), dim3(256), 0, (hipStream_t)stream, a);
   DX_LAUNCH_CHECK("dx_upsample_sym_bwd");
   return DX_OK;
 }

@@ -61,17 +61,6 @@ class Lengths:
         # inference.GraphedSynthesizer: padded-shape buckets (exist = the batch's true longest length) and the batched accent encoder
         # (exist = lengths: every reference behaves as if it were run alone, scripts/synthesize.py:420-448).
         self.exist = None
-        self._order = None
-
-    @property
-    def order(self):
-        """device int32 [B]: utterance indices, longest first (ops.length_order) -- computed by one tiny launch on first use (under graph
-        capture: recorded, so every replay re-derives it from the static length buffer).  Attention workgroups are handed out in this order."""
-        if not ops._ATTN_ORDER:
-            return None
-        if self._order is None:
-            self._order = ops.length_order(self.i32)
-        return self._order
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -180,25 +169,20 @@ class FFTBlockFn(torch.autograd.Function):
             ops.conv_gemm(x, packs['in'], in_b, lens=L, halo=0, out_dtype=hd, prec=prec)     # bf16 mode: attention reads bf16 q/k/v
         so = rt.seed_offset                        # device scalar added to the seeds (graph replays), or None
         sh = ops.gemm_shadow(prec)                 # bf16 mode: GEMM operands also exist as bf16 copies written by their producers
-        if ops.attn_proj_ln_applies(qkv, heads, packs['out'], prec, lens.order):
-            # attention of both heads + out-projection + dropout + residual + LayerNorm in ONE launch (same bits as the two launches below)
+        if ops.attn_proj_ln_applies(qkv, heads, packs['out'], prec):
+            # 16-bit modes: attention of both heads + out-projection + dropout + residual + LayerNorm in ONE launch
             att, lse, z1, y1, mean1, rstd1, *rest = ops.attn_proj_ln_fwd(qkv, lens.i32, heads, s_attn, p_attn, packs['out'], out_b, x, ln1_w, ln1_b, None,
                                                                          seed_pre=s_ln1, p_pre=p_attn, shadow=sh, seed_offset=so, prec=prec)
             y1g = rest[0] if sh else y1
         else:
-            att, lse = ops.attention_fwd(qkv, lens.i32, heads, s_attn, p_attn, prec=prec, seed_offset=so, ctx_dtype=hd, order=lens.order)   # 16-bit modes: 16-bit context
-            if ops.proj_ln_applies(att, packs['out'], prec):   # out-projection + dropout + residual + LayerNorm: one launch, z1 straight from LDS
-                z1, y1, mean1, rstd1, *rest = ops.proj_ln_fwd(att, packs['out'], out_b, x, ln1_w, ln1_b, None, lens.i32, seed_pre=s_ln1, p_pre=p_attn,
-                                                             shadow=sh, seed_offset=so, prec=prec)
-                y1g = rest[0] if sh else y1
-            else:
-                z1 = ops.conv_gemm(att, packs['out'], out_b, lens=L, halo=0, prec=prec)
-                ln1 = ops.ln_fwd(z1, x, ln1_w, ln1_b, None, lens.i32, seed_pre=s_ln1, p_pre=p_attn, shadow=sh, seed_offset=so, prec=prec)
-                y1, mean1, rstd1 = ln1[:3]
-                y1g = ln1[3] if sh else y1             # the copy the GEMMs read
+            att, lse = ops.attention_fwd(qkv, lens.i32, heads, s_attn, p_attn, prec=prec, seed_offset=so, ctx_dtype=hd)
+            z1 = ops.conv_gemm(att, packs['out'], out_b, lens=L, halo=0, prec=prec)
+            ln1 = ops.ln_fwd(z1, x, ln1_w, ln1_b, None, lens.i32, seed_pre=s_ln1, p_pre=p_attn, shadow=sh, seed_offset=so, prec=prec)
+            y1, mean1, rstd1 = ln1[:3]
+            y1g = ln1[3] if sh else y1             # the copy the GEMMs read
         fused = ops.ff_pair_applies(y1g, packs['c1'], packs['c2'], prec)
-        y2 = qkv_next = hmask = None
-        if fused and ops._FF_LN:   # ... and the block's second LayerNorm on the output tile while it is still in LDS
+        qkv_next = hmask = None
+        if fused:   # conv1 + ReLU + conv2 in ONE launch, the hidden tile consumed from LDS, and the block's second LayerNorm on the output tile
             if next_in is not None and not ops.next_qkv_applies(next_in[0], prec):
                 next_in = None
             need_bwd = any(ctx.needs_input_grad)
@@ -208,12 +192,9 @@ class FFTBlockFn(torch.autograd.Function):
                                                             want_mask=need_bwd)    # training: + the ReLU sign words the backward reads instead of h
             hmask = rest.pop() if need_bwd else None
             qkv_next = rest[0] if rest else None         # ... and the next block's in-projection on the normalised tile
-        elif fused:    # conv1 + ReLU + conv2 in ONE launch, the 1024-wide hidden tile consumed from LDS (h is still written: weight gradients)
-            z2, h = ops.ff_pair(y1g, packs['c1'], packs['c2'], c1_b, c2_b, L, prec=prec, rows_exist=lens.exist)
         else:
             h = ops.conv_gemm(y1g, packs['c1'], c1_b, relu=True, lens=L, halo=1, out_dtype=hd, prec=prec, rows_exist=lens.exist)   # conv2 reads one row past the end
             z2 = ops.conv_gemm(h, packs['c2'], c2_b, lens=L, halo=0, prec=prec, rows_exist=lens.exist)
-        if y2 is None:
             y2, mean2, rstd2 = ops.ln_fwd(z2, y1, ln2_w, ln2_b, film, lens.i32, seed_pre=s_ln2, p_pre=p_conv, seed_offset=so, prec=prec)
         ctx.save_for_backward(x, film, qkv, att, lse, z1, mean1, rstd1, y1g, h, z2, mean2, rstd2, ln1_w, ln1_b, ln2_w, ln2_b)
         ctx.lens, ctx.packs, ctx.heads = lens, packs, heads
@@ -245,15 +226,14 @@ class FFTBlockFn(torch.autograd.Function):
         g = sk.get
         sh = ops.gemm_shadow(prec)
         so = ctx.seed_offset
-        if ctx.fused and ops._FF_BLOCK_BWD and sh and (film is None or film.stride(-1) == 1):
+        if ctx.fused:
             # LayerNorm2-backward (prologue) -> conv2^T -> ReLU mask -> conv1^T -> LayerNorm1-backward (epilogue): ONE launch
             # ... -> the out-projection's input gradient (datt) on the same tile
-            fuse_datt = att.dtype == ops._H16[prec] and ops._FF_BLOCK_DATT
             dz1, dh, dproj, dff, dfilm, dln2_w, dln2_b, dln1_w, dln1_b, datt = ops.ff_block_bwd(
                 dy2, z2, mean2, rstd2, ln2_w, ln2_b, film, packs['c1'], packs['c2'], L, h, z1, mean1, rstd1, ln1_w, ln1_b,
                 seed2=s_ln2, p2=p_conv, seed1=s_ln1, p1=p_attn, seed_offset=so, prec=prec, arena=arena,
                 sinks={'ln2_w': g('ln2_w'), 'ln2_b': g('ln2_b'), 'ln1_w': g('ln1_w'), 'ln1_b': g('ln1_b')},
-                out_pack=packs['out'] if fuse_datt else None, hmask=ctx.hmask)
+                out_pack=packs['out'], hmask=ctx.hmask)
             dc2_w, dc2_b = ops.conv_wgrad(dff, h, packs['c2'], L, 0, arena=arena, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, defer=True)
         else:
             datt = None
@@ -263,11 +243,8 @@ class FFTBlockFn(torch.autograd.Function):
             dff = r2[5] if sh else (da2 if da2 is not None else dz2)      # gradient w.r.t. the conv2 output, as the GEMMs read it
             # (before the pair below accumulates onto dz2 in place: without a 16-bit shadow and without dropout dff IS dz2)
             dc2_w, dc2_b = ops.conv_wgrad(dff, h, packs['c2'], L, 0, arena=arena, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, defer=True)
-            if ctx.fused:  # conv2^T -> ReLU mask -> conv1^T in one launch, accumulated into the residual-branch gradient
-                dy1, dh = ops.ff_pair(dff, packs['c1'], packs['c2'], None, None, L, backward=True, aux=h, out=dz2, accumulate=True, prec=prec)
-            else:
-                dh = ops.conv_gemm(dff, packs['c2'], None, transpose=True, relu_aux=h, lens=L, halo=1, out_dtype=h.dtype, prec=prec)
-                dy1 = ops.conv_gemm(dh, packs['c1'], None, transpose=True, out=dz2, accumulate=True, lens=L, halo=0, prec=prec)  # + residual branch
+            dh = ops.conv_gemm(dff, packs['c2'], None, transpose=True, relu_aux=h, lens=L, halo=1, out_dtype=h.dtype, prec=prec)
+            dy1 = ops.conv_gemm(dh, packs['c1'], None, transpose=True, out=dz2, accumulate=True, lens=L, halo=0, prec=prec)  # + residual branch
             r1 = ops.ln_bwd(dy1, z1, mean1, rstd1, ln1_w, ln1_b, None, L, want_da=p_attn > 0, seed_pre=s_ln1, seed_offset=so, prec=prec,
                             p_pre=p_attn, arena=arena, w_sink=g('ln1_w'), b_sink=g('ln1_b'), shadow=sh)
             dz1, da1, dln1_w, dln1_b = r1[:4]
@@ -276,7 +253,7 @@ class FFTBlockFn(torch.autograd.Function):
         dout_w, dout_b = ops.conv_wgrad(dproj, att, packs['out'], L, 0, arena=arena, w_sink=g('out_w'), b_sink=g('out_b'), prec=prec, defer=True)
         if datt is None:
             datt = ops.conv_gemm(dproj, packs['out'], None, transpose=True, lens=L, halo=0, prec=prec, out_dtype=att.dtype)   # stored like the context
-        dqkv = ops.attention_bwd(qkv, att, datt, lse, L, ctx.heads, s_attn, p_attn, out_dtype=qkv.dtype, prec=prec, seed_offset=so, order=lens.order)
+        dqkv = ops.attention_bwd(qkv, att, datt, lse, L, ctx.heads, s_attn, p_attn, out_dtype=qkv.dtype, prec=prec, seed_offset=so)
         din_w, din_b = ops.conv_wgrad(dqkv, x, packs['in'], L, 0, arena=arena, w_sink=g('in_w'), b_sink=g('in_b'), prec=prec, defer=True)
         dx = ops.conv_gemm(dqkv, packs['in'], None, transpose=True, out=dz1, accumulate=True, lens=L, halo=0, prec=prec)  # + residual branch
         return (dx, dfilm, None, None, None, None,

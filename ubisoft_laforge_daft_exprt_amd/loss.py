@@ -7,17 +7,11 @@ handed to autograd by ``_LossFn``.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 from torch import nn
 
 from . import ops
 from .functional import Lengths
-
-
-_PITCH_16BIT = os.environ.get('DX_PITCH_16BIT', '1') != '0'
-_PITCH_FUSED = os.environ.get('DX_PITCH_FUSED', '1') != '0'      # 0: the layer-by-layer launches also in the 16-bit modes (A/B timing, tests)
 
 
 def pitch_predictor_shapes(n_mel_channels=80, hidden_dim=256, kernel_size=3):
@@ -103,7 +97,7 @@ class _LossFn(torch.autograd.Function):
         if pitch_layers is not None and frames_pitch is not None and cfg['pcw'] > 0:
             prec = pitch_layers[0]['pack'].rt.precision                          # one value for the whole chain
             frames_pitch = frames_pitch.contiguous()
-            if _PITCH_FUSED and ops.pitch_chain_applies(pitch_layers, mel_pred, prec):
+            if ops.pitch_chain_applies(pitch_layers, mel_pred, prec):
                 # one launch each way (csrc/dx_pitch.hip): activations stay in LDS, the backward gets ReLU sign bits instead of activations
                 pp, masks = ops.pitch_chain_fwd(mel_pred, pitch_layers, lens.i32, prec, arena=arena)
                 psum = ops.pitch_mse(pp, frames_pitch, lens.i32, arena=arena)
@@ -115,7 +109,7 @@ class _LossFn(torch.autograd.Function):
                 x = ops.transpose(mel_pred)                                          # (B, T, M)
                 acts = []
                 depth = len(pitch_layers) - 1                                       # stacked k=3 convs: halos 3, 2, 1, 0
-                hd = ops.hidden_dtype(prec) if _PITCH_16BIT else torch.float32     # 16-bit modes: the 256-wide activations of the frozen predictor
+                hd = ops.hidden_dtype(prec)                                        # 16-bit modes: the 256-wide activations of the frozen predictor
                 for i, layer in enumerate(pitch_layers[:-1]):                      # (only ever GEMM operands / ReLU masks) are stored in 16 bits
                     r = ops.conv_gemm(x, layer['pack'], layer['b'], relu=True, lens=lens.i32, halo=depth - i, prec=prec, out_dtype=hd)
                     acts.append(r)

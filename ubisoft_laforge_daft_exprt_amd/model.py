@@ -10,8 +10,6 @@ from __future__ import annotations
 
 import math
 
-import os
-
 import torch
 from torch import nn
 
@@ -263,46 +261,15 @@ class StyleAdapter(nn.Module):
     def forward(self, style_embedding):
         gammas = self.gammas_predictor(style_embedding)
         betas = self.betas_predictor(style_embedding)
-        out, col, blk = {}, 0, 0
-        B = gammas.shape[0]
-        chans = {ch for _, ch in self.module_params.values()}
-        if len(chans) == 1:
-            # every module has the same width: the scalar post-multiplier affine, the (gamma | beta) concatenation and the split
-            # into per-block tensors are done ONCE for all blocks (same element-wise arithmetic, a third of the glue launches)
-            ch = chans.pop()
-            nb_all = sum(nb for nb, _ in self.module_params.values())
-            if gammas.is_cuda and os.environ.get('DX_FILM_FUSED', '1') != '0':      # one launch forward, one backward (functional.FilmAffineFn)
-                pm = self.post_multipliers if self.post_mult_weight != 0.0 else None
-                *blocks, whole = Fx.FilmAffineFn.apply(gammas, betas, pm, nb_all, getattr(self, '_dx_rt', None))
-                for name, (nb, _) in self.module_params.items():
-                    # the (B, nb, 2C) tensor of the reference's return value: a strided view of the block-major buffer
-                    out[name] = FilmSet(blocks[blk:blk + nb], whole[blk:blk + nb].transpose(0, 1))
-                    blk += nb
-                return out
-            g = gammas.view(B, nb_all, ch)
-            b = betas.view(B, nb_all, ch)
-            if self.post_mult_weight != 0.0:
-                g = self.post_multipliers[0][None, :, None] * g + 1
-                b = self.post_multipliers[1][None, :, None] * b
-            else:
-                g = g + 1
-            film_all = torch.cat((g, b), dim=2)
-            blocks = Fx.SplitFilmFn.apply(film_all)
-            for name, (nb, _) in self.module_params.items():
-                out[name] = FilmSet(blocks[blk:blk + nb], film_all[:, blk:blk + nb])
-                blk += nb
-            return out
-        for name, (nb, ch) in self.module_params.items():
-            # (B, nb, ch) scalar post-multiplier affine: O(B * 1024) element-wise glue on the autograd tape
-            g = gammas[:, col:col + nb * ch].view(B, nb, ch)
-            b = betas[:, col:col + nb * ch].view(B, nb, ch)
-            if self.post_mult_weight != 0.0:
-                g = self.post_multipliers[0, blk:blk + nb][None, :, None] * g + 1
-                b = self.post_multipliers[1, blk:blk + nb][None, :, None] * b
-            else:
-                g = g + 1
-            out[name] = torch.cat((g, b), dim=2)
-            col += nb * ch
+        # both modules are D wide: the scalar post-multiplier affine, the (gamma | beta) concatenation and the split into per-block
+        # tensors are done ONCE for all blocks, one launch forward, one backward (functional.FilmAffineFn)
+        nb_all = sum(nb for nb, _ in self.module_params.values())
+        pm = self.post_multipliers if self.post_mult_weight != 0.0 else None
+        *blocks, whole = Fx.FilmAffineFn.apply(gammas, betas, pm, nb_all, getattr(self, '_dx_rt', None))
+        out, blk = {}, 0
+        for name, (nb, _) in self.module_params.items():
+            # the (B, nb, 2C) tensor of the reference's return value: a strided view of the block-major buffer
+            out[name] = FilmSet(blocks[blk:blk + nb], whole[blk:blk + nb].transpose(0, 1))
             blk += nb
         return out
 

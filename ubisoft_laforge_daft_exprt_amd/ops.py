@@ -6,7 +6,6 @@ arithmetic on the path is done by libdaft_exprt_hip.so.  Every wrapper launches 
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
@@ -271,8 +270,8 @@ def conv_gemm(x, pack: PackedWeight, bias=None, *, transpose=False, relu=False, 
     return out
 
 
-_FF_FUSED_MIN_TILES = int(os.environ.get('DX_FF_FUSED_MIN_TILES', '96'))       # 126-token tiles (the frame axis)
-_FF_FUSED_MIN_TILES62 = int(os.environ.get('DX_FF_FUSED_MIN_TILES62', '64'))   # 62-token tiles (short batches: the symbol axis)
+_FF_FUSED_MIN_TILES = 96       # 126-token tiles (the frame axis)
+_FF_FUSED_MIN_TILES62 = 64     # 62-token tiles (short batches: the symbol axis)
 
 
 def ff_pair_applies(x, pack1: PackedWeight, pack2: PackedWeight, prec) -> bool:
@@ -308,18 +307,9 @@ def ff_pair(x, pack1: PackedWeight, pack2: PackedWeight, bias1, bias2, lens, *, 
     return out, h
 
 
-_FF_LN = os.environ.get('DX_FF_LN', '1') != '0'
-
-
-_FF_QKV = os.environ.get('DX_FF_QKV', '1') != '0'
-
-
 def next_qkv_applies(pack_in: PackedWeight, prec) -> bool:
     """The next block's attention in-projection can ride in the ff_pair epilogue: 128 -> 384, one tap, a 16-bit operand mode."""
-    return _FF_QKV and _half(prec) == 1 and pack_in.taps == 1 and pack_in.cin == 128 and pack_in.cout == 384
-
-
-_FF_MASK = os.environ.get('DX_FF_MASK', '1') != '0'
+    return _half(prec) == 1 and pack_in.taps == 1 and pack_in.cin == 128 and pack_in.cout == 384
 
 
 def ff_pair_ln(x, pack1: PackedWeight, pack2: PackedWeight, bias1, bias2, lens, res, ln_w, ln_b, film, *, seed_pre=0, p_pre=0.0, seed_offset=None,
@@ -340,7 +330,7 @@ def ff_pair_ln(x, pack1: PackedWeight, pack2: PackedWeight, bias1, bias2, lens, 
     y = torch.empty_like(z)
     mean = torch.empty(B, N, dtype=torch.float32, device=x.device)
     rstd = torch.empty(B, N, dtype=torch.float32, device=x.device)
-    mask = torch.empty(B * ((N + 61) // 62), Fc // 128, 4, 2, 64, dtype=torch.int32, device=x.device) if (want_mask and _FF_MASK) else None     # (room for either tile width)
+    mask = torch.empty(B * ((N + 61) // 62), Fc // 128, 4, 2, 64, dtype=torch.int32, device=x.device) if want_mask else None     # (room for either tile width)
     tail = (mask,) if want_mask else ()
     _log(pack1, ('ffpair', B * N, N, 128, Fc, 3))
     if next_in is not None:
@@ -375,10 +365,6 @@ def ff_pair_lnbwd(x, pack1: PackedWeight, pack2: PackedWeight, lens, aux, out, z
     _fn('dx_ff_pair_lnbwd', prec)(_p(x), _rows(x), _p(i2.bwd), _p(i1.bwd), _p(aux), _rows(aux), _p(dh), _rows(dh), _p(out), B, N, Fc, _p(lens), int(halo),
                                   _p(z), _p(mean), _p(rstd), _p(ln_w), _p(ln_b), _p(dg), _p(dw), _p(db), seed_pre, float(p_pre), _p(seed_offset), _stream())
     return out, dh, dg, (None if w_sink is not None else dw), (None if b_sink is not None else db)
-
-
-_FF_BLOCK_BWD = os.environ.get('DX_FF_BLOCK_BWD', '1') != '0'
-_FF_BLOCK_DATT = os.environ.get('DX_FF_BLOCK_DATT', '1') != '0'
 
 
 def ff_block_bwd(dy2, z2, mean2, rstd2, ln2_w, ln2_b, film, pack1: PackedWeight, pack2: PackedWeight, lens, aux, z1, mean1, rstd1, ln1_w, ln1_b, *,
@@ -490,7 +476,7 @@ class _WgradJob(ctypes.Structure):          # DxWgradJob of include/daft_exprt_h
 
 # layers per dx_conv_wgrad_batched launch (the library takes up to 32), by kernel size.  Measured in the C2 step: the k = 1 layers gain from
 # one launch for all of them (4 launches 243 us -> 2 launches 172 us), the k = 3 layers do not (8 per launch: 668 us, 24 per launch: 687 us)
-WGRAD_BATCH = {1: int(os.environ.get('DX_WGRAD_BATCH_K1', '32')), 3: int(os.environ.get('DX_WGRAD_BATCH_K3', '8'))}
+WGRAD_BATCH = {1: 32, 3: 8}
 WGRAD_BATCH_LOG = {}
 
 
@@ -542,9 +528,8 @@ def colsum(x, C=None):
     return out
 
 
-# longest-first dispatch of the attention workgroups: measured neutral at C2 (28.2 vs 29.0 us: one resident round, no tail), so it is OFF by
-# default and its two length_order launches per step are not issued; DX_ATTN_ORDER=1 turns it on (long-form / very uneven batches)
-_ATTN_ORDER = os.environ.get('DX_ATTN_ORDER', '0') != '0'
+# longest-first dispatch of the attention workgroups (the ``order`` argument below): measured neutral at C2 (28.2 vs 29.0 us: one resident
+# round, no tail), so the model does not use it
 
 
 def length_order(lens_i32):
@@ -600,22 +585,10 @@ def ln_fwd(a, res, w, b, film, lens, *, seed_pre=0, p_pre=0.0, seed_post=0, p_po
     return (y, mean, rstd, y_h) if shadow else (y, mean, rstd)
 
 
-def proj_ln_applies(x, pack: PackedWeight, prec) -> bool:
-    """The fused out-projection + LayerNorm kernel serves the 16-bit operand modes at the FFT block's shape (128 -> 128, k = 1)."""
-    return (prec in _H16 and x.dtype == _H16[prec] and x.dim() == 3 and x.shape[2] == 128 and pack.taps == 1 and pack.cin == 128
-            and pack.cout == 128 and _PROJ_LN)
-
-
-_PROJ_LN = os.environ.get('DX_PROJ_LN', '1') != '0'
-
-
-_ATTN_PROJ_LN = os.environ.get('DX_ATTN_PROJ_LN', '1') != '0'
-
-
-def attn_proj_ln_applies(qkv, heads, pack: PackedWeight, prec, order=None) -> bool:
+def attn_proj_ln_applies(qkv, heads, pack: PackedWeight, prec) -> bool:
     """Attention forward + out-projection + LayerNorm in one launch: the 16-bit modes at the FFT block's shape (2 heads x 64, 16-bit q/k/v)."""
-    return (_ATTN_PROJ_LN and _PROJ_LN and prec in _H16 and qkv.dtype == _H16[prec] and qkv.dim() == 3 and qkv.shape[2] == 384 and heads == 2
-            and order is None and pack.taps == 1 and pack.cin == 128 and pack.cout == 128)
+    return (prec in _H16 and qkv.dtype == _H16[prec] and qkv.dim() == 3 and qkv.shape[2] == 384 and heads == 2
+            and pack.taps == 1 and pack.cin == 128 and pack.cout == 128)
 
 
 def attn_proj_ln_fwd(qkv, lens, heads, seed, p_drop, pack: PackedWeight, proj_bias, res, w, b, film, *, seed_pre=0, p_pre=0.0, shadow=False,

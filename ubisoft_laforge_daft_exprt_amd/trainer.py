@@ -86,7 +86,7 @@ class Trainer:
         self.use_graphs, self.max_graphs = bool(use_graphs), int(max_graphs)
         # the FFT blocks' weight gradients go straight into the buckets (sink) and have no consumer before the exchange, so they are
         # queued during backward and launched 8 layers at a time (ops.flush_wgrads, after every backward phase below)
-        model.runtime.defer_wgrad = bool(grad_sink) and os.environ.get('DX_DEFER_WGRAD', '1') != '0'
+        model.runtime.defer_wgrad = bool(grad_sink)
         # fp16 operand mode: gradients that live in 16-bit tensors (dqkv, the 1024-wide hidden gradients) would underflow; the
         # backward runs on loss * loss_scale and the fused Adam multiplies by 1 / loss_scale (static scale; bf16 needs none).
         # An overflow (non-finite gradient norm) SKIPS the update on every rank (the norm is computed after the all-reduce, so all
