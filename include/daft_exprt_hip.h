@@ -65,7 +65,9 @@ int dx_pack_weights_host(const void* descs, int n, int bf16, void* stream);
  * 'same' padding although the buffers hold N rows per batch row.  NULL: every batch row has N rows (the reference's padded grid, whose
  * N is the longest utterance: model.py:14-24).  With it, ONE allocation / captured HIP graph of N rows serves every batch whose longest
  * utterance is <= N with unchanged results (rows_exist[b] = that batch's max length), and a batch row can be made to behave as if it
- * were run alone (rows_exist[b] = lens[b]: scripts/synthesize.py:420-448 runs the accent encoder per reference wav). */
+ * were run alone (rows_exist[b] = lens[b]: scripts/synthesize.py:420-448 runs the accent encoder per reference wav).  Output rows
+ * n >= rows_exist[b] do not exist either: they are written as zero (with accumulate: left as they are).  That makes the input-gradient
+ * convolution of a bucketed training step (dY -> dX) match the same launch on the tensors cut to rows_exist[b] rows. */
 int dx_conv_gemm(const void* X, int ldx, const void* Wp, const float* bias, void* Y, int ldy,
                  int B, int N, int Cin, int Cout, int taps, int bf16,
                  int relu, const float* post_scale, const float* post_shift,
@@ -78,8 +80,10 @@ int dx_conv_gemm(const void* X, int ldx, const void* Wp, const float* bias, void
  * w.r.t. its weight, train.py:435 loss.backward()).  G may be a zeroed scratch gradient or a live `.grad` / all-reduce bucket view. */
 int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
                   int B, int N, int Cin, int Cout, int taps, const int* lens, int skip_halo,
-                  int bf16, int dy_bf16, int x_bf16, float* dbias, void* stream);
-/* dbias (optional, caller-zeroed [Cout]): the bias gradient sum_rows dY is accumulated by the same launch from the staged dY tiles */
+                  int bf16, int dy_bf16, int x_bf16, float* dbias, const int* rows_exist, void* stream);
+/* dbias (optional, caller-zeroed [Cout]): the bias gradient sum_rows dY is accumulated by the same launch from the staged dY tiles.
+ * rows_exist (optional, device int32 [B], as in dx_conv_gemm): dY and X rows n >= rows_exist[b] read as zero, so nothing stored there
+ * reaches G or dbias (NULL: all N rows exist). */
 /* Up to 32 weight gradients of one kind (same taps, same operand storage, bf16 / fp16 operand mode, Cin % 128 == 0) in ONE launch:
  * the eight k = 3 layers of a 4-block FFT stack fill the chip at a 4-way token split instead of 16-way per layer (a quarter of the fp32
  * atomics); more layers run as further rounds of workgroups of the same launch (their atomic epilogues overlap the next round).  `jobs` is a HOST array of njobs DxWgradJob (read during the call; the descriptors travel as kernel arguments); every field
@@ -87,6 +91,7 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
 typedef struct DxWgradJob {
   const void* dY; const void* X; float* G; float* dbias; const int* lens;
   int ldy, ldx, B, N, Cin, Cout, skip_halo, reserved;
+  const int* rows_exist;      /* optional, as in dx_conv_wgrad (after `reserved`: the earlier fields keep their offsets) */
 } DxWgradJob;
 int dx_conv_wgrad_batched(const void* jobs, int njobs, int taps, int dy_bf16, int x_bf16, void* stream);
 /* grad (Cout, Cin, taps) (+)= G[taps][Cout][Cin]   (re-layout helper; dx_conv_wgrad itself now writes the parameter layout) */
@@ -137,13 +142,16 @@ int dx_ff_pair_lnbwd(const void* X, int ldx, const void* Wa, const void* Wb, con
  * (input-gradient pair).  Outputs: Y = dz1 (fp32, the residual gradient for the attention half), DG1 = dropout(dz1) and DG2 = dropout(dz2)
  * as 16 bits (operands of the out-projection's and the second conv's backward GEMMs), H = the hidden gradient; dw* / db* / dfilm accumulate.
  * Wout_bwd / DATT (optional, together): the backward pack of the attention out-projection's (128, 128) weight and a 16-bit [B][N][128]
- * output: the epilogue then also computes DATT = DG1 x W_out, the input gradient of the out-projection (what dx_attention_bwd takes as dctx). */
+ * output: the epilogue then also computes DATT = DG1 x W_out, the input gradient of the out-projection (what dx_attention_bwd takes as dctx).
+ * rows_exist (optional, device int32 [B], as in dx_conv_gemm): rows n >= rows_exist[b] do not exist for the two convolutions and the two
+ * LayerNorms: dY2 there reads as zero and every gradient row there (Y, DG1, DG2, DATT, H) is zero. */
 int dx_ff_block_bwd(const float* dY2, const float* z2, const float* mean2, const float* rstd2, const float* ln2_w, const float* ln2_b,
                     const float* film, int ld_film, void* DG2, float* dw2, float* db2, float* dfilm, int ld_dfilm, uint64_t seed2, float p2,
                     const void* Wa, const void* Wb, const void* aux, int ld_aux, void* H, int ldh, float* Y,
                     int B, int N, int F, const int* lens, int skip_halo,
                     const float* z1, const float* mean1, const float* rstd1, const float* ln1_w, const float* ln1_b, void* DG1, float* dw1, float* db1,
-                    uint64_t seed1, float p1, const void* Wout_bwd, void* DATT, const uint64_t* seed_offset, const void* hmask, void* stream);
+                    uint64_t seed1, float p1, const void* Wout_bwd, void* DATT, const uint64_t* seed_offset, const void* hmask,
+                    const int* rows_exist, void* stream);
 /* out[c] += sum_rows X[row][c]   (bias gradients) */
 int dx_colsum(const void* X, int ldx, float* out, long rows, int C, int x_bf16, void* stream);
 
@@ -239,7 +247,8 @@ int dx_upsample_sym_bwd(const float* dxs_in, const float* dsigma, const float* x
 /* ---- loss reductions and gradients: loss.py:99-146 ------------------------------------------------------------------- */
 int dx_mel_stats(const float* mel_pred, const float* mel_target, float* ep, float* et, float* l1sum, float* l2sum,
                  int B, int M, int T, void* stream);
-int dx_energy_diff(const float* ep, const float* et, const int* lens, float* des, float* esum, int B, int T, void* stream);
+/* rows_exist (optional, device int32 [B], as in dx_conv_gemm): frames t >= rows_exist[b] are the smoothing window's zero padding */
+int dx_energy_diff(const float* ep, const float* et, const int* lens, float* des, float* esum, int B, int T, const int* rows_exist, void* stream);
 /* e_per_total = 1: c_e is divided by sum_b lens[b] on the device (loss.py:129 normalises the energy term by the batch's valid frames) */
 int dx_mel_grad(const float* mel_pred, const float* mel_target, const float* ep, const float* des, const int* lens,
                 float c_l1, float c_l2, float c_e, int e_per_total, float* dmel, int B, int M, int T, void* stream);
@@ -258,12 +267,16 @@ int dx_pitch_grad(const float* pp, int ldp, const float* gt, const int* lens, co
  * 256-wide k = 3 convolutions written by dx_pack_weights (fwd takes the forward packs, bwd the backward packs); b*: biases; s* / t*: eval-mode
  * BatchNorm folded to a scale / shift per channel; w3: row 0 of the last convolution's weight in checkpoint layout (256, 3) fp32, b3 its bias;
  * masks: (B, T, 3, 8) uint32 written by fwd (ReLU sign bits: the network is frozen, so the backward needs no activations), read by bwd.
- * Only tokens n < lens[b] are produced (the loss and the model mask the rest).  Every entry point with 16-bit packs also exists as <name>_f16. */
+ * Only tokens n < lens[b] are produced (the loss and the model mask the rest).  Every entry point with 16-bit packs also exists as <name>_f16.
+ * rows_exist (optional, device int32 [B], as in dx_conv_gemm): frames n >= rows_exist[b] are the convolutions' zero padding although T frames
+ * are stored (fwd ignores the mel there, bwd ignores dpp / masks there); NULL: all T frames exist. */
 int dx_pitch_chain_fwd(const float* mel, int B, int M, int T, const int* lens, const void* w0, const void* w1, const void* w2,
                        const float* b0, const float* b1, const float* b2, const float* s0, const float* s1, const float* s2,
-                       const float* t0, const float* t1, const float* t2, const float* w3, float b3, float* pp, void* masks, void* stream);
+                       const float* t0, const float* t1, const float* t2, const float* w3, float b3, float* pp, void* masks,
+                       const int* rows_exist, void* stream);
 int dx_pitch_chain_bwd(const float* dpp, int B, int M, int T, const int* lens, const void* w0, const void* w1, const void* w2,
-                       const float* s0, const float* s1, const float* s2, const float* w3, const void* masks, float* dmel, void* stream);
+                       const float* s0, const float* s1, const float* s2, const float* w3, const void* masks, float* dmel,
+                       const int* rows_exist, void* stream);
 
 /* ---- on-device batch conditioning: dynamic_stats.py:131-195 ------------------------------------------------ */
 int dx_condition_prosody(const float* in, float* out, const long* speaker_ids, const float* table, const int* valid,

@@ -68,7 +68,7 @@ def main():
             rc = dll.dx_ff_block_bwd(P(dy2), P(z1), P(mean1), P(rstd1), P(ln_w), P(ln_b), P(film), 2 * D, P(dg2), P(acc[0]), P(acc[1]), P(dfilm), 2 * D,
                                      ctypes.c_uint64(5), F32(0.1), P(i2.bwd), P(i1.bwd), P(aux_b), Fc, P(h), Fc, P(y), B, N, Fc, P(lens), 1,
                                      P(z1), P(mean1), P(rstd1), P(ln_w), P(ln_b), P(dg1), P(acc[2]), P(acc[3]), ctypes.c_uint64(6), F32(0.1),
-                                     P(pout.bwd), P(datt), P(None), P(hmask if os.environ.get('DX_STAMP_MASK', '1') != '0' else None), S)
+                                     P(pout.bwd), P(datt), P(None), P(hmask if os.environ.get('DX_STAMP_MASK', '1') != '0' else None), P(None), S)
         assert rc == 0
     torch.cuda.synchronize()
     st = stamps.cpu()

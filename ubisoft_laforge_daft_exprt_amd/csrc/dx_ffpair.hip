@@ -1014,12 +1014,15 @@ int dx_ff_pair_lnbwd(const void* X, int ldx, const void* Wa, const void* Wb, con
 //   [epilogue] dz1 = LayerNorm1-backward(Y + pair result; z1, mean1, rstd1, w1) -> Y;  dropout(dz1) (16 bits) -> DG1;  dw1 / db1 +=
 // i.e. dx_ln_bwd (C = 128, FiLM optional, halo 0) + dx_ff_pair (input-gradient pair) + dx_ln_bwd (no FiLM) of model.py:225-233 / :206-217 /
 // :188-191 backward.  Y is an OUTPUT here (nothing is read from it); dfilm (optional, [B][ld_dfilm >= 256]) accumulates like dw / db.
+// rows_exist (optional [B]): rows n >= rows_exist[b] do not exist for either LayerNorm or the two convolutions -- their dY2 reads as zero and
+// every gradient row there (Y, DG1, DG2, DATT, H) is zero, whatever the inputs hold there.
 int dx_ff_block_bwd(const float* dY2, const float* z2, const float* mean2, const float* rstd2, const float* ln2_w, const float* ln2_b,
                     const float* film, int ld_film, void* DG2, float* dw2, float* db2, float* dfilm, int ld_dfilm, uint64_t seed2, float p2,
                     const void* Wa, const void* Wb, const void* aux, int ld_aux, void* H, int ldh, float* Y,
                     int B, int N, int F, const int* lens, int skip_halo,
                     const float* z1, const float* mean1, const float* rstd1, const float* ln1_w, const float* ln1_b, void* DG1, float* dw1, float* db1,
-                    uint64_t seed1, float p1, const void* Wout_bwd, void* DATT, const uint64_t* seed_offset, const void* hmask, void* stream) {
+                    uint64_t seed1, float p1, const void* Wout_bwd, void* DATT, const uint64_t* seed_offset, const void* hmask,
+                    const int* rows_exist, void* stream) {
   DX_REQUIRE(ln1_w != nullptr && ln2_w != nullptr, "dx_ff_block_bwd: null pointer");
   DX_REQUIRE((Wout_bwd == nullptr) == (DATT == nullptr) && ((uintptr_t)Wout_bwd % 16) == 0 && ((uintptr_t)DATT % 16) == 0, "dx_ff_block_bwd: Wout_bwd and DATT come together, 16-byte aligned");
   DX_REQUIRE(p2 >= 0.f && p2 < 1.f, "dx_ff_block_bwd: dropout p out of range");
@@ -1029,7 +1032,7 @@ int dx_ff_block_bwd(const float* dY2, const float* z2, const float* mean2, const
   pro.lnp_film = film; pro.lnp_ld_film = ld_film; pro.lnp_dg = (dx_h16*)DG2; pro.lnp_dw = dw2; pro.lnp_db = db2; pro.lnp_dfilm = dfilm;
   pro.lnb_wt = (const dx_h16*)Wout_bwd; pro.lnb_datt = (dx_h16*)DATT;
   pro.lnp_ld_dfilm = ld_dfilm; pro.lnp_seed = (unsigned long long)seed2; pro.lnp_thresh = (unsigned)lrintf(p2 * 65536.f); pro.lnp_inv_keep = 1.f / (1.f - p2);
-  return ff_pair_launch(nullptr, 128, Wa, Wb, nullptr, nullptr, aux, ld_aux, H, ldh, Y, 128, B, N, F, 0, 1, lens, skip_halo, nullptr,
+  return ff_pair_launch(nullptr, 128, Wa, Wb, nullptr, nullptr, aux, ld_aux, H, ldh, Y, 128, B, N, F, 0, 1, lens, skip_halo, rows_exist,
                         nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, (unsigned long long)seed1, p1, (const unsigned long long*)seed_offset,
                         z1, mean1, rstd1, ln1_w, ln1_b, DG1, dw1, db1, &pro, stream, (unsigned*)hmask);
 }

@@ -228,6 +228,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmArgs a)
 
   // epilogue: lane holds channels co..co+3 of token n
   const int len_b = a.lens ? a.lens[b] : a.N;
+  const int ne_b = NL;                                    // output rows n >= rows_exist[b] do not exist either: written as zero
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int co = co0 + wc * 64 + i * 16 + g * 4;
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmArgs a)
             if (co + e < a.Cout && !(a.relu_aux[row * a.ld_aux + co + e] > 0.f)) v[e] = 0.f;
         }
       }
-      if (a.mask_rows && n >= len_b) { v[0] = v[1] = v[2] = v[3] = 0.f; }
+      if ((a.mask_rows && n >= len_b) || n >= ne_b) { v[0] = v[1] = v[2] = v[3] = 0.f; }
       if (a.y_bf16) {
         dx_h16* dsth = reinterpret_cast<dx_h16*>(a.Y) + row * a.ldy + co;
         *reinterpret_cast<uint2*>(dsth) = pack_bf16x4(make_float4(v[0], v[1], v[2], v[3]));
@@ -502,6 +503,7 @@ __global__ __launch_bounds__(512, 2) void conv_ws_kernel(const ConvGemmArgs a, i
         }
 
     const int len_b = a.lens ? a.lens[cb] : a.N;
+    const int ne_b = a.rows_exist ? a.rows_exist[cb] : a.N;   // output rows n >= rows_exist[b]: written as zero
     if (a.y_bf16) {
       // bf16 outputs (the 1024-wide hidden tensors): row-per-lane 8-byte global stores are store-issue bound, so the tile goes
       // through LDS and leaves as fully coalesced 16-byte row segments; ReLU-mask / padding mask are applied on the way out
@@ -553,7 +555,7 @@ __global__ __launch_bounds__(512, 2) void conv_ws_kernel(const ConvGemmArgs a, i
                 if (!(a.relu_aux[grow * a.ld_aux + co + e] > 0.f)) o[e] = (dx_h16)0.f;
             }
           }
-          if (a.mask_rows && n >= len_b) {
+          if ((a.mask_rows && n >= len_b) || n >= ne_b) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (dx_h16)0.f;
           }
@@ -601,7 +603,7 @@ __global__ __launch_bounds__(512, 2) void conv_ws_kernel(const ConvGemmArgs a, i
               if (co + e < a.Cout && !(a.relu_aux[row * a.ld_aux + co + e] > 0.f)) v[e] = 0.f;
           }
         }
-        if (a.mask_rows && n >= len_b) { v[0] = v[1] = v[2] = v[3] = 0.f; }
+        if ((a.mask_rows && n >= len_b) || n >= ne_b) { v[0] = v[1] = v[2] = v[3] = 0.f; }
         if (a.y_bf16) {
           *reinterpret_cast<uint2*>(reinterpret_cast<dx_h16*>(a.Y) + row * a.ldy + co) = pack_bf16x4(make_float4(v[0], v[1], v[2], v[3]));
           continue;
@@ -939,6 +941,7 @@ __global__ __launch_bounds__(512) void conv_dk_kernel(const ConvGemmArgs a) {
 
   // epilogue: lane holds channels co..co+3 of token n; this wave finishes token sub-tiles 4*kg .. 4*kg+3 of its 32 channels
   const int len_b = a.lens ? a.lens[b] : a.N;
+  const int ne_b = NL;                                             // output rows n >= rows_exist[b]: written as zero
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int co = co0 + wq * 32 + i * 16 + g * 4;
@@ -977,7 +980,7 @@ __global__ __launch_bounds__(512) void conv_dk_kernel(const ConvGemmArgs a) {
             if (co + e < a.Cout && !(a.relu_aux[row * a.ld_aux + co + e] > 0.f)) v[e] = 0.f;
         }
       }
-      if (a.mask_rows && n >= len_b) { v[0] = v[1] = v[2] = v[3] = 0.f; }
+      if ((a.mask_rows && n >= len_b) || n >= ne_b) { v[0] = v[1] = v[2] = v[3] = 0.f; }
       if (a.y_bf16) {
         *reinterpret_cast<uint2*>(reinterpret_cast<dx_h16*>(a.Y) + row * a.ldy + co) = pack_bf16x4(make_float4(v[0], v[1], v[2], v[3]));
         continue;
@@ -1027,6 +1030,7 @@ struct WgradArgs {
   int B, N, Cin, Cout, ksplit;
   const int* lens; int skip_halo;   // chunks starting at or beyond len_b + skip_halo carry a zero dY: skipped
   float* dbias;                     // optional: dbias[co] += column sums of dY (fused bias gradient)
+  const int* rows_exist;            // optional [B]: dY and X rows n >= rows_exist[b] do not exist (read as zero; see ConvGemmArgs)
 };
 
 constexpr int WG_BK = 32;     // tokens per K chunk
@@ -1062,19 +1066,20 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
     if (a.skip_halo >= 0 && nc >= a.lens[b] + a.skip_halo) continue;
     const float* dYb = a.dY + (size_t)b * a.N * a.ldy;
     const float* Xb = a.X + (size_t)b * a.N * a.ldx;
+    const int nl = a.rows_exist ? a.rows_exist[b] : a.N;
     __syncthreads();
     for (int u = tid; u < WG_BK * 32; u += 256) {
       const int row = u >> 5, q = u & 31;
       const int n = nc + row, co = co0 + q * 4;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n < a.N && co < a.Cout) v = *reinterpret_cast<const float4*>(dYb + (size_t)n * a.ldy + co);
+      if (n < nl && co < a.Cout) v = *reinterpret_cast<const float4*>(dYb + (size_t)n * a.ldy + co);
       *reinterpret_cast<float4*>(&Ds[row * WG_LD + q * 4]) = v;
     }
     for (int u = tid; u < (WG_BK + TAPS - 1) * 32; u += 256) {
       const int row = u >> 5, q = u & 31;
       const int n = nc + row - PAD, ci = ci0 + q * 4;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n >= 0 && n < a.N && ci < a.Cin) v = *reinterpret_cast<const float4*>(Xb + (size_t)n * a.ldx + ci);
+      if (n >= 0 && n < nl && ci < a.Cin) v = *reinterpret_cast<const float4*>(Xb + (size_t)n * a.ldx + ci);
       *reinterpret_cast<float4*>(&Xs[row * WG_LD + q * 4]) = v;
     }
     __syncthreads();
@@ -1140,6 +1145,7 @@ struct WgradBf16Args {
   int B, N, Cin, Cout, ksplit;
   const int* lens; int skip_halo;
   float* dbias;
+  const int* rows_exist;
 };
 
 // Up to WG_MAX_JOBS weight gradients of one kind (same taps, same operand storage) in ONE launch: blockIdx.y = job.  A single 128 -> 1024
@@ -1151,6 +1157,7 @@ constexpr int WG_MAX_JOBS = 32;
 struct WgradJobDev {
   const void* dY; const void* X; float* G; float* dbias; const int* lens;
   int ldy, ldx, B, N, Cin, Cout, skip_halo, pad_;
+  const int* rows_exist;        // optional [B]: dY and X rows n >= rows_exist[b] do not exist (read as zero)
 };
 struct WgradBatchArgs {
   WgradJobDev job[WG_MAX_JOBS];
@@ -1218,6 +1225,7 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
     const WgradJobDev& j = ba.job[job_id];                  // kernel-argument memory, wave-uniform index: scalar loads
     a.dY = j.dY; a.ldy = j.ldy; a.dy_bf16 = DYH; a.X = j.X; a.ldx = j.ldx; a.x_bf16 = XH; a.G = j.G;
     a.B = j.B; a.N = j.N; a.Cin = j.Cin; a.Cout = j.Cout; a.ksplit = ba.ksplit; a.lens = j.lens; a.skip_halo = j.skip_halo; a.dbias = j.dbias;
+    a.rows_exist = j.rows_exist;
   }
   if (tile_id >= ((a.Cout + TILE - 1) / TILE) * ((a.Cin + CIW * 32 - 1) / (CIW * 32))) return;   // a job with fewer tiles than the widest
   // wave: 64 co x 32 ci -> 4 x 2 x TAPS MFMA tiles; waves = 2 (co) x CIW (ci).
@@ -1296,7 +1304,8 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
   {                                                                                                                           \
     const ptrdiff_t dbase_ = ((ptrdiff_t)(B_) * a.N + (NC_)) * a.ldy;                                                         \
     const ptrdiff_t xbase_ = ((ptrdiff_t)(B_) * a.N + (NC_) - PAD) * a.ldx;                                                   \
-    const int dlim_ = a.N - (NC_), xlo_ = PAD - (NC_), xhi_ = a.N - (NC_) + PAD;                                              \
+    const int nl_ = a.rows_exist ? a.rows_exist[B_] : a.N;                                                                   \
+    const int dlim_ = nl_ - (NC_), xlo_ = PAD - (NC_), xhi_ = nl_ - (NC_) + PAD;                                              \
     _Pragma("unroll") for (int it = 0; it < D_IT; ++it) {                                                                     \
       f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};                                                                                    \
       if (drow0 + it * DSTEP < dlim_) {                                                                                       \
@@ -1463,10 +1472,19 @@ __global__ __launch_bounds__(CIW * 128, CIW == 2 ? 2 : 1) void wgrad_bf16_kernel
     const bool dch_ok = co0 + sunit * 8 < a.Cout, xch_ok = ci0 + sunit * 8 < a.Cin;
     const int dsoff = srow * a.ldy + co0 + sunit * 8, xsoff = srow * a.ldx + ci0 + sunit * 8;     // elements
     const dx_h16* const zero_src = reinterpret_cast<const dx_h16*>(dx_wgrad_zero_unit);
+    // rows of utterance bb that exist (bb is wave-uniform): through the scalar cache, like the limits below (a vector load here would
+    // sit in the counted DMA queue)
+    auto exist_s = [&](int bb) {
+      if (!a.rows_exist) return a.N;
+      int ne;
+      asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ne) : "s"(a.rows_exist + bb) : "memory");
+      return ne;
+    };
     auto issue = [&](int img, int bb, int nn) {
       const dx_h16* const dsrc = reinterpret_cast<const dx_h16*>(a.dY) + ((ptrdiff_t)bb * a.N + nn) * a.ldy;
       const dx_h16* const xsrc = reinterpret_cast<const dx_h16*>(a.X) + ((ptrdiff_t)bb * a.N + nn - PAD) * a.ldx;
-      const int dlim = a.N - nn, xlo = PAD - nn, xhi = min(a.N - nn + PAD, WB_BK + TAPS - 1);
+      const int nl = exist_s(bb);
+      const int dlim = nl - nn, xlo = PAD - nn, xhi = min(nl - nn + PAD, WB_BK + TAPS - 1);
       char* const ibase = smem_b + img * DMA_IMGB;
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
@@ -2096,10 +2114,10 @@ int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, voi
 }
 
 // G (fp32, caller-initialised, the PARAMETER's own layout (Cout, Cin, taps)) += dY^T * shift(X): a weight gradient, or a
-// pre-zeroed / running `.grad` view to accumulate into.
+// pre-zeroed / running `.grad` view to accumulate into.  rows_exist (optional [B]): dY and X rows n >= rows_exist[b] read as zero.
 int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
                   int B, int N, int Cin, int Cout, int taps, const int* lens, int skip_halo,
-                  int bf16, int dy_bf16, int x_bf16, float* dbias, void* stream) {
+                  int bf16, int dy_bf16, int x_bf16, float* dbias, const int* rows_exist, void* stream) {
   DX_REQUIRE(dY && X && G, "dx_conv_wgrad: null pointer");
   DX_REQUIRE(bf16 || !(dy_bf16 || x_bf16), "dx_conv_wgrad: bf16 storage needs bf16 operand mode");
   const bool bf16_ok = (Cin % 8) == 0 && (ldx % 8) == 0 && (Cout % 8) == 0 && (ldy % 8) == 0;
@@ -2121,7 +2139,7 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
     constexpr int target_k1 = 192;
     const int ksplit = std::max(1, std::min(total_chunks, dx_cdiv(wide ? target_wide : (taps == 1 ? target_k1 : target_blocks), tiles)));
     WgradBatchArgs a{};
-    a.job[0] = WgradJobDev{dY, X, G, dbias, lens, ldy, ldx, B, N, Cin, Cout, skip_halo, 0};
+    a.job[0] = WgradJobDev{dY, X, G, dbias, lens, ldy, ldx, B, N, Cin, Cout, skip_halo, 0, rows_exist};
     a.ksplit = ksplit;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(tiles, 1, ksplit);
@@ -2145,7 +2163,7 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
   const int tiles = dx_cdiv(Cout, TILE) * dx_cdiv(Cin, TILE);
   const int total_chunks = B * dx_cdiv(N, WG_BK);
   int ksplit = std::max(1, std::min(total_chunks, dx_cdiv(1024, tiles * taps)));
-  WgradArgs a{(const float*)dY, ldy, (const float*)X, ldx, G, B, N, Cin, Cout, ksplit, lens, skip_halo, dbias};
+  WgradArgs a{(const float*)dY, ldy, (const float*)X, ldx, G, B, N, Cin, Cout, ksplit, lens, skip_halo, dbias, rows_exist};
   hipStream_t s = (hipStream_t)stream;
   dx_prof_begin(DX_PROF_WGRAD_GEMM, s);
   if (taps == 3) hipLaunchKernelGGL(wgrad_kernel<3>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
@@ -2160,6 +2178,7 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
 struct DxWgradJob {       // mirrors include/daft_exprt_hip.h
   const void* dY; const void* X; float* G; float* dbias; const int* lens;
   int ldy, ldx, B, N, Cin, Cout, skip_halo, reserved;
+  const int* rows_exist;
 };
 int dx_conv_wgrad_batched(const void* jobs_, int njobs, int taps, int dy_bf16, int x_bf16, void* stream) {
   const DxWgradJob* jobs = reinterpret_cast<const DxWgradJob*>(jobs_);
@@ -2175,7 +2194,7 @@ int dx_conv_wgrad_batched(const void* jobs_, int njobs, int taps, int dy_bf16, i
                "dx_conv_wgrad_batched: job %d: Cin must be a multiple of 128, Cout / ld* of 8 (Cin=%d Cout=%d)", i, j.Cin, j.Cout);
     DX_REQUIRE(((uintptr_t)j.X % 16) == 0 && ((uintptr_t)j.dY % 16) == 0, "dx_conv_wgrad_batched: job %d: pointers must be 16-byte aligned", i);
     DX_REQUIRE(j.skip_halo < 0 || j.lens, "dx_conv_wgrad_batched: job %d: skip_halo needs lens", i);
-    a.job[i] = WgradJobDev{j.dY, j.X, j.G, j.dbias, j.lens, j.ldy, j.ldx, j.B, j.N, j.Cin, j.Cout, j.skip_halo, 0};
+    a.job[i] = WgradJobDev{j.dY, j.X, j.G, j.dbias, j.lens, j.ldy, j.ldx, j.B, j.N, j.Cin, j.Cout, j.skip_halo, 0, j.rows_exist};
     const int t = dx_cdiv(j.Cout, TILE) * (j.Cin / 128);
     tiles = std::max(tiles, t);
     tile_jobs += t;

@@ -50,16 +50,18 @@ __global__ __launch_bounds__(256) void mel_stats_kernel(const float* __restrict_
 
 // smoothed energy difference; des = 2 * (smooth(ep) - smooth(et)) * [t < len];  esum += diff^2 * mask
 __global__ __launch_bounds__(256) void energy_diff_kernel(const float* __restrict__ ep, const float* __restrict__ et, const int* __restrict__ lens,
-                                                          float* __restrict__ des, float* __restrict__ esum, int T) {
+                                                          float* __restrict__ des, float* __restrict__ esum, int T,
+                                                          const int* __restrict__ rows_exist) {
   __shared__ float scratch[4];
   const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  const int TE = rows_exist ? min(rows_exist[b], T) : T;   // frames beyond it are the pooling's zero padding
   float e = 0.f;
   if (t < T) {
     float a = 0.f, c = 0.f;
 #pragma unroll
     for (int k = -2; k <= 2; ++k) {
       const int u = t + k;
-      if (u >= 0 && u < T) { a += ep[(size_t)b * T + u]; c += et[(size_t)b * T + u]; }
+      if (u >= 0 && u < TE) { a += ep[(size_t)b * T + u]; c += et[(size_t)b * T + u]; }
     }
     const float diff = a / 5.f - c / 5.f;       // AvgPool1d counts the zero padding (count_include_pad=True)
     const bool valid = t < lens[b];
@@ -180,9 +182,9 @@ int dx_mel_stats(const float* mel_pred, const float* mel_target, float* ep, floa
   return DX_OK;
 }
 
-int dx_energy_diff(const float* ep, const float* et, const int* lens, float* des, float* esum, int B, int T, void* stream) {
+int dx_energy_diff(const float* ep, const float* et, const int* lens, float* des, float* esum, int B, int T, const int* rows_exist, void* stream) {
   DX_REQUIRE(ep && et && lens && des && esum && B > 0 && T > 0, "dx_energy_diff: bad arguments");
-  hipLaunchKernelGGL(energy_diff_kernel, dim3(dx_cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, ep, et, lens, des, esum, T);
+  hipLaunchKernelGGL(energy_diff_kernel, dim3(dx_cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, ep, et, lens, des, esum, T, rows_exist);
   DX_LAUNCH_CHECK("dx_energy_diff");
   return DX_OK;
 }

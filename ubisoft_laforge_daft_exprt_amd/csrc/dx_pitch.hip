@@ -34,6 +34,7 @@ __device__ __forceinline__ int pc_off(int row, int slot) { return row * 128 + ((
 struct PitchArgs {
   const float* mel; float* dmel; int B, M, T;          // (B, M, T) fp32, M = 80
   const int* lens;
+  const int* rows_exist;                               // optional [B]: frames n >= rows_exist[b] do not exist (zero padding), although T are stored
   const dx_h16* w0; const dx_h16* w1; const dx_h16* w2;   // forward: the forward packs of layers 0..2; backward: the backward packs of layers 0..2
   const float* b0; const float* b1; const float* b2;
   const float* s0; const float* s1; const float* s2;   // BatchNorm scale (eval mode, folded)
@@ -148,12 +149,13 @@ __global__ __launch_bounds__(512) void pitch_fwd_kernel(const PitchArgs a) {
     int b, n0;
     pc_find_tile(pre, a.B, tile, b, n0);
     b = __builtin_amdgcn_readfirstlane(b); n0 = __builtin_amdgcn_readfirstlane(n0);
+    const int TE = a.rows_exist ? min(a.rows_exist[b], a.T) : a.T;   // frames of this utterance that exist
     __syncthreads();                                   // the previous tile's readers of the images / scratch are done
     // ---- window of the mel -> image A (channels 0..79 real, 80..95 zero), sign-bit staging area zeroed -----------------------------------
     for (int u = tid; u < 96 * PC_IR; u += 512) {      // the first layer walks 96 input channels (three K steps): channels M..95 are zeros
       const int c = u / PC_IR, p = u - c * PC_IR;
       const int n = n0 - 4 + p;
-      const float v = (c < a.M && n >= 0 && n < a.T) ? a.mel[((size_t)b * a.M + c) * a.T + n] : 0.f;
+      const float v = (c < a.M && n >= 0 && n < TE) ? a.mel[((size_t)b * a.M + c) * a.T + n] : 0.f;
       *reinterpret_cast<dx_h16*>(imgA + (c >> 6) * PC_CHUNK + pc_off(p, (c & 63) >> 3) + (c & 7) * 2) = (dx_h16)v;
     }
     for (int u = tid; u < PC_MASK / 4; u += 512) mask_s[u] = 0u;
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(512) void pitch_fwd_kernel(const PitchArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int row = base + 16 * j + r, n = n0 - 4 + row;
-          const bool exists = n >= 0 && n < a.T;
+          const bool exists = n >= 0 && n < TE;
           float x[4];
           unsigned bits = 0;
 #pragma unroll
@@ -255,23 +257,24 @@ __global__ __launch_bounds__(512) void pitch_bwd_kernel(const PitchArgs a) {
     int b, n0;
     pc_find_tile(pre, a.B, tile, b, n0);
     b = __builtin_amdgcn_readfirstlane(b); n0 = __builtin_amdgcn_readfirstlane(n0);
+    const int TE = a.rows_exist ? min(a.rows_exist[b], a.T) : a.T;   // frames of this utterance that exist
     __syncthreads();
     // ---- window of dpp and of the sign bits ----------------------------------------------------------------------------------------------
     for (int p = tid; p < PC_IR + 2; p += 512) {
       const int n = n0 - 4 + p;
-      grow[p] = (n >= 0 && n < a.T) ? a.dpp[(size_t)b * a.T + n] : 0.f;
+      grow[p] = (n >= 0 && n < TE) ? a.dpp[(size_t)b * a.T + n] : 0.f;
     }
     for (int u = tid; u < 3 * PC_IR * 8; u += 512) {
       const int d = u & 7, row = (u >> 3) % PC_IR, l = u / (8 * PC_IR);
       const int n = n0 - 4 + row;
-      mask_s[u] = (n >= 0 && n < a.T) ? a.masks[(((size_t)b * a.T + n) * 3 + l) * 8 + d] : 0u;
+      mask_s[u] = (n >= 0 && n < TE) ? a.masks[(((size_t)b * a.T + n) * 3 + l) * 8 + d] : 0u;
     }
     __syncthreads();
     // ---- d(x2)[m][c] = sum_t w3[c][t] g[m - t + 1]; x scale2 x mask2 -> image A, rows 1 .. 128 ----------------------------------------------------
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int row = 1 + (tid >> 5) + 16 * k, n = n0 - 4 + row;
-      const bool exists = n >= 0 && n < a.T;
+      const bool exists = n >= 0 && n < TE;
       const float g0 = grow[row + 1], g1 = grow[row], g2 = grow[row - 1];         // taps 0, 1, 2 meet g[m + 1], g[m], g[m - 1]
       const unsigned mb = (mask_s[(2 * PC_IR + row) * 8 + (vslot >> 2)] >> ((vslot & 3) * 8)) & 0xffu;
       float v[8];
@@ -305,7 +308,7 @@ __global__ __launch_bounds__(512) void pitch_bwd_kernel(const PitchArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int row = base + 16 * j + r, n = n0 - 4 + row;
-          const bool exists = n >= 0 && n < a.T && row < PC_IR;
+          const bool exists = n >= 0 && n < TE && row < PC_IR;
           const unsigned mb = exists ? (mask_s[(ml * PC_IR + row) * 8 + wave] >> (i * 16 + 4 * g)) & 0xfu : 0u;
           float x[4];
 #pragma unroll
@@ -320,7 +323,7 @@ __global__ __launch_bounds__(512) void pitch_bwd_kernel(const PitchArgs a) {
       f32x4 acc[1][8];
       pc_mfma_pass<8, 1>(a.w0, 8, 8, wave, imgA, 4, lane, acc);                    // backward pack of layer 0: rows 80 -> 128, K 256
       const int ch0 = wave * 16 + 4 * g;
-      const int len_b = min(a.lens[b], a.T);           // tokens beyond the length: the model masks their gradient, nothing is written there
+      const int len_b = min(a.lens[b], TE);            // tokens beyond the length: the model masks their gradient, nothing is written there
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int p = 16 * j + r, n = n0 + p;
@@ -340,14 +343,16 @@ extern "C" {
 
 // pp (B, T) = the frozen predictor on mel (B, 80, T); masks (B, T, 3, 8) uint32 for dx_pitch_chain_bwd.  w0..w2: forward packs of the three
 // 256-wide convolutions (dx_pack_weights, 16-bit), b*: biases, s* / t*: folded BatchNorm scale / shift, w3: row 0 of the last conv's weight in
-// checkpoint layout (256, 3) fp32, b3: its bias.  Replaces loss.py:131-136 applied through dx_conv_gemm / dx_channel_affine / dx_transpose.
+// checkpoint layout (256, 3) fp32, b3: its bias.  rows_exist (optional [B]): frames n >= rows_exist[b] are the convolutions' zero padding
+// (the mel read there is ignored).  Replaces loss.py:131-136 applied through dx_conv_gemm / dx_channel_affine / dx_transpose.
 int dx_pitch_chain_fwd(const float* mel, int B, int M, int T, const int* lens, const void* w0, const void* w1, const void* w2,
                        const float* b0, const float* b1, const float* b2, const float* s0, const float* s1, const float* s2,
-                       const float* t0, const float* t1, const float* t2, const float* w3, float b3, float* pp, void* masks, void* stream) {
+                       const float* t0, const float* t1, const float* t2, const float* w3, float b3, float* pp, void* masks,
+                       const int* rows_exist, void* stream) {
   DX_REQUIRE(mel && lens && w0 && w1 && w2 && b0 && b1 && b2 && s0 && s1 && s2 && t0 && t1 && t2 && w3 && pp && masks, "dx_pitch_chain_fwd: null pointer");
   DX_REQUIRE(B > 0 && B <= PC_MAX_B && T > 0 && M > 64 && M <= 96, "dx_pitch_chain_fwd: B <= %d and 64 < n_mel <= 96 (the first layer's pack must be 128 wide: B=%d M=%d)", PC_MAX_B, B, M);
   PitchArgs a{};
-  a.mel = mel; a.B = B; a.M = M; a.T = T; a.lens = lens;
+  a.mel = mel; a.B = B; a.M = M; a.T = T; a.lens = lens; a.rows_exist = rows_exist;
   a.w0 = (const dx_h16*)w0; a.w1 = (const dx_h16*)w1; a.w2 = (const dx_h16*)w2;
   a.b0 = b0; a.b1 = b1; a.b2 = b2; a.s0 = s0; a.s1 = s1; a.s2 = s2; a.t0 = t0; a.t1 = t1; a.t2 = t2;
   a.w3 = w3; a.b3 = b3; a.pp = pp; a.masks = (unsigned*)masks;
@@ -366,11 +371,12 @@ int dx_pitch_chain_fwd(const float* mel, int B, int M, int T, const int* lens, c
 // dmel (B, 80, T) += d(loss)/d(mel) through the frozen predictor, from dpp (B, T) and the forward's masks.  w0..w2: the BACKWARD packs of the
 // three 256-wide convolutions.  Replaces loss.py's input-gradient chain (four dx_conv_gemm(transpose) launches + dx_transpose(add)).
 int dx_pitch_chain_bwd(const float* dpp, int B, int M, int T, const int* lens, const void* w0, const void* w1, const void* w2,
-                       const float* s0, const float* s1, const float* s2, const float* w3, const void* masks, float* dmel, void* stream) {
+                       const float* s0, const float* s1, const float* s2, const float* w3, const void* masks, float* dmel,
+                       const int* rows_exist, void* stream) {
   DX_REQUIRE(dpp && lens && w0 && w1 && w2 && s0 && s1 && s2 && w3 && masks && dmel, "dx_pitch_chain_bwd: null pointer");
   DX_REQUIRE(B > 0 && B <= PC_MAX_B && T > 0 && M > 64 && M <= 96, "dx_pitch_chain_bwd: B <= %d and 64 < n_mel <= 96 (B=%d M=%d)", PC_MAX_B, B, M);
   PitchArgs a{};
-  a.dpp = dpp; a.B = B; a.M = M; a.T = T; a.lens = lens; a.dmel = dmel;
+  a.dpp = dpp; a.B = B; a.M = M; a.T = T; a.lens = lens; a.dmel = dmel; a.rows_exist = rows_exist;
   a.w0 = (const dx_h16*)w0; a.w1 = (const dx_h16*)w1; a.w2 = (const dx_h16*)w2;
   a.s0 = s0; a.s1 = s1; a.s2 = s2; a.w3 = w3; a.masks = (unsigned*)const_cast<void*>(masks);
   static bool configured = false;

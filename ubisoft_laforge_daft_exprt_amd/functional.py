@@ -59,7 +59,8 @@ class Lengths:
         # optional device int32 [B]: rows n >= exist[b] of utterance b do not exist for the k = 3 convolutions (they read zero), although
         # the tensors have more rows.  None = the reference's padded grid (every utterance has max(lengths) rows).  Set by
         # inference.GraphedSynthesizer: padded-shape buckets (exist = the batch's true longest length) and the batched accent encoder
-        # (exist = lengths: every reference behaves as if it were run alone, scripts/synthesize.py:420-448).
+        # (exist = lengths: every reference behaves as if it were run alone, scripts/synthesize.py:420-448), and by trainer.Trainer in
+        # bucketed mode (exist = the batch's true longest length; the backward Functions pass it to every k = 3 launch as well).
         self.exist = None
 
 
@@ -210,8 +211,7 @@ class FFTBlockFn(torch.autograd.Function):
     def backward(ctx, dy2, _dqkv_next=None):
         x, film, qkv, att, lse, z1, mean1, rstd1, y1, h, z2, mean2, rstd2, ln1_w, ln1_b, ln2_w, ln2_b = ctx.saved_tensors
         lens, packs = ctx.lens, ctx.packs
-        if lens.exist is not None:
-            raise NotImplementedError('Lengths.exist (padded-shape buckets / stand-alone rows) is a forward-only feature')
+        E = lens.exist                             # rows at or beyond it do not exist for the k = 3 launches (None: all N rows do)
         p_attn, p_conv, s_attn, s_ln1, s_ln2 = ctx.drop
         dy2 = dy2.contiguous()
         L = lens.i32
@@ -233,8 +233,8 @@ class FFTBlockFn(torch.autograd.Function):
                 dy2, z2, mean2, rstd2, ln2_w, ln2_b, film, packs['c1'], packs['c2'], L, h, z1, mean1, rstd1, ln1_w, ln1_b,
                 seed2=s_ln2, p2=p_conv, seed1=s_ln1, p1=p_attn, seed_offset=so, prec=prec, arena=arena,
                 sinks={'ln2_w': g('ln2_w'), 'ln2_b': g('ln2_b'), 'ln1_w': g('ln1_w'), 'ln1_b': g('ln1_b')},
-                out_pack=packs['out'], hmask=ctx.hmask)
-            dc2_w, dc2_b = ops.conv_wgrad(dff, h, packs['c2'], L, 0, arena=arena, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, defer=True)
+                out_pack=packs['out'], hmask=ctx.hmask, rows_exist=E)
+            dc2_w, dc2_b = ops.conv_wgrad(dff, h, packs['c2'], L, 0, arena=arena, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, defer=True, rows_exist=E)
         else:
             datt = None
             r2 = ops.ln_bwd(dy2, z2, mean2, rstd2, ln2_w, ln2_b, film, L, want_da=p_conv > 0, seed_pre=s_ln2, seed_offset=so, prec=prec,
@@ -242,14 +242,15 @@ class FFTBlockFn(torch.autograd.Function):
             dz2, da2, dln2_w, dln2_b, dfilm = r2[:5]
             dff = r2[5] if sh else (da2 if da2 is not None else dz2)      # gradient w.r.t. the conv2 output, as the GEMMs read it
             # (before the pair below accumulates onto dz2 in place: without a 16-bit shadow and without dropout dff IS dz2)
-            dc2_w, dc2_b = ops.conv_wgrad(dff, h, packs['c2'], L, 0, arena=arena, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, defer=True)
-            dh = ops.conv_gemm(dff, packs['c2'], None, transpose=True, relu_aux=h, lens=L, halo=1, out_dtype=h.dtype, prec=prec)
-            dy1 = ops.conv_gemm(dh, packs['c1'], None, transpose=True, out=dz2, accumulate=True, lens=L, halo=0, prec=prec)  # + residual branch
+            dc2_w, dc2_b = ops.conv_wgrad(dff, h, packs['c2'], L, 0, arena=arena, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, defer=True, rows_exist=E)
+            dh = ops.conv_gemm(dff, packs['c2'], None, transpose=True, relu_aux=h, lens=L, halo=1, out_dtype=h.dtype, prec=prec, rows_exist=E)
+            dy1 = ops.conv_gemm(dh, packs['c1'], None, transpose=True, out=dz2, accumulate=True, lens=L, halo=0, prec=prec,  # + residual branch
+                                rows_exist=E)
             r1 = ops.ln_bwd(dy1, z1, mean1, rstd1, ln1_w, ln1_b, None, L, want_da=p_attn > 0, seed_pre=s_ln1, seed_offset=so, prec=prec,
                             p_pre=p_attn, arena=arena, w_sink=g('ln1_w'), b_sink=g('ln1_b'), shadow=sh)
             dz1, da1, dln1_w, dln1_b = r1[:4]
             dproj = r1[5] if sh else (da1 if da1 is not None else dz1)
-        dc1_w, dc1_b = ops.conv_wgrad(dh, y1, packs['c1'], L, 1, arena=arena, w_sink=g('c1_w'), b_sink=g('c1_b'), prec=prec, defer=True)
+        dc1_w, dc1_b = ops.conv_wgrad(dh, y1, packs['c1'], L, 1, arena=arena, w_sink=g('c1_w'), b_sink=g('c1_b'), prec=prec, defer=True, rows_exist=E)
         dout_w, dout_b = ops.conv_wgrad(dproj, att, packs['out'], L, 0, arena=arena, w_sink=g('out_w'), b_sink=g('out_b'), prec=prec, defer=True)
         if datt is None:
             datt = ops.conv_gemm(dproj, packs['out'], None, transpose=True, lens=L, halo=0, prec=prec, out_dtype=att.dtype)   # stored like the context
@@ -307,7 +308,7 @@ class AccentFront0Fn(torch.autograd.Function):
         g = sk.get
         dz0, _, dl0_w, dl0_b, _ = ops.ln_bwd(dy0.contiguous(), h0, m0, r0, l0_w, l0_b, None, L, relu_mask=True, seed_post=ctx.seed, p_post=p,
                                               seed_offset=ctx.seed_offset, prec=ctx.prec, w_sink=g('l0_w'), b_sink=g('l0_b'), halo=2, arena=arena)
-        dc0_w, dc0_b = ops.conv_wgrad(dz0, x0, packs['p0'], L, 2, w_sink=g('c0_w'), b_sink=g('c0_b'), prec=ctx.prec, arena=arena)
+        dc0_w, dc0_b = ops.conv_wgrad(dz0, x0, packs['p0'], L, 2, w_sink=g('c0_w'), b_sink=g('c0_b'), prec=ctx.prec, arena=arena, rows_exist=lens.exist)
         return None, None, None, None, None, dc0_w, dc0_b, dl0_w, dl0_b
 
 
@@ -348,12 +349,13 @@ class AccentFront12Fn(torch.autograd.Function):
         g = sk.get
         dz2, _, dl2_w, dl2_b, _ = ops.ln_bwd(dout, h2, m2, r2, l2_w, l2_b, None, L, relu_mask=True, seed_post=seeds[1], p_post=p, seed_offset=so, prec=prec,
                                               w_sink=g('l2_w'), b_sink=g('l2_b'), halo=0, arena=arena)
-        dc2_w, dc2_b = ops.conv_wgrad(dz2, y1, packs['p2'], L, 0, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, arena=arena)
-        dy1 = ops.conv_gemm(dz2, packs['p2'], None, transpose=True, lens=L, halo=1, out_dtype=h1.dtype, prec=prec)
+        E = lens.exist                             # (rows >= E: their input gradients are written as zero, so the halo-1 LayerNorm sees none)
+        dc2_w, dc2_b = ops.conv_wgrad(dz2, y1, packs['p2'], L, 0, w_sink=g('c2_w'), b_sink=g('c2_b'), prec=prec, arena=arena, rows_exist=E)
+        dy1 = ops.conv_gemm(dz2, packs['p2'], None, transpose=True, lens=L, halo=1, out_dtype=h1.dtype, prec=prec, rows_exist=E)
         dz1, _, dl1_w, dl1_b, _ = ops.ln_bwd(dy1, h1, m1, r1, l1_w, l1_b, None, L, relu_mask=True, seed_post=seeds[0], p_post=p, seed_offset=so, prec=prec,
                                               w_sink=g('l1_w'), b_sink=g('l1_b'), halo=1, arena=arena)
-        dc1_w, dc1_b = ops.conv_wgrad(dz1, y0, packs['p1'], L, 1, w_sink=g('c1_w'), b_sink=g('c1_b'), prec=prec, arena=arena)
-        dy0 = ops.conv_gemm(dz1, packs['p1'], None, transpose=True, lens=L, halo=2, out_dtype=y0.dtype, prec=prec)
+        dc1_w, dc1_b = ops.conv_wgrad(dz1, y0, packs['p1'], L, 1, w_sink=g('c1_w'), b_sink=g('c1_b'), prec=prec, arena=arena, rows_exist=E)
+        dy0 = ops.conv_gemm(dz1, packs['p1'], None, transpose=True, lens=L, halo=2, out_dtype=y0.dtype, prec=prec, rows_exist=E)
         return (dy0, None, None, None, None, None, None, None,
                 dc1_w, dc1_b, dl1_w, dl1_b, dc2_w, dc2_b, dl2_w, dl2_b, dwe, dbe, dwp, dbp)
 

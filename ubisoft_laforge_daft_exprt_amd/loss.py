@@ -84,7 +84,7 @@ class _LossFn(torch.autograd.Function):
         ep, et, sums = ops.mel_stats(mel_pred, mel_target, arena=arena)
         des = esum = None
         if cfg['ecw'] > 0:
-            des, esum = ops.energy_diff(ep, et, lens.i32, arena=arena)
+            des, esum = ops.energy_diff(ep, et, lens.i32, arena=arena, rows_exist=lens.exist)
         # energy term: ecw / (sum of valid lengths), the division done on the device (nothing host-side is frozen into a graph)
         need_grad = cfg.get('need_grad', True)       # False under no_grad (Trainer.validate): the terms only, none of the gradient launches
         # ``grad_scale``: d(what the caller differentiates) / d(total), known up front (a trainer: loss scale / accumulation steps).  Every
@@ -99,11 +99,11 @@ class _LossFn(torch.autograd.Function):
             frames_pitch = frames_pitch.contiguous()
             if ops.pitch_chain_applies(pitch_layers, mel_pred, prec):
                 # one launch each way (csrc/dx_pitch.hip): activations stay in LDS, the backward gets ReLU sign bits instead of activations
-                pp, masks = ops.pitch_chain_fwd(mel_pred, pitch_layers, lens.i32, prec, arena=arena)
+                pp, masks = ops.pitch_chain_fwd(mel_pred, pitch_layers, lens.i32, prec, arena=arena, rows_exist=lens.exist)
                 psum = ops.pitch_mse(pp, frames_pitch, lens.i32, arena=arena)
                 if need_grad:
                     g = ops.pitch_grad(pp, frames_pitch, lens.i32, psum, gs * cfg['pcw'], out=ops._zeros(arena, B, T, device=dev))
-                    ops.pitch_chain_bwd(g, masks, pitch_layers, lens.i32, prec, dmel)              # dmel is this function's own fresh tensor
+                    ops.pitch_chain_bwd(g, masks, pitch_layers, lens.i32, prec, dmel, rows_exist=lens.exist)   # dmel: this function's own fresh tensor
             else:
                 # layer by layer (the exact-fp32 mode, other architectures): channels-last; gradient flows through it to the mel only
                 x = ops.transpose(mel_pred)                                          # (B, T, M)
@@ -111,11 +111,12 @@ class _LossFn(torch.autograd.Function):
                 depth = len(pitch_layers) - 1                                       # stacked k=3 convs: halos 3, 2, 1, 0
                 hd = ops.hidden_dtype(prec)                                        # 16-bit modes: the 256-wide activations of the frozen predictor
                 for i, layer in enumerate(pitch_layers[:-1]):                      # (only ever GEMM operands / ReLU masks) are stored in 16 bits
-                    r = ops.conv_gemm(x, layer['pack'], layer['b'], relu=True, lens=lens.i32, halo=depth - i, prec=prec, out_dtype=hd)
+                    r = ops.conv_gemm(x, layer['pack'], layer['b'], relu=True, lens=lens.i32, halo=depth - i, prec=prec, out_dtype=hd,
+                                      rows_exist=lens.exist)
                     acts.append(r)
                     x = ops.channel_affine(r, layer['scale'], layer['shift'], prec=prec)
                 last = pitch_layers[-1]
-                pp = ops.conv_gemm(x, last['pack'], last['b'], lens=lens.i32, halo=0, prec=prec)      # (B, T, 4): channel 0 is the prediction
+                pp = ops.conv_gemm(x, last['pack'], last['b'], lens=lens.i32, halo=0, prec=prec, rows_exist=lens.exist)   # (B, T, 4): channel 0 = the prediction
                 psum = ops.pitch_mse(pp, frames_pitch, lens.i32, arena=arena)                          # (read and written in place: no slice copies)
                 if need_grad:
                     g = ops.pitch_grad(pp, frames_pitch, lens.i32, psum, gs * cfg['pcw'], out=ops._zeros(arena, B, T, 4, device=dev))
@@ -123,8 +124,8 @@ class _LossFn(torch.autograd.Function):
                     for k in range(len(pitch_layers) - 1, 0, -1):
                         prev = pitch_layers[k - 1]
                         g = ops.conv_gemm(g, pitch_layers[k]['pack'], None, transpose=True, post_scale=prev['scale'], post_shift=prev['zeros'],
-                                          relu_aux=acts[k - 1], lens=lens.i32, halo=depth - k + 1, prec=prec, out_dtype=hd)
-                    d = ops.conv_gemm(g, pitch_layers[0]['pack'], None, transpose=True, lens=lens.i32, halo=0, prec=prec)
+                                          relu_aux=acts[k - 1], lens=lens.i32, halo=depth - k + 1, prec=prec, out_dtype=hd, rows_exist=lens.exist)
+                    d = ops.conv_gemm(g, pitch_layers[0]['pack'], None, transpose=True, lens=lens.i32, halo=0, prec=prec, rows_exist=lens.exist)
                     dmel = ops.transpose(d, add_to=dmel)                                   # dmel is this function's own fresh tensor
         # the seven terms, the total and the two small gradients: one launch (was ~30 one-element ATen launches)
         terms, total, d_spk, d_pm = ops.loss_finalize(ce, dlogits, cfg['spk_weight'], pm, cfg['pmw'], sums, lens.i32, M, cfg['msw'],
@@ -195,6 +196,7 @@ class DaftExprtLoss(nn.Module):
         lens = output_lengths if isinstance(output_lengths, Lengths) else getattr(output_lengths, '_dx_lengths', None)
         if lens is None or lens.i64 is not output_lengths:     # (the model leaves its Lengths object on the tensor it returns)
             lens = Lengths(output_lengths, host=getattr(output_lengths, '_dx_host_lengths', None))
+            lens.exist = getattr(output_lengths, '_dx_rows_exist', None)
         pm = post_multipliers if (self.post_mult_weight != 0.0 and torch.is_tensor(post_multipliers)) else None
         # ``iteration``: the step number, or -- from a trainer that replays captured graphs -- the adversarial weight itself as a
         # device scalar it updates before every replay

@@ -395,8 +395,11 @@ class DaftExprt(nn.Module):
     @staticmethod
     def _lengths(t):
         """A fresh ``Lengths`` per forward call (never reused across calls: the tensor's contents may have changed), left on the tensor
-        object so that the loss, which is handed the same output-length tensor, does not build a second one (an int64 -> int32 launch)."""
+        object so that the loss, which is handed the same output-length tensor, does not build a second one (an int64 -> int32 launch).
+        ``t._dx_rows_exist`` (device int32 [B], set by a bucketed trainer.Trainer on its static length tensors): the rows that exist on this
+        axis although the batch tensors are allocated longer (Lengths.exist)."""
         obj = Lengths(t, host=getattr(t, '_dx_host_lengths', None))
+        obj.exist = getattr(t, '_dx_rows_exist', None)
         try:
             t._dx_lengths = obj
         except AttributeError:

@@ -368,11 +368,13 @@ def ff_pair_lnbwd(x, pack1: PackedWeight, pack2: PackedWeight, lens, aux, out, z
 
 
 def ff_block_bwd(dy2, z2, mean2, rstd2, ln2_w, ln2_b, film, pack1: PackedWeight, pack2: PackedWeight, lens, aux, z1, mean1, rstd1, ln1_w, ln1_b, *,
-                 seed2=0, p2=0.0, seed1=0, p1=0.0, seed_offset=None, halo=1, prec=None, arena=None, sinks=None, out_pack=None, hmask=None):
+                 seed2=0, p2=0.0, seed1=0, p1=0.0, seed_offset=None, halo=1, prec=None, arena=None, sinks=None, out_pack=None, hmask=None,
+                 rows_exist=None):
     """LayerNorm2-backward -> input-gradient pair -> LayerNorm1-backward in one launch (dx_ff_block_bwd).  ``sinks``: dict with optional
     pre-zeroed ``.grad`` tensors 'ln2_w', 'ln2_b', 'ln1_w', 'ln1_b'.  ``out_pack``: the attention out-projection's PackedWeight (128 x 128):
     the launch then also produces datt = dg1 x W_out.  Returns (dz1, dh, dg1_16bit, dg2_16bit, dfilm or None, dln2_w, dln2_b, dln1_w,
-    dln1_b, datt or None) -- the four affine gradients are None where a sink took them."""
+    dln1_b, datt or None) -- the four affine gradients are None where a sink took them.  ``rows_exist``: the forward's (see conv_gemm): rows
+    at or beyond it read as zero and get zero gradients."""
     prec = pack1.rt.precision if prec is None else prec
     B, N, D = dy2.shape
     Fc = pack1.cout
@@ -396,7 +398,7 @@ def ff_block_bwd(dy2, z2, mean2, rstd2, ln2_w, ln2_b, film, pack1: PackedWeight,
                                  _p(dg2), _p(acc['ln2_w']), _p(acc['ln2_b']), _p(dfilm), 256, seed2, float(p2),
                                  _p(i2.bwd), _p(i1.bwd), _p(aux), _rows(aux), _p(dh), _rows(dh), _p(dz1), B, N, Fc, _p(lens), int(halo),
                                  _p(z1), _p(mean1), _p(rstd1), _p(ln1_w), _p(ln1_b), _p(dg1), _p(acc['ln1_w']), _p(acc['ln1_b']),
-                                 seed1, float(p1), _p(wt), _p(datt), _p(seed_offset), _p(hmask), _stream())
+                                 seed1, float(p1), _p(wt), _p(datt), _p(seed_offset), _p(hmask), _p(rows_exist), _stream())
     ret = lambda k: None if sinks.get(k) is not None else acc[k]
     return dz1, dh, dg1, dg2, dfilm, ret('ln2_w'), ret('ln2_b'), ret('ln1_w'), ret('ln1_b'), datt
 
@@ -445,10 +447,11 @@ def _zeros(arena, *shape, device=None):
     return arena.take(*shape) if arena is not None else torch.zeros(*shape, dtype=torch.float32, device=device)
 
 
-def conv_wgrad(dy, x, pack: PackedWeight, lens=None, halo=-1, bias=True, arena=None, w_sink=None, b_sink=None, prec=None, defer=False):
+def conv_wgrad(dy, x, pack: PackedWeight, lens=None, halo=-1, bias=True, arena=None, w_sink=None, b_sink=None, prec=None, defer=False,
+               rows_exist=None):
     """(dW, db): gradient w.r.t. the (Cout, Cin[, taps]) parameter in its own layout, and the bias gradient (column sums of
     dY, accumulated by the same launch).  ``w_sink`` / ``b_sink``: pre-zeroed ``.grad`` tensors to accumulate into directly
-    (the corresponding return value is then None)."""
+    (the corresponding return value is then None).  ``rows_exist`` (device int32 [B]): rows of dy and x at or beyond it read as zero."""
     B_, N_ = (1, x.shape[0]) if x.dim() == 2 else (x.shape[0], x.shape[1])
     # the kernel accumulates in the parameter's own (Cout, Cin, taps) layout: straight into the sink, or into a fresh gradient
     g = w_sink if w_sink is not None else _zeros(arena, *pack.weight.shape, device=x.device)
@@ -462,16 +465,17 @@ def conv_wgrad(dy, x, pack: PackedWeight, lens=None, halo=-1, bias=True, arena=N
         # queued: launched with up to 7 other layers of the same kind by flush_wgrads (the trainer flushes at the end of every backward phase)
         key = (pack.taps, _is_bf16(dy), _is_bf16(x), prec)
         rt.wgrad_queue.setdefault(key, []).append(((_p(dy), _p(x), _p(g), _p(db), _p(lens), _rows(dy), _rows(x), B_, N_, pack.cin, pack.cout,
-                                                    int(halo), 0), (dy, x, g, db, lens)))
+                                                    int(halo), 0, _p(rows_exist)), (dy, x, g, db, lens, rows_exist)))
         return None, None
     _fn('dx_conv_wgrad', prec)(_p(dy), _rows(dy), _p(x), _rows(x), _p(g), B_, N_, pack.cin, pack.cout, pack.taps, _p(lens), int(halo),
-                               _half(prec), _is_bf16(dy), _is_bf16(x), _p(db), _stream())
+                               _half(prec), _is_bf16(dy), _is_bf16(x), _p(db), _p(rows_exist), _stream())
     return (None if w_sink is not None else g), (None if b_sink is not None else db)
 
 
 class _WgradJob(ctypes.Structure):          # DxWgradJob of include/daft_exprt_hip.h
     _fields_ = [(n, ctypes.c_void_p) for n in ('dY', 'X', 'G', 'dbias', 'lens')] + \
-               [(n, ctypes.c_int) for n in ('ldy', 'ldx', 'B', 'N', 'Cin', 'Cout', 'skip_halo', 'reserved')]
+               [(n, ctypes.c_int) for n in ('ldy', 'ldx', 'B', 'N', 'Cin', 'Cout', 'skip_halo', 'reserved')] + \
+               [('rows_exist', ctypes.c_void_p)]
 
 
 # layers per dx_conv_wgrad_batched launch (the library takes up to 32), by kernel size.  Measured in the C2 step: the k = 1 layers gain from
@@ -792,11 +796,11 @@ def mel_stats(mel_pred, mel_target, arena=None):
     return ep, et, sums
 
 
-def energy_diff(ep, et, lens, arena=None):
+def energy_diff(ep, et, lens, arena=None, rows_exist=None):
     B, T = ep.shape
     des = torch.empty_like(ep)
     esum = _zeros(arena, 1, device=ep.device)
-    lib().dx_energy_diff(_p(ep), _p(et), _p(lens), _p(des), _p(esum), B, T, _stream())
+    lib().dx_energy_diff(_p(ep), _p(et), _p(lens), _p(des), _p(esum), B, T, _p(rows_exist), _stream())
     return des, esum
 
 
@@ -854,8 +858,9 @@ def pitch_chain_applies(layers, mel, prec) -> bool:
             and all(l['scale'] is not None for l in layers[:3]))
 
 
-def pitch_chain_fwd(mel, layers, lens, prec, arena=None):
-    """(pp (B, T), masks) = the frozen pitch predictor on mel (B, n_mel, T) fp32 in one launch; ``masks`` feeds pitch_chain_bwd."""
+def pitch_chain_fwd(mel, layers, lens, prec, arena=None, rows_exist=None):
+    """(pp (B, T), masks) = the frozen pitch predictor on mel (B, n_mel, T) fp32 in one launch; ``masks`` feeds pitch_chain_bwd.
+    ``rows_exist`` (device int32 [B]): frames at or beyond it are the convolutions' zero padding."""
     B, M, T = mel.shape
     pp = _zeros(arena, B, T, device=mel.device)          # tokens >= len are never written (and never read unmasked)
     masks = torch.empty(B, T, 3, 8, dtype=torch.int32, device=mel.device)
@@ -864,17 +869,17 @@ def pitch_chain_fwd(mel, layers, lens, prec, arena=None):
                                     _p(layers[0]['b']), _p(layers[1]['b']), _p(layers[2]['b']),
                                     _p(layers[0]['scale']), _p(layers[1]['scale']), _p(layers[2]['scale']),
                                     _p(layers[0]['shift']), _p(layers[1]['shift']), _p(layers[2]['shift']),
-                                    _p(layers[3]['w']), float(layers[3]['b3']), _p(pp), _p(masks), _stream())
+                                    _p(layers[3]['w']), float(layers[3]['b3']), _p(pp), _p(masks), _p(rows_exist), _stream())
     return pp, masks
 
 
-def pitch_chain_bwd(dpp, masks, layers, lens, prec, dmel):
+def pitch_chain_bwd(dpp, masks, layers, lens, prec, dmel, rows_exist=None):
     """dmel (B, n_mel, T) += the gradient of the frozen predictor's output with respect to its input mel, from dpp (B, T)."""
     B, M, T = dmel.shape
     img = [l['pack'].image(prec) for l in layers[:3]]
     _fn('dx_pitch_chain_bwd', prec)(_p(dpp), B, M, T, _p(lens), _p(img[0].bwd), _p(img[1].bwd), _p(img[2].bwd),
                                     _p(layers[0]['scale']), _p(layers[1]['scale']), _p(layers[2]['scale']),
-                                    _p(layers[3]['w']), _p(masks), _p(dmel), _stream())
+                                    _p(layers[3]['w']), _p(masks), _p(dmel), _p(rows_exist), _stream())
     return dmel
 
 

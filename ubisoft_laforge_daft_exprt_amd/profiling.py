@@ -97,7 +97,7 @@ def price(name, a, geom: Geometry):
         from . import ops
         jobs = ops.WGRAD_BATCH_LOG.get(a['jobs'], (None, []))[1]       # the descriptors of this launch (kept while a timer is installed)
         flops = byt = 0
-        for (_dy, _x, _g, _db, lens, _ldy, _ldx, B, N, Cin, Cout, _halo, _r) in jobs:
+        for (_dy, _x, _g, _db, lens, _ldy, _ldx, B, N, Cin, Cout, *_rest) in jobs:
             rows = geom.rows(B, N, lens is not None)
             flops += 2.0 * a['taps'] * Cin * Cout * rows
             byt += rows * (Cout * (2 if a['dy_bf16'] else 4) + Cin * (2 if a['x_bf16'] else 4)) + a['taps'] * Cin * Cout * 4

@@ -27,6 +27,12 @@ MI355X-specific structure of one update (``use_graphs=True``, the default):
     optimiser step, and at the top of ``train_step`` when anything else changed the parameters (``load_checkpoint``).
   * the optimiser (fused Adam, LR by value) and the one-launch weight re-pack stay outside the graphs: ten launches.
   * ``validate`` = train.py:163-209: eval-mode forward + loss under ``no_grad`` as one captured graph per padded shape.
+  * ``bucket=(l_step, t_step)``: the reference's collate pads every batch to its own longest utterance, so the exact padded shape
+    changes almost every step and every new shape costs an eager step plus a capture.  In bucketed mode a micro-batch whose longest
+    utterances are (L, T) runs at (L rounded up to l_step, T rounded up to t_step): the padded inputs get zero tails, and device
+    int32 vectors ``exist`` = L / T (Lengths.exist, carried on the length tensors as ``_dx_rows_exist``) tell every k = 3 launch,
+    forward and backward, that rows beyond them do not exist.  With dropout off the step computes what the exact-shape step
+    computes ("logical rows vs stride"); dropout masks are drawn over the bucket's row stride instead.
 
 Like the reference, a NaN loss does not stop the update (train.py:445-450 only skips LOGGING); ``nan_steps`` counts them.
 The iteration counter starts at 1 (train.py:286) and the learning rate of step ``i`` is ``update_learning_rate(hparams, i)``.
@@ -59,6 +65,30 @@ def group_of(name: str, levels: int = 3) -> int:
     return min(levels, 2)
 
 
+def pad_batch(inputs, Lb, Tb):
+    """A parsed micro-batch (DaftExprt.parse_batch) whose longest utterances are (L, T), padded with zeros to (Lb >= L, Tb >= T) rows:
+    -> (inputs, targets) of the padded shape.  Its two length tensors are fresh objects carrying ``_dx_rows_exist`` (device int32 [B] =
+    L / T: rows beyond them do not exist for the k = 3 launches, Lengths.exist) and the PADDED shape's host lengths (``_dx_host_lengths``:
+    host metadata only sizes tensors, so a graph captured on one batch serves every batch of its bucket)."""
+    B, L = inputs[0].shape
+    T = inputs[8].shape[2]
+    if Lb < L or Tb < T:
+        raise ValueError(f'cannot pad a ({L}, {T}) batch to ({Lb}, {Tb})')
+    pad = lambda t, n: torch.nn.functional.pad(t, (0, n - t.shape[-1])) if t.shape[-1] != n else t
+    padded = list(inputs)
+    for i in (0, 1, 2, 3, 4):                         # symbols, durations (float, int), symbol energy / pitch: (B, L)
+        padded[i] = pad(inputs[i], Lb)
+    for i in (6, 7, 8):                               # frame energy / pitch (B, T), mels (B, n_mel, T)
+        padded[i] = pad(inputs[i], Tb)
+    for i, n, e in ((5, Lb, L), (9, Tb, T)):
+        lt = inputs[i].clone()                        # a fresh tensor object: no Lengths cached on it by an earlier call
+        lt._dx_host_lengths = [n] * B
+        lt._dx_rows_exist = torch.full((B,), e, dtype=torch.int32, device=lt.device)
+        padded[i] = lt
+    padded = tuple(padded)
+    return padded, (padded[1], padded[3], padded[4], padded[8], padded[9], padded[10])      # the targets alias the inputs, as parse_batch builds them
+
+
 PHASE_NAMES = ('A: forward, loss, backward of decoder / upsampler / phoneme encoder / style adapter / classifier',
                'B: backward of the accent encoder\'s four FFT blocks', 'C: backward of prenet layers 2 and 1 (+ prosody embeddings)',
                'D: backward of prenet layer 0')
@@ -71,9 +101,11 @@ class _StepGraphs:
 
 class Trainer:
     def __init__(self, model, criterion, hparams, conditioner=None, process_group=None, bucket_mb=16.0, grad_sink=True,
-                 use_graphs=True, max_graphs=16, cuts='auto'):
+                 use_graphs=True, max_graphs=16, cuts='auto', bucket=None):
         """``cuts``: how many times the backward is cut into phases (0..3) so that a finished phase's gradient buckets are exchanged
-        while the next phase computes.  'auto' = 3 when there is more than one rank, 0 (one phase, one graph) otherwise."""
+        while the next phase computes.  'auto' = 3 when there is more than one rank, 0 (one phase, one graph) otherwise.
+        ``bucket``: None (graphs keyed on each micro-batch's exact padded shape) or (l_step, t_step), e.g. (inference.L_STEP,
+        inference.T_STEP) = (16, 64): micro-batches are padded up to multiples of these and one graph serves every batch of a bucket."""
         self.model, self.criterion, self.hparams, self.conditioner = model, criterion, hparams, conditioner
         self.device = next(model.parameters()).device
         import torch.distributed as dist
@@ -84,6 +116,11 @@ class Trainer:
         self.reducer = GradientReducer(model, bucket_mb=bucket_mb, process_group=process_group, grad_sink=grad_sink,
                                        group_of=lambda n: group_of(n, self.cut_levels), explicit_launch=True)
         self.use_graphs, self.max_graphs = bool(use_graphs), int(max_graphs)
+        if bucket is not None:
+            bucket = (int(bucket[0]), int(bucket[1]))
+            if bucket[0] < 1 or bucket[1] < 1:
+                raise ValueError(f'bucket steps must be positive, got {bucket!r}')
+        self.bucket = bucket
         # the FFT blocks' weight gradients go straight into the buckets (sink) and have no consumer before the exchange, so they are
         # queued during backward and launched 8 layers at a time (ops.flush_wgrads, after every backward phase below)
         model.runtime.defer_wgrad = bool(grad_sink)
@@ -188,9 +225,16 @@ class Trainer:
         return tot, terms, [phase(level) for level in range(1, self.cut_levels + 1)]
 
     def _parse(self, batches):
-        parsed = [self.model.parse_batch(self.device, b) for b in batches]
+        parsed = [self._bucketed(*self.model.parse_batch(self.device, b)) for b in batches]
         key = (self.model.runtime.precision,) + tuple((tuple(i[0].shape), tuple(i[8].shape)) for i, _ in parsed)   # (B, L_max), (B, n_mel, T_max) per micro-batch
         return parsed, key
+
+    def _bucketed(self, inputs, targets):
+        """Bucketed mode: the parsed micro-batch padded up to its bucket (pad_batch); without a bucket it is returned as it is."""
+        if self.bucket is None:
+            return inputs, targets
+        L, T = inputs[0].shape[1], inputs[8].shape[2]
+        return pad_batch(inputs, -(-L // self.bucket[0]) * self.bucket[0], -(-T // self.bucket[1]) * self.bucket[1])
 
     def _static_inputs(self, parsed):
         static = []
@@ -199,6 +243,9 @@ class Trainer:
             for i in (5, 9):                                  # host lengths ride along: shapes / maxima are part of the key
                 h = getattr(inputs[i], '_dx_host_lengths', None)
                 si[i]._dx_host_lengths = h if h is not None else inputs[i].tolist()   # (a sync, at capture time only)
+                e = getattr(inputs[i], '_dx_rows_exist', None)
+                if e is not None:                             # bucketed: rewritten before every replay (_copy_static)
+                    si[i]._dx_rows_exist = e.clone()
             st = (si[1], si[3], si[4], si[8], si[9], si[10])  # the targets alias the inputs, as parse_batch builds them
             static.append((si, st))
         return static
@@ -240,10 +287,24 @@ class Trainer:
             self.val_graphs.clear()
             self._conditioner_generation = gen
 
+    @staticmethod
+    def _copy_static(si, inputs):
+        """A micro-batch into the static input buffers of a graph (inputs of the same shapes), with its existence vectors."""
+        for dst, src in zip(si, inputs):
+            if dst.data_ptr() != src.data_ptr():      # a batch built by resident_batch() already lives in the static buffers
+                dst.copy_(src, non_blocking=True)
+        for i in (5, 9):
+            e = getattr(si[i], '_dx_rows_exist', None)
+            if e is not None:
+                e.copy_(inputs[i]._dx_rows_exist, non_blocking=True)
+
     def resident_batch(self, batch):
         """The batch copied into the static input buffers of its shape's graphs (captured now if need be) and handed back as a
         reference 14-tuple of THOSE tensors: ``train_step`` then finds its inputs in place (a data loader writing pinned host batches
-        straight into the static buffers does the same).  One micro-batch per update only."""
+        straight into the static buffers does the same).  One micro-batch per update only.  Not available in bucketed mode (ValueError):
+        there the static buffers have the bucket's shape and the existence vectors, which a reference 14-tuple cannot carry."""
+        if self.bucket is not None:
+            raise ValueError('resident_batch() is not available in bucketed mode (Trainer(bucket=...)): pass the batch to train_step()')
         if self.accumulation_steps != 1 or not self.use_graphs:
             return batch
         self._check_conditioner()
@@ -274,9 +335,7 @@ class Trainer:
                 g = self._capture(parsed, key)
             g.hits += 1
             for (si, _), (inputs, _) in zip(g.inputs, parsed):
-                for dst, src in zip(si, inputs):
-                    if dst.data_ptr() != src.data_ptr():      # a batch built by resident_batch() already lives in the static buffers
-                        dst.copy_(src, non_blocking=True)
+                self._copy_static(si, inputs)
             for gid, graph in enumerate(g.graphs):
                 graph.replay()
                 red.launch_group(gid)                         # exchanged (RCCL, its own stream) while the next phase's graph runs
@@ -315,7 +374,7 @@ class Trainer:
         kept, n = [], 0
         try:
             for batch in batches:
-                (inputs, targets), = [model.parse_batch(self.device, batch)]
+                (inputs, targets), = [self._bucketed(*model.parse_batch(self.device, batch))]
                 if keep_outputs or not self.use_graphs:      # the caller wants the tensors themselves: eager
                     raw = (inputs[6], inputs[7])
                     cin = self.conditioner.process_batch(inputs, self.device) if self.conditioner is not None else inputs
@@ -332,8 +391,7 @@ class Trainer:
                     g = self.val_graphs.get(key)
                     if g is None:
                         g = self._capture_val([(inputs, targets)], key)
-                    for dst, src in zip(g.inputs[0][0], inputs):
-                        dst.copy_(src, non_blocking=True)
+                    self._copy_static(g.inputs[0][0], inputs)
                     g.graphs[0].replay()
                     tot += g.loss
                     terms += g.terms_dev[0]
