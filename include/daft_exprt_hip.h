@@ -75,13 +75,21 @@ int dx_conv_gemm(const void* X, int ldx, const void* Wp, const float* bias, void
                  const int* lens, int mask_rows, float out_scale, int skip_halo,
                  int x_bf16, int y_bf16, int aux_bf16, const int* rows_exist, void* stream);
 /* x_bf16 / y_bf16 / aux_bf16 = 1: that tensor is stored as bf16 (bf16 operand mode only; ld* count elements).  Used for the
- * 1024-wide hidden activations of the conv feed-forward and the prenet, whose HBM traffic otherwise bounds the step. */
+ * 1024-wide hidden activations of the conv feed-forward and the prenet, whose HBM traffic otherwise bounds the step.
+ * bf16 (operand mode): 0 = exact f32 (f32 pack), 1 = bf16 (bf16 pack), 2 = split bf16: fp32 storage and the f32 pack, every operand
+ * split as x = hi + lo (hi = bf16_rne(x), lo = bf16_rne(x - hi), lo = 0 where hi is not finite: an inf / NaN operand makes the same
+ * outputs non-finite as in mode 0, though an inf may come out as NaN; a finite |x| above bf16's largest value, 3.39e38, splits
+ * as hi = inf) and each product formed as
+ * hi*lo + lo*hi + hi*hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (~16 mantissa bits).  Mode 2 needs x_bf16 = y_bf16 =
+ * aux_bf16 = 0; any other value or combination is an error before any launch.  dx_conv_gemm_f16 rejects mode 2. */
 /* G (fp32, caller-initialised, the parameter's OWN checkpoint layout (Cout, Cin, taps)) += dY^T * shifted X   (autograd of the conv
  * w.r.t. its weight, train.py:435 loss.backward()).  G may be a zeroed scratch gradient or a live `.grad` / all-reduce bucket view. */
 int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
                   int B, int N, int Cin, int Cout, int taps, const int* lens, int skip_halo,
                   int bf16, int dy_bf16, int x_bf16, float* dbias, const int* rows_exist, void* stream);
-/* dbias (optional, caller-zeroed [Cout]): the bias gradient sum_rows dY is accumulated by the same launch from the staged dY tiles.
+/* bf16 (operand mode): 0 = exact f32, 1 = bf16, 2 = split bf16 (as in dx_conv_gemm; needs dy_bf16 = x_bf16 = 0; the bias gradient is
+ * summed from the fp32 dY, in the exact-f32 kernel's order).  dx_conv_wgrad_f16 rejects mode 2.
+ * dbias (optional, caller-zeroed [Cout]): the bias gradient sum_rows dY is accumulated by the same launch from the staged dY tiles.
  * rows_exist (optional, device int32 [B], as in dx_conv_gemm): dY and X rows n >= rows_exist[b] read as zero, so nothing stored there
  * reaches G or dbias (NULL: all N rows exist). */
 /* Up to 32 weight gradients of one kind (same taps, same operand storage, bf16 / fp16 operand mode, Cin % 128 == 0) in ONE launch:
@@ -178,7 +186,10 @@ int dx_attention_bwd(const void* qkv, int ld, const void* ctx, const void* dctx,
 /* bf16 = 1: QK^T / PV (and the five backward products) on v_mfma_f32_16x16x32_bf16, softmax and accumulation in fp32;
  * qkv_bf16 / dqkv_bf16 / ctx_bf16 = 1: the in-projection output / its gradient / the attention context are stored as bf16 (ld in
  * elements; ctx and dctx share ldc AND the storage type: ctx_bf16 = 1 means both are 16-bit).  The context is only ever consumed as a 16-bit GEMM operand (out-projection, its weight gradient)
- * and in delta = rowsum(dctx * ctx), so storing it in 16 bits halves four passes over it. */
+ * and in delta = rowsum(dctx * ctx), so storing it in 16 bits halves four passes over it.
+ * bf16 = 2 (split-bf16 operand mode, dx_attention_fwd and dx_attention_bwd): fp32 storage (every *_bf16 flag 0); the seven products run
+ * on split-bf16 operands as in dx_conv_gemm, P and dS split in registers, softmax, dropout and accumulation in fp32.  The _f16 twins
+ * reject 2; any other value is an error. */
 
 /* ---- dropout + residual + LayerNorm + FiLM + mask: model.py:188-191, :225-233, :256-258, :655-669 ------------------- */
 /* z = drop_pre(a) + res is written back over `a`; y = mask(film(drop_post(LN(z)))); C in {128, 1024}.

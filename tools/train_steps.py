@@ -19,7 +19,7 @@ import torch.distributed as dist
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--precision', default='bf16', choices=['f32', 'bf16'])
+    ap.add_argument('--precision', default='bf16', choices=['f32', 'bf16', 'bf16x3'])
     ap.add_argument('--accumulation', type=int, default=1)
     ap.add_argument('--batch-size', type=int, default=16)
     ap.add_argument('--features', default='', help='list file in the reference format (features_dir|feature_file|speaker_id per line)')

@@ -43,7 +43,7 @@ def _timed_step(trainer, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=40)
-    ap.add_argument('--precision', default='bf16', choices=['f32', 'bf16'])
+    ap.add_argument('--precision', default='bf16', choices=['f32', 'bf16', 'bf16x3'])
     ap.add_argument('--modes', default='exact,bucketed,eager')
     ap.add_argument('--overhead-reps', type=int, default=10)
     args = ap.parse_args()

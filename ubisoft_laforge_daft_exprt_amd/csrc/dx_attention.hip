@@ -14,12 +14,14 @@
 // All accumulation is fp32; exp / log are the fp32 libm forms.
 #include "dx_common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
 constexpr int HD = 64;       // head dim
 constexpr int TLD = 68;      // LDS row stride (floats) of a [64][64] tile: 16-B aligned rows, column reads conflict free
 constexpr float QSCALE = 0.125f;  // 1/sqrt(64), exact
+constexpr bool kSplitBuild = std::is_same<dx_h16, __bf16>::value;   // operand mode 2 (split bf16) exists in the bf16 build only
 // bf16 kernels keep scores in log2 units (v_exp_f32 is 2^x): the S operand is scaled by QSCALE * log2(e) once when it is
 // loaded, and the saved log-sum-exp is base 2 (scratch between the bf16 forward and backward, never user-visible)
 constexpr float LOG2E = 1.4426950408889634f;
@@ -391,6 +393,318 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnBwdArgs 
         }
       }
       dv[dt] = accv; dk[dt] = acck;
+    }
+  }
+  if (krow < a.N) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      *reinterpret_cast<float4*>(outk + dt * 16 + g * 4) = make_float4(dk[dt][0], dk[dt][1], dk[dt][2], dk[dt][3]);
+      *reinterpret_cast<float4*>(outv + dt * 16 + g * 4) = make_float4(dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]);
+    }
+  }
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// split-bf16 operand mode (operand mode 2): the geometry, masking, dropout and order of the three f32 kernels above, every product on
+// v_mfma_f32_16x16x32_bf16 as hi*lo + lo*hi + hi*hi (dx_common.h).  K / V (Q / dO) tiles are split while they are staged: hi and lo
+// bf16 images, row-major ([row][col], the A operand of a product over the head dim) and / or transposed ([col][row], the A operand of a
+// product over keys / queries).  Q, dO, K, V of the workgroup's own rows and the probabilities P / dS are split in registers.
+// A 32-k MFMA operand pairs two of the f32 kernels' 16-k groups: lane group g holds k = 32c + 4g + e and 32c + 16 + 4g + e (e < 4), the
+// same k for A and B, so f32 fragments ks = 2c, 2c + 1 (or score tiles kt = 2c, 2c + 1) form operand c.
+// ------------------------------------------------------------------------------------------------
+constexpr int SLD = 68;      // bf16 per row of a split image (136-byte rows: 8-byte aligned fragment halves)
+
+template <bool RM, bool TR>
+__device__ __forceinline__ void stage_split(__bf16* rm_h, __bf16* rm_l, __bf16* tr_h, __bf16* tr_l, const float* base, int ld, int col0,
+                                            int r0, int N, int tid) {
+  for (int u = tid; u < 64 * 16; u += 256) {
+    const int row = u >> 4, q = u & 15;
+    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (r0 + row < N) v = *reinterpret_cast<const f32x4*>(base + (size_t)(r0 + row) * ld + col0 + q * 4);
+    uint2 h, l;
+    split_bf16x4(v, h, l);
+    if constexpr (RM) {
+      *reinterpret_cast<uint2*>(rm_h + row * SLD + q * 4) = h;
+      *reinterpret_cast<uint2*>(rm_l + row * SLD + q * 4) = l;
+    }
+    if constexpr (TR) {
+      typedef __bf16 b4 __attribute__((ext_vector_type(4)));
+      const b4 hv = __builtin_bit_cast(b4, h), lv = __builtin_bit_cast(b4, l);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { tr_h[(q * 4 + e) * SLD + row] = hv[e]; tr_l[(q * 4 + e) * SLD + row] = lv[e]; }
+    }
+  }
+}
+
+// operand c (k = 32c + 4g + e, 32c + 16 + 4g + e) of image row `row`
+__device__ __forceinline__ dx_bf16x8 split_frag(const __bf16* img, int row, int c, int g) {
+  const uint2 x = *reinterpret_cast<const uint2*>(img + row * SLD + 32 * c + 4 * g);
+  const uint2 y = *reinterpret_cast<const uint2*>(img + row * SLD + 32 * c + 16 + 4 * g);
+  return __builtin_bit_cast(dx_bf16x8, make_uint4(x.x, x.y, y.x, y.y));
+}
+__device__ __forceinline__ f32x4 v4(const float4& v) { return f32x4{v.x, v.y, v.z, v.w}; }
+
+__global__ __launch_bounds__(256, 2) void attn_fwd_split_kernel(const AttnArgs a_) {
+  AttnArgs a = a_;
+  if (a.seed_offset) a.seed += *a.seed_offset;
+  __shared__ __attribute__((aligned(16))) __bf16 Kh[64 * SLD], Kl[64 * SLD], Vth[64 * SLD], Vtl[64 * SLD];
+  const AttnBlock blk = attn_block(a.xcd_map);
+  const int b = a.order ? a.order[blk.z] : blk.z, h = blk.h, q0 = blk.tile * 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int len = a.lens[b];
+  const float* base = a.qkv + (size_t)b * a.N * a.ld;
+  const int qrow = q0 + wave * 16 + r;
+  float* out = a.ctx + ((size_t)b * a.N + qrow) * a.ldc + h * HD;
+  if (q0 >= len) {
+    if (qrow < a.N) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<float4*>(out + dt * 16 + g * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (g == 0) a.lse[((size_t)b * a.H + h) * a.N + qrow] = 0.f;
+    }
+    return;
+  }
+  const int qload = min(qrow, a.N - 1);
+  f32x4 qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = v4(*reinterpret_cast<const float4*>(base + (size_t)qload * a.ld + h * HD + ks * 16 + g * 4)) * QSCALE;
+  dx_bf16x8 qh[2], ql[2];
+  split_bf16x8(qf[0], qf[1], qh[0], ql[0]);
+  split_bf16x8(qf[2], qf[3], qh[1], ql[1]);
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;
+  const int bh = b * a.H + h;
+  const int ntiles = (len + 63) / 64;
+  for (int kt0 = 0; kt0 < ntiles; ++kt0) {
+    const int kbase = kt0 * 64;
+    __syncthreads();
+    stage_split<true, false>(Kh, Kl, nullptr, nullptr, base, a.ld, a.D + h * HD, kbase, a.N, tid);
+    stage_split<false, true>(nullptr, nullptr, Vth, Vtl, base, a.ld, 2 * a.D + h * HD, kbase, a.N, tid);
+    __syncthreads();
+    f32x4 st[4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) acc = dx_mma_split3(split_frag(Kh, kt * 16 + r, c, g), split_frag(Kl, kt * 16 + r, c, g), qh[c], ql[c], acc);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (kbase + kt * 16 + g * 4 + e >= len) acc[e] = -INFINITY;
+        mx = fmaxf(mx, acc[e]);
+      }
+      st[kt] = acc;
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const float alpha = expf(m_run - m_new);
+    float ls = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      float keep[4] = {1.f, 1.f, 1.f, 1.f};
+      if (a.thresh) dx_dropout_scale4(a.seed, drop_index(bh, a.N, qrow, kbase + kt * 16 + g * 4), a.thresh, a.inv_keep, keep);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float p = expf(st[kt][e] - m_new);
+        ls += p;
+        st[kt][e] = p * keep[e];
+      }
+    }
+    ls += __shfl_xor(ls, 16, 64);
+    ls += __shfl_xor(ls, 32, 64);
+    l_run = l_run * alpha + ls;
+    m_run = m_new;
+    dx_bf16x8 ph[2], pl[2];
+    split_bf16x8(st[0], st[1], ph[0], pl[0]);
+    split_bf16x8(st[2], st[3], ph[1], pl[1]);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      f32x4 acc = o[dt] * alpha;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) acc = dx_mma_split3(split_frag(Vth, dt * 16 + r, c, g), split_frag(Vtl, dt * 16 + r, c, g), ph[c], pl[c], acc);
+      o[dt] = acc;
+    }
+  }
+  if (qrow < a.N) {
+    const bool valid = qrow < len;
+    const float inv = valid ? 1.f / l_run : 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+      *reinterpret_cast<float4*>(out + dt * 16 + g * 4) = make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
+    if (g == 0) a.lse[((size_t)b * a.H + h) * a.N + qrow] = valid ? m_run + logf(l_run) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_split_kernel(const AttnBwdArgs a_) {
+  AttnBwdArgs a = a_;
+  if (a.seed_offset) a.seed += *a.seed_offset;
+  __shared__ __attribute__((aligned(16))) __bf16 Kh[64 * SLD], Kl[64 * SLD], Kth[64 * SLD], Ktl[64 * SLD], Vh[64 * SLD], Vl[64 * SLD];
+  const AttnBlock blk = attn_block(a.xcd_map);
+  const int b = a.order ? a.order[blk.z] : blk.z, h = blk.h, q0 = blk.tile * 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int len = a.lens[b];
+  const float* base = a.qkv + (size_t)b * a.N * a.ld;
+  const int qrow = q0 + wave * 16 + r;
+  float* out = a.dqkv + ((size_t)b * a.N + qrow) * a.ldg + h * HD;
+  if (q0 >= len) {
+    if (qrow < a.N) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<float4*>(out + dt * 16 + g * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
+  const int qload = min(qrow, a.N - 1);
+  const int bh = b * a.H + h;
+  f32x4 qf[4], gf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    qf[ks] = v4(*reinterpret_cast<const float4*>(base + (size_t)qload * a.ld + h * HD + ks * 16 + g * 4)) * QSCALE;
+    gf[ks] = v4(*reinterpret_cast<const float4*>(a.dctx + ((size_t)b * a.N + qload) * a.ldc + h * HD + ks * 16 + g * 4));
+  }
+  dx_bf16x8 qh[2], ql[2], gh[2], gl[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) { split_bf16x8(qf[2 * c], qf[2 * c + 1], qh[c], ql[c]); split_bf16x8(gf[2 * c], gf[2 * c + 1], gh[c], gl[c]); }
+  const float lse_q = a.lse[(size_t)bh * a.N + qload];
+  const float delta_q = a.delta[(size_t)bh * a.N + qload];
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int ntiles = (len + 63) / 64;
+  for (int kt0 = 0; kt0 < ntiles; ++kt0) {
+    const int kbase = kt0 * 64;
+    __syncthreads();
+    stage_split<true, true>(Kh, Kl, Kth, Ktl, base, a.ld, a.D + h * HD, kbase, a.N, tid);
+    stage_split<true, false>(Vh, Vl, nullptr, nullptr, base, a.ld, 2 * a.D + h * HD, kbase, a.N, tid);
+    __syncthreads();
+    f32x4 ds[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        s = dx_mma_split3(split_frag(Kh, kt * 16 + r, c, g), split_frag(Kl, kt * 16 + r, c, g), qh[c], ql[c], s);
+        dp = dx_mma_split3(split_frag(Vh, kt * 16 + r, c, g), split_frag(Vl, kt * 16 + r, c, g), gh[c], gl[c], dp);
+      }
+      float keep[4] = {1.f, 1.f, 1.f, 1.f};
+      if (a.thresh) dx_dropout_scale4(a.seed, drop_index(bh, a.N, qrow, kbase + kt * 16 + g * 4), a.thresh, a.inv_keep, keep);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool masked = kbase + kt * 16 + g * 4 + e >= len;
+        const float p = masked ? 0.f : expf(s[e] - lse_q);
+        s[e] = p * (dp[e] * keep[e] - delta_q) * QSCALE;
+      }
+      ds[kt] = s;
+    }
+    dx_bf16x8 dh[2], dl[2];
+    split_bf16x8(ds[0], ds[1], dh[0], dl[0]);
+    split_bf16x8(ds[2], ds[3], dh[1], dl[1]);
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        dq[dt] = dx_mma_split3(split_frag(Kth, dt * 16 + r, c, g), split_frag(Ktl, dt * 16 + r, c, g), dh[c], dl[c], dq[dt]);
+    }
+  }
+  if (qrow < a.N) {
+    const float z = qrow < len ? 1.f : 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+      *reinterpret_cast<float4*>(out + dt * 16 + g * 4) = make_float4(dq[dt][0] * z, dq[dt][1] * z, dq[dt][2] * z, dq[dt][3] * z);
+  }
+}
+
+constexpr size_t DKV_SPLIT_SMEM = (size_t)8 * 64 * SLD * sizeof(__bf16);   // Q and dO, hi / lo, row-major and transposed: 68 KB (dynamic)
+
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_split_kernel(const AttnBwdArgs a_) {
+  AttnBwdArgs a = a_;
+  if (a.seed_offset) a.seed += *a.seed_offset;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __bf16* Qh = reinterpret_cast<__bf16*>(smem);
+  __bf16 *Ql = Qh + 64 * SLD, *Qth = Ql + 64 * SLD, *Qtl = Qth + 64 * SLD, *Gh = Qtl + 64 * SLD, *Gl = Gh + 64 * SLD, *Gth = Gl + 64 * SLD,
+         *Gtl = Gth + 64 * SLD;
+  __shared__ float lse_s[64], delta_s[64];
+  const AttnBlock blk = attn_block(a.xcd_map);
+  const int b = a.order ? a.order[blk.z] : blk.z, h = blk.h, k0 = blk.tile * 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int len = a.lens[b];
+  const float* base = a.qkv + (size_t)b * a.N * a.ld;
+  const float* gbase = a.dctx + (size_t)b * a.N * a.ldc;
+  const int krow = k0 + wave * 16 + r;
+  float* outk = a.dqkv + ((size_t)b * a.N + krow) * a.ldg + a.D + h * HD;
+  float* outv = a.dqkv + ((size_t)b * a.N + krow) * a.ldg + 2 * a.D + h * HD;
+  if (k0 >= len) {
+    if (krow < a.N) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        *reinterpret_cast<float4*>(outk + dt * 16 + g * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(outv + dt * 16 + g * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    return;
+  }
+  const int kload = min(krow, a.N - 1);
+  const bool key_valid = krow < len;
+  const int bh = b * a.H + h;
+  f32x4 kf[4], vf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    kf[ks] = v4(*reinterpret_cast<const float4*>(base + (size_t)kload * a.ld + a.D + h * HD + ks * 16 + g * 4)) * QSCALE;
+    vf[ks] = v4(*reinterpret_cast<const float4*>(base + (size_t)kload * a.ld + 2 * a.D + h * HD + ks * 16 + g * 4));
+  }
+  dx_bf16x8 kh[2], kl[2], vh[2], vl[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) { split_bf16x8(kf[2 * c], kf[2 * c + 1], kh[c], kl[c]); split_bf16x8(vf[2 * c], vf[2 * c + 1], vh[c], vl[c]); }
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  const int ntiles = (len + 63) / 64;
+  for (int qt0 = 0; qt0 < ntiles; ++qt0) {
+    const int qbase = qt0 * 64;
+    __syncthreads();
+    stage_split<true, true>(Qh, Ql, Qth, Qtl, base, a.ld, h * HD, qbase, a.N, tid);
+    stage_split<true, true>(Gh, Gl, Gth, Gtl, gbase, a.ldc, h * HD, qbase, a.N, tid);
+    if (tid < 64) {
+      const int q = qbase + tid;
+      lse_s[tid] = q < a.N ? a.lse[(size_t)bh * a.N + q] : 0.f;
+      delta_s[tid] = q < a.N ? a.delta[(size_t)bh * a.N + q] : 0.f;
+    }
+    __syncthreads();
+    f32x4 pd[4], ds[4];
+#pragma unroll
+    for (int qt = 0; qt < 4; ++qt) {
+      f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        s = dx_mma_split3(split_frag(Qh, qt * 16 + r, c, g), split_frag(Ql, qt * 16 + r, c, g), kh[c], kl[c], s);
+        dp = dx_mma_split3(split_frag(Gh, qt * 16 + r, c, g), split_frag(Gl, qt * 16 + r, c, g), vh[c], vl[c], dp);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ql_ = qt * 16 + g * 4 + e, q = qbase + ql_;
+        const bool live = key_valid && q < len;
+        const float p = live ? expf(s[e] - lse_s[ql_]) : 0.f;
+        float keep = 1.f;
+        if (a.thresh) keep = dx_dropout_scale(a.seed, drop_index(bh, a.N, q, krow), a.thresh, a.inv_keep);
+        pd[qt][e] = p * keep;
+        ds[qt][e] = p * (dp[e] * keep - delta_s[ql_]) * QSCALE;
+      }
+    }
+    dx_bf16x8 ph[2], pl[2], dh[2], dl[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) { split_bf16x8(pd[2 * c], pd[2 * c + 1], ph[c], pl[c]); split_bf16x8(ds[2 * c], ds[2 * c + 1], dh[c], dl[c]); }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        dv[dt] = dx_mma_split3(split_frag(Gth, dt * 16 + r, c, g), split_frag(Gtl, dt * 16 + r, c, g), ph[c], pl[c], dv[dt]);
+        dk[dt] = dx_mma_split3(split_frag(Qth, dt * 16 + r, c, g), split_frag(Qtl, dt * 16 + r, c, g), dh[c], dl[c], dk[dt]);
+      }
     }
   }
   if (krow < a.N) {
@@ -1195,6 +1509,9 @@ int dx_attention_fwd(const void* qkvv, int ld, const int* lens, void* ctxv, int 
   float* ctx = (float*)ctxv;
   const float* qkv = (const float*)qkvv;
   if (int rc = check_common("dx_attention_fwd", qkv, ld, B, N, H, D)) return rc;
+  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_attention_fwd: bad operand mode %d", bf16);
+  const bool split = bf16 == 2;     // split-bf16 operands on fp32 storage: the storage rules of mode 0
+  if (split) bf16 = 0;
   DX_REQUIRE(!qkv_bf16 || (bf16 && (ld % 8) == 0), "dx_attention_fwd: bf16-stored qkv needs bf16 mode and ld %% 8 == 0");
   DX_REQUIRE(lens && ctx && lse && ldc >= D && (ldc % 4) == 0 && ((uintptr_t)ctx % 16) == 0, "dx_attention_fwd: bad output arguments");
   DX_REQUIRE(!ctx_bf16 || (bf16 && (ldc % 8) == 0), "dx_attention_fwd: a 16-bit context needs the 16-bit operand mode and ldc %% 8 == 0");
@@ -1208,6 +1525,7 @@ int dx_attention_fwd(const void* qkvv, int ld, const int* lens, void* ctxv, int 
   else if (bf16 && qkv_bf16) hipLaunchKernelGGL((attn_fwd_bf16_kernel<dx_h16, float>), grid, dim3(256), 0, s, a);
   else if (bf16 && ctx_bf16) hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, dx_h16>), grid, dim3(256), 0, s, a);
   else if (bf16) hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, float>), grid, dim3(256), 0, s, a);
+  else if (split) { if constexpr (kSplitBuild) hipLaunchKernelGGL(attn_fwd_split_kernel, grid, dim3(256), 0, s, a); }
   else hipLaunchKernelGGL(attn_fwd_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), 0, s, a);
   dx_prof_end(DX_PROF_ATTN_FWD, s);
   DX_LAUNCH_CHECK("dx_attention_fwd");
@@ -1247,6 +1565,9 @@ int dx_attention_bwd(const void* qkvv, int ld, const void* ctxv, const void* dct
                      const int* lens, void* dqkvv, int ldg, int B, int N, int H, int D, uint64_t seed, const uint64_t* seed_offset, float p_drop, int bf16,
                      int qkv_bf16, int dqkv_bf16, int ctx_bf16, const int* order, void* stream) {
   const float* qkv = (const float*)qkvv; float* dqkv = (float*)dqkvv; const float* ctx = (const float*)ctxv; const float* dctx = (const float*)dctxv;
+  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_attention_bwd: bad operand mode %d", bf16);
+  const bool split = bf16 == 2;     // split-bf16 operands on fp32 storage: the storage rules (and the delta pass) of mode 0
+  if (split) bf16 = 0;
   DX_REQUIRE(!ctx_bf16 || (bf16 && (ldc % 8) == 0), "dx_attention_bwd: a 16-bit context needs the 16-bit operand mode and ldc %% 8 == 0");
   if (int rc = check_common("dx_attention_bwd", qkv, ld, B, N, H, D)) return rc;
   DX_REQUIRE(!(qkv_bf16 || dqkv_bf16) || (bf16 && (ld % 8) == 0 && (ldg % 8) == 0), "dx_attention_bwd: bf16-stored qkv/dqkv need bf16 mode and ld %% 8 == 0");
@@ -1276,6 +1597,16 @@ int dx_attention_bwd(const void* qkvv, int ld, const void* ctxv, const void* dct
     else if (dqkv_bf16) { DX_ATTN_BWD(float, dx_h16) }
     else { DX_ATTN_BWD(float, float) }
 #undef DX_ATTN_BWD
+  } else if (split) {
+    if constexpr (kSplitBuild) {
+      static bool configured = false;
+      if (!configured) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DKV_SPLIT_SMEM);
+        configured = true;
+      }
+      hipLaunchKernelGGL(attn_bwd_dq_split_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), 0, s, a);
+      hipLaunchKernelGGL(attn_bwd_dkv_split_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), DKV_SPLIT_SMEM, s, a);
+    }
   } else {
     hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), 0, s, a);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), 0, s, a);

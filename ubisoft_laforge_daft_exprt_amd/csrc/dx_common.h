@@ -59,6 +59,40 @@ static inline int dx_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int dx_roundup(int a, int b) { return dx_cdiv(a, b) * b; }
 
 #ifdef __HIPCC__
+// ---- split-bf16 operands (C ABI operand mode 2, bf16 build) ---------------------------------------------------------------------
+// x = hi + lo with hi = bf16_rne(x), lo = bf16_rne(x - hi) (v_cvt_pk_bf16_f32); lo = 0 where hi is not finite, so an inf / NaN operand
+// makes exactly the sums non-finite that it makes non-finite in exact f32 (an inf may become NaN: inf * lo, lo = 0 where the other
+// operand is exact in bf16).  A product is hi_a*lo_b + lo_a*hi_b + hi_a*hi_b, the two small cross terms
+// first, fp32 accumulate: ~16 mantissa bits for 3 bf16 MFMAs where the exact-f32 form needs 8 K=4 ones.
+typedef __bf16 dx_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 dx_bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split_bf16x2(float x0, float x1, unsigned& hi, unsigned& lo) {
+  dx_bf16x2 h, l;
+  h[0] = (__bf16)x0; h[1] = (__bf16)x1;
+  const float h0 = (float)h[0], h1 = (float)h[1];
+  l[0] = (__bf16)(__builtin_isfinite(h0) ? x0 - h0 : 0.f);
+  l[1] = (__bf16)(__builtin_isfinite(h1) ? x1 - h1 : 0.f);
+  hi = __builtin_bit_cast(unsigned, h); lo = __builtin_bit_cast(unsigned, l);
+}
+__device__ __forceinline__ void split_bf16x4(const f32x4& v, uint2& hi, uint2& lo) {
+  split_bf16x2(v[0], v[1], hi.x, lo.x);
+  split_bf16x2(v[2], v[3], hi.y, lo.y);
+}
+// two 4-element groups -> one 8-element hi / lo MFMA operand (a first, then b)
+__device__ __forceinline__ void split_bf16x8(const f32x4& a, const f32x4& b, dx_bf16x8& hi, dx_bf16x8& lo) {
+  uint2 ha, la, hb, lb;
+  split_bf16x4(a, ha, la);
+  split_bf16x4(b, hb, lb);
+  hi = __builtin_bit_cast(dx_bf16x8, make_uint4(ha.x, ha.y, hb.x, hb.y));
+  lo = __builtin_bit_cast(dx_bf16x8, make_uint4(la.x, la.y, lb.x, lb.y));
+}
+__device__ __forceinline__ f32x4 dx_mma_split3(const dx_bf16x8& ah, const dx_bf16x8& al, const dx_bf16x8& bh, const dx_bf16x8& bl, f32x4 c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+  return c;
+}
+
 // ---- wave64 reductions -------------------------------------------------------------------------
 __device__ __forceinline__ float dx_wave_sum(float v) {
 #pragma unroll

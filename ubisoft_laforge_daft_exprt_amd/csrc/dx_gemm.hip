@@ -25,6 +25,7 @@
 #include "dx_common.h"
 #include <algorithm>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -67,6 +68,19 @@ template <> struct Mma<dx_h16> {
   }
 };
 
+// Split-bf16 operand mode (C ABI operand mode 2, bf16 build only): fp32 storage and the f32 weight pack; every operand is split while it is
+// staged into LDS as x = hi + lo, hi = bf16_rne(x), lo = bf16_rne(x - hi), and a product is hi_a*lo_b + lo_a*hi_b + hi_a*hi_b (fp32
+// accumulate): ~16 mantissa bits per product for 3 bf16 MFMAs where the exact-f32 form needs 8 K=4 ones.  sizeof == 4: the kernels keep
+// the f32 pack geometry and staging loads; the tag only selects the split staging and the bf16 MFMAs.
+struct dx_split3 { float v; };
+constexpr bool kSplitBuild = std::is_same<dx_h16, __bf16>::value;   // the fp16 twins have no split mode
+
+template <> struct Mma<dx_split3> {
+  static __device__ __forceinline__ void run(const dx_bf16x8& ah, const dx_bf16x8& al, const dx_bf16x8& bh, const dx_bf16x8& bl, f32x4& c) {
+    c = dx_mma_split3(ah, al, bh, bl, c);
+  }
+};
+
 __device__ __forceinline__ uint2 pack_bf16x4v(const f32x4& v) {
   bf16x4 h;
   h[0] = (dx_h16)v[0]; h[1] = (dx_h16)v[1]; h[2] = (dx_h16)v[2]; h[3] = (dx_h16)v[3];
@@ -105,6 +119,8 @@ template <typename T> __device__ __forceinline__ void w_unit(int u, int& row, in
 
 // TOK = tokens per workgroup (128, or 64 for narrow outputs that would otherwise launch fewer workgroups than CUs).
 // XH  = the activation tensor is stored as bf16 (bf16 operand mode only).
+// T = dx_split3: 32-k chunks of the fp32 operands are staged as a hi image (16-byte slots 0-3 of a row) and a lo image (slots 4-7); lane group
+// g's fragment is the 8 k of slot g (hi) and slot 4 + g (lo), one v_mfma_f32_16x16x32_bf16 per term and 16x16 tile.
 // Software pipeline: the global loads of K-chunk c+1 are issued into registers before the MFMAs of chunk c and written
 // to LDS after them, so HBM/L2 latency hides under the matrix work of the same wave.
 template <typename T, int TAPS, int TOK, bool XH>
@@ -115,6 +131,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmArgs a)
   constexpr int NJ = TOK / 32;                      // 16-token sub-tiles per wave
   constexpr int W_IT = TAPS * TILE * 8 / 256;       // 16-byte weight units per thread per chunk
   constexpr bool CVT = (sizeof(T) == 2) && !XH;     // fp32 activations converted to bf16 while staging
+  constexpr bool SPLIT = std::is_same<T, dx_split3>::value;
   constexpr int XU = CVT ? 16 : 8;                  // 16-byte global units per activation row per chunk
   constexpr int XE = XH ? 8 : 4;                    // elements per unit
   constexpr int X_IT = (XROWS * XU + 255) / 256;
@@ -182,13 +199,24 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmArgs a)
     _Pragma("unroll") for (int it = 0; it < W_IT; ++it) {                                                                        \
       int row, q;                                                                                                                \
       w_unit<T>(tid + it * 256, row, q);                                                                                         \
-      *reinterpret_cast<f32x4*>(Ws + lds_off(row, q)) = wreg[it];                                                               \
+      if constexpr (SPLIT) {                                                                                                     \
+        uint2 hi_, lo_;                                                                                                          \
+        split_bf16x4(wreg[it], hi_, lo_);                                                                                        \
+        *reinterpret_cast<uint2*>(Ws + lds_off(row, q >> 1) + ((q & 1) << 3)) = hi_;                                             \
+        *reinterpret_cast<uint2*>(Ws + lds_off(row, 4 + (q >> 1)) + ((q & 1) << 3)) = lo_;                                       \
+      } else *reinterpret_cast<f32x4*>(Ws + lds_off(row, q)) = wreg[it];                                                        \
     }                                                                                                                            \
     _Pragma("unroll") for (int it = 0; it < X_IT; ++it) {                                                                        \
       const int u = tid + it * 256;                                                                                              \
       const int row = u / XU, q = u % XU;                                                                                        \
       if (u < XROWS * XU) {                                                                                                      \
         if constexpr (CVT) *reinterpret_cast<uint2*>(Xs + lds_off(row, q >> 1) + ((q & 1) << 3)) = pack_bf16x4v(xreg[it]);       \
+        else if constexpr (SPLIT) {                                                                                              \
+          uint2 hi_, lo_;                                                                                                        \
+          split_bf16x4(xreg[it], hi_, lo_);                                                                                      \
+          *reinterpret_cast<uint2*>(Xs + lds_off(row, q >> 1) + ((q & 1) << 3)) = hi_;                                           \
+          *reinterpret_cast<uint2*>(Xs + lds_off(row, 4 + (q >> 1)) + ((q & 1) << 3)) = lo_;                                     \
+        }                                                                                                                        \
         else *reinterpret_cast<f32x4*>(Xs + lds_off(row, q)) = xreg[it];                                                         \
       }                                                                                                                          \
     }                                                                                                                            \
@@ -207,21 +235,44 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvGemmArgs a)
     DX_STORE_CHUNK();
     __syncthreads();
     if (ch + 1 < nchunks) DX_LOAD_CHUNK(ch + 1);
+    if constexpr (SPLIT) {
 #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
+      for (int tap = 0; tap < TAPS; ++tap) {
+        dx_bf16x8 wh[4], wl[4], xh[NJ], xl[NJ];
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        float4 wf[4], xf[NJ];
+        for (int i = 0; i < 4; ++i) {
+          const int row = tap * TILE + wc * 64 + i * 16 + r;
+          wh[i] = *reinterpret_cast<const dx_bf16x8*>(Ws + lds_off(row, g));
+          wl[i] = *reinterpret_cast<const dx_bf16x8*>(Ws + lds_off(row, 4 + g));
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int row = wt * (TOK / 2) + j * 16 + r + tap;
+          xh[j] = *reinterpret_cast<const dx_bf16x8*>(Xs + lds_off(row, g));
+          xl[j] = *reinterpret_cast<const dx_bf16x8*>(Xs + lds_off(row, 4 + g));
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          wf[i] = *reinterpret_cast<const float4*>(Ws + lds_off(tap * TILE + wc * 64 + i * 16 + r, ks * 4 + g));
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          xf[j] = *reinterpret_cast<const float4*>(Xs + lds_off(wt * (TOK / 2) + j * 16 + r + tap, ks * 4 + g));
+          for (int j = 0; j < NJ; ++j) Mma<dx_split3>::run(wh[i], wl[i], xh[j], xl[j], acc[i][j]);
+      }
+    } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+      for (int tap = 0; tap < TAPS; ++tap) {
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) Mma<T>::run(wf[i], xf[j], acc[i][j]);
+        for (int ks = 0; ks < 2; ++ks) {
+          float4 wf[4], xf[NJ];
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            wf[i] = *reinterpret_cast<const float4*>(Ws + lds_off(tap * TILE + wc * 64 + i * 16 + r, ks * 4 + g));
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            xf[j] = *reinterpret_cast<const float4*>(Xs + lds_off(wt * (TOK / 2) + j * 16 + r + tap, ks * 4 + g));
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) Mma<T>::run(wf[i], xf[j], acc[i][j]);
+        }
       }
     }
   }
@@ -1117,6 +1168,120 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
       for (int e = 0; e < 4; ++e) {
         const int co = co0 + wc * 64 + i * 16 + g * 4 + e;
         if (co < a.Cout) atomicAdd(&a.G[((size_t)co * a.Cin + ci) * TAPS + tap], acc[i][j][e]);   // the parameter's own (Cout, Cin, taps) layout
+      }
+    }
+  if (do_bias && co0 + tid < a.Cout && bsum != 0.f) atomicAdd(&a.dbias[co0 + tid], bsum);
+}
+
+// ------------------------------------------------------------------------------------------------
+// weight gradient, split-bf16 operands (operand mode 2): the tiling, token split and atomics of wgrad_kernel, one 32-token
+// v_mfma_f32_16x16x32_bf16 step per chunk and term.  The fp32 tiles are split while they are staged and stored channel-major
+// (K = token contiguous, 80-byte rows) as hi and lo images, so a lane's 8-token fragment is one ds_read_b128 (16 rows x 20 dwords:
+// conflict free).  A staging unit is 2 tokens x 4 channels (one packed bf16 pair per channel and image); 16 lanes walk the 32 tokens
+// and 4 channel quads per wave land on distinct banks.  A workgroup serves one tap, so X is staged already shifted by it (no halo).
+// ------------------------------------------------------------------------------------------------
+constexpr int WS_LD = 40;     // bf16 per channel row of a split image: 32 tokens + 8 pad
+
+__device__ __forceinline__ void store_split_pairs(__bf16* hi_img, __bf16* lo_img, int c0, int p, const float4& v0, const float4& v1) {
+  unsigned h, l;
+  split_bf16x2(v0.x, v1.x, h, l);
+  *reinterpret_cast<unsigned*>(hi_img + (c0 + 0) * WS_LD + 2 * p) = h; *reinterpret_cast<unsigned*>(lo_img + (c0 + 0) * WS_LD + 2 * p) = l;
+  split_bf16x2(v0.y, v1.y, h, l);
+  *reinterpret_cast<unsigned*>(hi_img + (c0 + 1) * WS_LD + 2 * p) = h; *reinterpret_cast<unsigned*>(lo_img + (c0 + 1) * WS_LD + 2 * p) = l;
+  split_bf16x2(v0.z, v1.z, h, l);
+  *reinterpret_cast<unsigned*>(hi_img + (c0 + 2) * WS_LD + 2 * p) = h; *reinterpret_cast<unsigned*>(lo_img + (c0 + 2) * WS_LD + 2 * p) = l;
+  split_bf16x2(v0.w, v1.w, h, l);
+  *reinterpret_cast<unsigned*>(hi_img + (c0 + 3) * WS_LD + 2 * p) = h; *reinterpret_cast<unsigned*>(lo_img + (c0 + 3) * WS_LD + 2 * p) = l;
+}
+
+template <int TAPS>
+__global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a) {
+  constexpr int PAD = (TAPS - 1) / 2;
+  static_assert(WG_BK == 32, "one 32-k MFMA step per chunk");
+  __shared__ __attribute__((aligned(16))) __bf16 Dh[TILE * WS_LD];
+  __shared__ __attribute__((aligned(16))) __bf16 Dl[TILE * WS_LD];
+  __shared__ __attribute__((aligned(16))) __bf16 Xh[TILE * WS_LD];
+  __shared__ __attribute__((aligned(16))) __bf16 Xl[TILE * WS_LD];
+  const int ci_tiles = (a.Cin + TILE - 1) / TILE;
+  const int co0 = (blockIdx.x / ci_tiles) * TILE;
+  const int ci0 = (blockIdx.x % ci_tiles) * TILE;
+  const int tap = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wc = wave >> 1, wt = wave & 1;
+  const int r = lane & 15, g = lane >> 4;
+
+  const int chunks_per_row = (a.N + WG_BK - 1) / WG_BK;
+  const int total = a.B * chunks_per_row;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool do_bias = a.dbias != nullptr && tap == 0 && ci0 == 0 && tid < TILE;
+  float bsum = 0.f;
+
+  for (int c = blockIdx.z; c < total; c += a.ksplit) {
+    const int b = c / chunks_per_row;
+    const int nc = (c - b * chunks_per_row) * WG_BK;
+    if (a.skip_halo >= 0 && nc >= a.lens[b] + a.skip_halo) continue;
+    const float* dYb = a.dY + (size_t)b * a.N * a.ldy;
+    const float* Xb = a.X + (size_t)b * a.N * a.ldx;
+    const int nl = a.rows_exist ? a.rows_exist[b] : a.N;
+    __syncthreads();
+    for (int u = tid; u < (WG_BK / 2) * 32; u += 256) {
+      const int p = u & 15, q = u >> 4;
+      const int n = nc + 2 * p, co = co0 + q * 4;
+      float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+      if (co < a.Cout) {
+        if (n < nl) v0 = *reinterpret_cast<const float4*>(dYb + (size_t)n * a.ldy + co);
+        if (n + 1 < nl) v1 = *reinterpret_cast<const float4*>(dYb + (size_t)(n + 1) * a.ldy + co);
+      }
+      store_split_pairs(Dh, Dl, q * 4, p, v0, v1);
+    }
+    for (int u = tid; u < (WG_BK / 2) * 32; u += 256) {
+      const int p = u & 15, q = u >> 4;
+      const int n = nc + 2 * p + tap - PAD, ci = ci0 + q * 4;
+      float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+      if (ci < a.Cin) {
+        if (n >= 0 && n < nl) v0 = *reinterpret_cast<const float4*>(Xb + (size_t)n * a.ldx + ci);
+        if (n + 1 >= 0 && n + 1 < nl) v1 = *reinterpret_cast<const float4*>(Xb + (size_t)(n + 1) * a.ldx + ci);
+      }
+      store_split_pairs(Xh, Xl, q * 4, p, v0, v1);
+    }
+    __syncthreads();
+    if (do_bias && co0 + tid < a.Cout) {        // the fp32 dY (an L2 hit), summed in wgrad_kernel's order
+#pragma unroll 8
+      for (int k = 0; k < WG_BK; ++k) bsum += nc + k < nl ? dYb[(size_t)(nc + k) * a.ldy + co0 + tid] : 0.f;
+    }
+    dx_bf16x8 dh[4], dl[4], xh[4], xl[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = wc * 64 + i * 16 + r;
+      dh[i] = *reinterpret_cast<const dx_bf16x8*>(Dh + row * WS_LD + g * 8);
+      dl[i] = *reinterpret_cast<const dx_bf16x8*>(Dl + row * WS_LD + g * 8);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = wt * 64 + j * 16 + r;
+      xh[j] = *reinterpret_cast<const dx_bf16x8*>(Xh + row * WS_LD + g * 8);
+      xl[j] = *reinterpret_cast<const dx_bf16x8*>(Xl + row * WS_LD + g * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Mma<dx_split3>::run(dh[i], dl[i], xh[j], xl[j], acc[i][j]);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ci = ci0 + wt * 64 + j * 16 + r;
+      if (ci >= a.Cin) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int co = co0 + wc * 64 + i * 16 + g * 4 + e;
+        if (co < a.Cout) atomicAdd(&a.G[((size_t)co * a.Cin + ci) * TAPS + tap], acc[i][j][e]);
       }
     }
   if (do_bias && co0 + tid < a.Cout && bsum != 0.f) atomicAdd(&a.dbias[co0 + tid], bsum);
@@ -2078,7 +2243,8 @@ int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, voi
                  int x_bf16, int y_bf16, int aux_bf16, const int* rows_exist, void* stream) {
   const float* X = (const float*)Xv; float* Y = (float*)Yv; const float* relu_aux = (const float*)relu_auxv;
   DX_REQUIRE(X && Wp && Y, "dx_conv_gemm: null pointer");
-  DX_REQUIRE(bf16 || !(x_bf16 || y_bf16 || aux_bf16), "dx_conv_gemm: bf16 storage needs bf16 operand mode");
+  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_conv_gemm: bad operand mode %d", bf16);
+  DX_REQUIRE(bf16 == 1 || !(x_bf16 || y_bf16 || aux_bf16), "dx_conv_gemm: bf16 storage needs bf16 operand mode");
   DX_REQUIRE(!x_bf16 || ((Cin % 8) == 0 && (ldx % 8) == 0), "dx_conv_gemm: bf16 input needs Cin, ldx multiples of 8");
   DX_REQUIRE(!y_bf16 || ((Cout % 4) == 0 && (ldy % 4) == 0 && !accumulate), "dx_conv_gemm: bf16 output needs Cout, ldy multiples of 4 and no accumulate");
   DX_REQUIRE(!aux_bf16 || ((Cout % 4) == 0 && (ld_aux % 4) == 0), "dx_conv_gemm: bf16 relu_aux needs Cout, ld_aux multiples of 4");
@@ -2092,7 +2258,7 @@ int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, voi
   DX_REQUIRE((post_scale == nullptr) == (post_shift == nullptr), "dx_conv_gemm: post_scale/post_shift must come together");
   DX_REQUIRE(!mask_rows || lens, "dx_conv_gemm: mask_rows needs lens");
   int d[4];
-  dx_pack_dims(Cout, Cin, bf16, d);
+  dx_pack_dims(Cout, Cin, bf16 == 1, d);     // the split mode reads the f32 pack
   ConvGemmArgs a{X, ldx, Wp, bias, Y, ldy, B, N, Cin, Cout, d[1], d[0], relu, post_scale, post_shift,
                  relu_aux, ld_aux, accumulate, lens, mask_rows, out_scale, skip_halo, x_bf16, y_bf16, aux_bf16, rows_exist};
   hipStream_t s = (hipStream_t)stream;
@@ -2100,7 +2266,9 @@ int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, voi
   constexpr int ws_min_tiles = 64;
   // deep-K layers: weights straight from the fragment-major pack into registers, live tiles numbered first
   constexpr int dk_min_cin = 256;
-  if (bf16 && d[1] >= dk_min_cin && (Cin % 64) == 0 && (long)B * N * ldx < (1L << 31)) {
+  if (bf16 == 2) {
+    if constexpr (kSplitBuild) { if (taps == 3) launch_conv<dx_split3, 3>(a, s); else launch_conv<dx_split3, 1>(a, s); }
+  } else if (bf16 && d[1] >= dk_min_cin && (Cin % 64) == 0 && (long)B * N * ldx < (1L << 31)) {
     if (x_bf16) { if (taps == 3) launch_conv_dk<3, true>(a, s); else launch_conv_dk<1, true>(a, s); }
     else { if (taps == 3) launch_conv_dk<3, false>(a, s); else launch_conv_dk<1, false>(a, s); }
   } else if (bf16 && d[1] == 128 && (long)B * dx_cdiv(N, 128) >= ws_min_tiles) {      // short-K layers: weight-stationary persistent kernel
@@ -2119,10 +2287,11 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
                   int B, int N, int Cin, int Cout, int taps, const int* lens, int skip_halo,
                   int bf16, int dy_bf16, int x_bf16, float* dbias, const int* rows_exist, void* stream) {
   DX_REQUIRE(dY && X && G, "dx_conv_wgrad: null pointer");
-  DX_REQUIRE(bf16 || !(dy_bf16 || x_bf16), "dx_conv_wgrad: bf16 storage needs bf16 operand mode");
+  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_conv_wgrad: bad operand mode %d", bf16);
+  DX_REQUIRE(bf16 == 1 || !(dy_bf16 || x_bf16), "dx_conv_wgrad: bf16 storage needs bf16 operand mode");
   const bool bf16_ok = (Cin % 8) == 0 && (ldx % 8) == 0 && (Cout % 8) == 0 && (ldy % 8) == 0;
   DX_REQUIRE(bf16_ok || !(dy_bf16 || x_bf16), "dx_conv_wgrad: bf16-stored operands need Cin/Cout/ld multiples of 8 (Cin=%d Cout=%d)", Cin, Cout);
-  if (bf16 && bf16_ok) {   // odd tiny shapes (speaker logits) take the exact f32 kernel below
+  if (bf16 == 1 && bf16_ok) {   // odd tiny shapes (speaker logits) take the exact f32 kernel below
     DX_REQUIRE(B > 0 && N > 0 && Cin > 0 && Cout > 0 && (taps == 1 || taps == 3), "dx_conv_wgrad: bad dims");
     DX_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0, "dx_conv_wgrad: pointers must be 16-byte aligned");
     DX_REQUIRE(skip_halo < 0 || lens, "dx_conv_wgrad: skip_halo needs lens");
@@ -2166,7 +2335,12 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
   WgradArgs a{(const float*)dY, ldy, (const float*)X, ldx, G, B, N, Cin, Cout, ksplit, lens, skip_halo, dbias, rows_exist};
   hipStream_t s = (hipStream_t)stream;
   dx_prof_begin(DX_PROF_WGRAD_GEMM, s);
-  if (taps == 3) hipLaunchKernelGGL(wgrad_kernel<3>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
+  if (bf16 == 2) {
+    if constexpr (kSplitBuild) {
+      if (taps == 3) hipLaunchKernelGGL(wgrad_split_kernel<3>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
+      else           hipLaunchKernelGGL(wgrad_split_kernel<1>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
+    }
+  } else if (taps == 3) hipLaunchKernelGGL(wgrad_kernel<3>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
   else           hipLaunchKernelGGL(wgrad_kernel<1>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
   dx_prof_end(DX_PROF_WGRAD_GEMM, s);
   DX_LAUNCH_CHECK("dx_conv_wgrad");

@@ -362,7 +362,8 @@ class DaftExprt(nn.Module):
             m._dx_rt = self.runtime
 
     def set_precision(self, name: str):
-        """'f32' (exact-f32 MFMA operands, parity mode) or 'bf16' (bf16 MFMA operands, fp32 accumulate; throughput mode)."""
+        """'f32' (exact-f32 MFMA operands, parity mode), 'bf16' / 'fp16' (16-bit MFMA operands, fp32 accumulate; throughput modes) or
+        'bf16x3' (f32 storage and launches, conv GEMMs and weight gradients on split-bf16 operands; parity-grade, see ops.set_precision)."""
         self.runtime.set_precision(name)
         return self
 

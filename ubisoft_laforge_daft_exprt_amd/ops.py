@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from ._lib import lib
 
-PRECISIONS = ('f32', 'bf16', 'fp16')
+PRECISIONS = ('f32', 'bf16', 'fp16', 'bf16x3')
 
 
 class Runtime:
@@ -68,6 +68,8 @@ DEFAULT = Runtime('f32')
 
 def set_precision(name: str) -> None:
     """'f32': exact-f32 MFMA operands (parity mode).  'bf16' / 'fp16': 16-bit MFMA operands, fp32 accumulate (throughput modes).
+    'bf16x3': the f32 mode's storage and launches, with the conv GEMMs and weight gradients on split-bf16 operands (x = hi + lo,
+    three bf16 MFMAs per product, fp32 accumulate): parity-grade results at a fraction of the exact-f32 MFMA time.
     Sets the default for models / losses constructed afterwards (and for kernel-level calls without a model); a live model is
     switched with ``model.set_precision(name)``."""
     DEFAULT.set_precision(name)
@@ -86,8 +88,19 @@ def record_launches(enable: bool, rt=None):
 
 
 def _half(prec) -> int:
-    """operand-mode flag of the C ABI: 0 = exact f32, 1 = 16-bit operands (bf16 build, or fp16 in the ``_f16`` twins)"""
+    """16-bit STORAGE: 1 when the mode keeps activations / packs in a 16-bit type (bf16, fp16), else 0 (f32, bf16x3)"""
     return 1 if prec in ('bf16', 'fp16') else 0
+
+
+def _mode(prec) -> int:
+    """operand-mode flag of the C ABI (the ``bf16`` argument): 0 = exact f32, 1 = 16-bit operands (bf16 build, or fp16 in the ``_f16``
+    twins), 2 = split-bf16 operands on fp32 storage (bf16x3)"""
+    return 2 if prec == 'bf16x3' else _half(prec)
+
+
+def _pack_prec(prec):
+    """The weight-pack image a precision reads: bf16x3 reads the f32 pack"""
+    return 'f32' if prec == 'bf16x3' else prec
 
 
 _H16 = {'bf16': torch.bfloat16, 'fp16': torch.float16}
@@ -207,6 +220,7 @@ class PackedWeight:
         return (w._version, w.data_ptr(), self.rt.pack_epoch if w.requires_grad else 0)
 
     def _image(self, prec) -> _PackImage:
+        prec = _pack_prec(prec)
         img = self._images.get(prec)
         w = self.weight
         if img is None or img.fwd.device != w.device:
@@ -223,7 +237,7 @@ class PackedWeight:
 
     def image(self, prec=None) -> _PackImage:
         """The up-to-date image at ``prec`` (default: the runtime's precision)."""
-        prec = prec or self.rt.precision
+        prec = _pack_prec(prec or self.rt.precision)
         img = self._image(prec)
         key = self._current_key()
         if key != img.key:                     # (the padded speaker-logit layer's copy bumps its _version under capture: recorded too)
@@ -264,7 +278,7 @@ def conv_gemm(x, pack: PackedWeight, bias=None, *, transpose=False, relu=False, 
     ldy = _rows(out)
     _log(pack, ('conv', B_ * N_, N_, cin, cout, pack.taps))
     _fn('dx_conv_gemm', prec)(_p(x), ldx, _p(img.bwd if transpose else img.fwd), _p(bias), _p(out), ldy, B_, N_, cin, cout, pack.taps,
-                       img.half, int(relu), _p(post_scale), _p(post_shift), _p(relu_aux),
+                       _mode(prec), int(relu), _p(post_scale), _p(post_shift), _p(relu_aux),
                        0 if relu_aux is None else _rows(relu_aux), int(accumulate), _p(lens), int(mask_rows), float(out_scale), int(halo),
                        _is_bf16(x), _is_bf16(out), _is_bf16(relu_aux), _p(rows_exist), _stream())
     return out
@@ -468,7 +482,7 @@ def conv_wgrad(dy, x, pack: PackedWeight, lens=None, halo=-1, bias=True, arena=N
                                                     int(halo), 0, _p(rows_exist)), (dy, x, g, db, lens, rows_exist)))
         return None, None
     _fn('dx_conv_wgrad', prec)(_p(dy), _rows(dy), _p(x), _rows(x), _p(g), B_, N_, pack.cin, pack.cout, pack.taps, _p(lens), int(halo),
-                               _half(prec), _is_bf16(dy), _is_bf16(x), _p(db), _p(rows_exist), _stream())
+                               _mode(prec), _is_bf16(dy), _is_bf16(x), _p(db), _p(rows_exist), _stream())
     return (None if w_sink is not None else g), (None if b_sink is not None else db)
 
 
@@ -553,7 +567,7 @@ def attention_fwd(qkv, lens, heads, seed, p_drop, prec=None, seed_offset=None, c
     prec = prec or DEFAULT.precision
     _check_h16(prec, qkv, ctx)
     _fn('dx_attention_fwd', prec)(_p(qkv), _rows(qkv), _p(lens), _p(ctx), D, _p(lse), B, N, heads, D, seed, _p(seed_offset), float(p_drop),
-                           _half(prec), _is_bf16(qkv), _is_bf16(ctx), _p(order), _stream())
+                           _mode(prec), _is_bf16(qkv), _is_bf16(ctx), _p(order), _stream())
     return ctx, lse
 
 
@@ -566,7 +580,7 @@ def attention_bwd(qkv, ctx, dctx, lse, lens, heads, seed, p_drop, out_dtype=torc
     delta = torch.empty(B, heads, N, dtype=torch.float32, device=qkv.device)
     prec = prec or DEFAULT.precision
     _fn('dx_attention_bwd', prec)(_p(qkv), _rows(qkv), _p(ctx), _p(dctx), _rows(dctx), _p(lse), _p(delta), _p(lens), _p(dqkv), _rows(dqkv),
-                           B, N, heads, D, seed, _p(seed_offset), float(p_drop), _half(prec), _is_bf16(qkv), _is_bf16(dqkv), _is_bf16(ctx),
+                           B, N, heads, D, seed, _p(seed_offset), float(p_drop), _mode(prec), _is_bf16(qkv), _is_bf16(dqkv), _is_bf16(ctx),
                            _p(order), _stream())
     return dqkv
 

@@ -13,7 +13,8 @@ from __future__ import annotations
 
 from collections import OrderedDict
 
-PEAK_TFLOPS = {'f32': 157.3, 'bf16': 2500.0}
+# 'bf16x3': an fp32-EQUIVALENT peak -- the bf16 rate over the three split-bf16 MFMAs each fp32 product costs (FLOPs are counted once)
+PEAK_TFLOPS = {'f32': 157.3, 'bf16': 2500.0, 'bf16x3': 2500.0 / 3}
 PEAK_HBM_GBS = 8000.0
 
 
@@ -40,6 +41,8 @@ def _conv_route(a):
     """Mirror of the kernel choice in csrc/dx_gemm.hip dx_conv_gemm (for labelling only)."""
     if not a['bf16']:
         return 'conv_gemm_kernel<f32>'
+    if a['bf16'] == 2:
+        return 'conv_gemm_kernel<bf16x3>'
     cinp = (a['Cin'] + 63) // 64 * 64
     if cinp >= 256 and a['Cin'] % 64 == 0:
         return f"conv_dk_kernel<{a['taps']}>"
@@ -57,7 +60,7 @@ def price(name, a, geom: Geometry):
     if name == 'dx_conv_gemm':
         rows = geom.rows(a['B'], a['N'], has('lens'))
         xb, yb, ab = (2 if a['x_bf16'] else 4), (2 if a['y_bf16'] else 4), (2 if a['aux_bf16'] else 4)
-        wb = 2 if a['bf16'] else 4
+        wb = 2 if a['bf16'] == 1 else 4
         byt = rows * (a['Cin'] * xb + a['Cout'] * yb * (2 if a['accumulate'] else 1) + (a['Cout'] * ab if has('relu_aux') else 0)) \
             + a['taps'] * a['Cin'] * a['Cout'] * wb
         return _conv_route(a), 'mfma', 2.0 * a['taps'] * a['Cin'] * a['Cout'] * rows, byt
@@ -90,7 +93,8 @@ def price(name, a, geom: Geometry):
         rows = geom.rows(a['B'], a['N'], has('lens'))
         byt = rows * (a['Cout'] * (2 if a['dy_bf16'] else 4) + a['Cin'] * (2 if a['x_bf16'] else 4)) + a['taps'] * a['Cin'] * a['Cout'] * 4
         wide = a['Cin'] % 128 == 0 and -(-a['Cout'] // 128) * -(-a['Cin'] // 64) >= 64      # the library's choice of the 128 x 128 tile (dx_gemm.hip)
-        label = (f"wgrad_bf16_kernel<{a['taps']}{',wide' if wide else ''}>" if a['bf16'] and a['Cin'] % 8 == 0 and a['Cout'] % 8 == 0
+        label = (f"wgrad_split_kernel<{a['taps']},bf16x3>" if a['bf16'] == 2
+                 else f"wgrad_bf16_kernel<{a['taps']}{',wide' if wide else ''}>" if a['bf16'] and a['Cin'] % 8 == 0 and a['Cout'] % 8 == 0
                  else f"wgrad_kernel<{a['taps']}>")
         return label, 'mfma', 2.0 * a['taps'] * a['Cin'] * a['Cout'] * rows, byt
     if name == 'dx_conv_wgrad_batched':
@@ -106,10 +110,11 @@ def price(name, a, geom: Geometry):
         rows, pairs = geom.rows(a['B'], a['N']), geom.pairs(a['B'], a['N'])
         D, H = a['D'], a['H']
         qb = 2 if a['qkv_bf16'] else 4
+        sfx = ' <bf16x3>' if a['bf16'] == 2 else ''         # split-bf16 kernels (priced at the fp32-equivalent peak)
         if name == 'dx_attention_fwd':                       # S = QK^T and O = PV: 2 products of 2 N^2 hd per head
-            return 'attn_fwd', 'mfma', 4.0 * pairs * D, rows * (3 * D * qb + D * 4 + H * 4)
+            return 'attn_fwd' + sfx, 'mfma', 4.0 * pairs * D, rows * (3 * D * qb + D * 4 + H * 4)
         gb = 2 if a['dqkv_bf16'] else 4                      # dQ kernel: S, dP, dQ; dK/dV kernel: S, dP, dV, dK: 7 products
-        return 'attn_bwd (dq + dkv)', 'mfma', 14.0 * pairs * D, rows * (2 * 3 * D * qb + 2 * D * 4 + 3 * D * gb + 2 * H * 4)
+        return 'attn_bwd (dq + dkv)' + sfx, 'mfma', 14.0 * pairs * D, rows * (2 * 3 * D * qb + 2 * D * 4 + 3 * D * gb + 2 * H * 4)
     if name in ('dx_pitch_chain_fwd', 'dx_pitch_chain_bwd'):      # the frozen predictor: 3 taps x (M x 256 + 2 x 256 x 256) MACs per token + the one-channel layer
         rows = geom.rows(a['B'], a['T'], True)
         flops = 2.0 * 3 * (a['M'] * 256 + 2 * 256 * 256 + 256) * rows
@@ -194,7 +199,7 @@ def summarize(records, geom: Geometry, precision: str):
         t = e['total_us'] * 1e-6
         r = {'launches': e['launches'], 'total_us': round(e['total_us'], 1), 'avg_us': round(e['total_us'] / e['launches'], 2), 'bound': e['bound']}
         if e['bound'] == 'mfma':
-            peak = PEAK_TFLOPS['f32' if '<f32>' in label or (precision == 'f32') else 'bf16']
+            peak = PEAK_TFLOPS['bf16x3' if 'bf16x3>' in label else 'f32' if '<f32>' in label or precision in ('f32', 'bf16x3') else 'bf16']
             r.update(achieved=round(e['flops'] / t / 1e12, 2), unit='TFLOP/s', peak=peak, frac=round(e['flops'] / t / 1e12 / peak, 4),
                      algorithmic_bytes_per_launch=int(e['bytes'] / e['launches']))
         elif e['unpriced'] == 0:
