@@ -2,6 +2,7 @@
 
     python bench.py --gpus 1 --steps 10 --warmup 3
     python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     # + what the last timed step returned, as DIR/*.npy
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full                 # + sustained run, f32 mode, C4 inference, CPU baseline, roofline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], SURVEY.md §8d "C2"): 48 utterances per GPU, 50-120 symbols, 2-12 frames per symbol
@@ -10,6 +11,9 @@ seeded frozen pitch predictor.  The timed step is the whole training step: forwa
 gradient all-reduce when N > 1) + the fused Adam update and the one-launch weight re-pack that follows it (the metric is
 "fwd+bwd"; the optimiser is a superset of that work, ~1.5 % of a step, and stays inside the timed region so that no work of
 a real training step is skipped).  ``python bench.py --gpus N`` starts its N ranks itself.  One JSON line is printed by rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, dump (if asked) and print.  ``--full`` adds the
+measurements that take runs of their own (a minute or two more) and the figures derived from the last timed step and committed records.
 """
 import argparse
 import json
@@ -118,14 +122,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--precision', default='bf16', choices=['f32', 'bf16', 'fp16'])
     ap.add_argument('--config', default='C2', choices=['C1', 'C2', 'C5'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and report what the headline does not need: the sustained run, the f32-mode step, the C4 inference '
+                         'batch, the CPU baseline, the per-kernel roofline of the last timed step and the committed parity record')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-kernel-events', action='store_true')
     ap.add_argument('--launch-dump', default='', help='write one JSON line per launch of the last (eager, event-bracketed) timed step')
     ap.add_argument('--kernel-table', default='', help='write the per-kernel roofline table of the last timed step to this JSON file')
     ap.add_argument('--no-graph', action='store_true', help='issue every launch from Python instead of replaying the two captured HIP graphs')
     ap.add_argument('--no-dropout', action='store_true', help='diagnostic only: the headline metric is measured with dropout on')
     ap.add_argument('--cuts', default='auto', help="backward phases of the trainer: 'auto' (3 cuts when N > 1, none on one GPU) or 0..3")
-    ap.add_argument('--no-extras', action='store_true', help='skip the sustained run, the f32-mode step and the C4 inference batch that follow the timed region')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the sustained run, the f32-mode step and the C4 inference batch')
     ap.add_argument('--dump-outputs', default='', metavar='DIR',
                     help='write what the last timed step returned (loss, loss terms, gradient norm, seeded samples of the updated parameters '
                          'and their gradients) to DIR/<name>.npy, float32; rank 0 only')
@@ -259,12 +266,12 @@ def main():
         exposed_ms = float(te[0])
 
     roofline = roofline_hbm = table = None
-    if use_events and rank == 0:
+    if use_events and rank == 0 and (args.full or args.launch_dump or args.kernel_table):
         from ubisoft_laforge_daft_exprt_amd import profiling
         geom = profiling.Geometry([batch[9].tolist(), batch[5].tolist()])
         table = profiling.summarize(records, geom, args.precision)
         step_us = 1e6 * elapsed / args.steps
-        mfma = [(k, v) for k, v in table.items() if v['bound'] == 'mfma']
+        mfma = [(k, v) for k, v in table.items() if v['bound'] == 'mfma'] if args.full else []
         if mfma:
             k, v = mfma[0]                                            # the single kernel with the most time in the step
             traffic = traffic_source = None
@@ -282,10 +289,11 @@ def main():
                         'measured_on': 'events around every launch of this kernel in the last timed step',
                         'other_mfma_kernels': {kk: {'frac': vv['frac'], 'achieved': vv['achieved'], 'launches': vv['launches'], 'avg_us': vv['avg_us'],
                                                     'share_of_step': round(vv['total_us'] / step_us, 3)} for kk, vv in mfma[1:8]}}
-        roofline_hbm = {k: {'achieved': v['achieved'], 'unit': 'GB/s', 'peak': v['peak'], 'frac': v['frac'], 'launches': v['launches'],
-                            'avg_us': v['avg_us'], 'algorithmic_bytes_per_launch': v['algorithmic_bytes_per_launch'],
-                            'share_of_step': round(v['total_us'] / step_us, 3)}
-                        for k, v in table.items() if v['bound'] == 'hbm' and 'achieved' in v and v['total_us'] / step_us >= 0.002}
+        if args.full:
+            roofline_hbm = {k: {'achieved': v['achieved'], 'unit': 'GB/s', 'peak': v['peak'], 'frac': v['frac'], 'launches': v['launches'],
+                                'avg_us': v['avg_us'], 'algorithmic_bytes_per_launch': v['algorithmic_bytes_per_launch'],
+                                'share_of_step': round(v['total_us'] / step_us, 3)}
+                            for k, v in table.items() if v['bound'] == 'hbm' and 'achieved' in v and v['total_us'] / step_us >= 0.002}
         if args.launch_dump:                                          # every launch of the eager step in issue order: entry point, shape arguments, us
             keep = ('B', 'N', 'Cin', 'Cout', 'taps', 'F', 'C', 'L', 'T', 'D', 'H', 'transpose', 'accumulate', 'njobs', 'rows', 'n')
             with open(args.launch_dump, 'w') as f:
@@ -297,9 +305,10 @@ def main():
                 json.dump({'precision': args.precision, 'config': args.config, 'ms_per_step': 1e3 * elapsed / args.steps, 'kernels': table}, f, indent=1)
 
     # ---- what follows the timed region: numbers that used to exist only in builder-run files -------------------------
+    # --full only: a plain run stops at the headline and what is read off its timed steps
     extras = {}
     ms_step = 1e3 * elapsed / args.steps
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # (1) sustained: the same captured step replayed for >= 2 s (the timed region above is a 0.13 s burst; clocks sag under
         #     sustained MFMA load).  Every rank takes part (the step contains the collectives); the count comes from the max-over-ranks time.
         n_sus = max(args.steps, int(2000.0 / ms_step) + 1)
@@ -315,7 +324,7 @@ def main():
         sus = time.perf_counter() - ts
         extras['sustained'] = {'seconds': round(sus, 3), 'steps': n_sus, 'ms_per_step': round(1e3 * sus / n_sus, 3),
                                'value': round(total_frames * n_sus / sus, 1)}
-    if not args.no_extras and world == 1 and rank == 0:
+    if args.full and not args.no_extras and world == 1 and rank == 0:
         # (2) the parity mode (exact-f32 MFMA operands: the mode that meets the 1e-4 mel-L1 bar), same batch, same trainer structure
         if args.precision != 'f32':
             pkg.set_precision('f32')
@@ -351,7 +360,7 @@ def main():
     # (4) parity of the measured mode on the measured shape, from the last committed GPU test record (tests/test_configs_gpu.py)
     parity = None
     import glob
-    recs = sorted(glob.glob(os.path.join(REPO, 'profiles', f'r*_parity_{args.config.lower()}_{args.precision}.json')))
+    recs = sorted(glob.glob(os.path.join(REPO, 'profiles', f'r*_parity_{args.config.lower()}_{args.precision}.json'))) if args.full else []
     if recs:
         with open(recs[-1]) as f:
             pr = json.load(f)
@@ -399,7 +408,7 @@ def main():
             result['roofline'] = roofline
         if roofline_hbm:
             result['roofline_hbm'] = roofline_hbm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             avail = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
             cores = min(avail, 16)                                       # a 1-GPU box is given a 16-CPU share
             result['cpu_baseline'] = cpu_baseline(hp, cores, args.config, n_speakers)

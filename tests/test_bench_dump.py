@@ -75,3 +75,25 @@ def test_bench_steps_ms_per_step_and_dump(tmp_path):
     assert a['loss_terms'].shape == (1, 7) and np.isfinite(a['loss_terms']).all()
     assert np.isfinite(a['grad_norm']) and a['grad_norm'] > 0
     assert np.isfinite(a['params_sample']).all() and np.isfinite(a['grads_sample']).all() and np.any(a['grads_sample'] != 0)
+
+
+FULL_ONLY = ('sustained', 'f32_mode', 'inference_c4', 'cpu_baseline', 'roofline', 'roofline_hbm', 'parity')
+
+
+def test_full_is_offered():
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--help'], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and '--full' in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_only():
+    """Without --full the run times its steps and prints the headline: none of the measurements that take runs of their own."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1'],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res['metric'] == 'mel frames/sec (fwd+bwd)' and res['unit'] == 'valid mel frames/s' and res['higher_is_better'] is True
+    assert res['dtype'] == 'bf16' and res['steps'] == 2 and res['warmup'] == 1 and res['ms_per_step'] > 0 and res['value'] > 0
+    assert not [k for k in FULL_ONLY if k in res]
