@@ -304,6 +304,34 @@ int dx_adam_step(float* p, const float* g, float* m, float* v, long n, float lr,
                  float weight_decay, int step, const float* normsq, float max_norm, float grad_scale, int* skipped,
                  float* norm_out, float* zero_after, void* stream);
 
+/* ---- HiFi-GAN V1 vocoder, inference (reference vocoder/hifigan.py HiFiGANGenerator.forward; csrc/dx_vocoder.hip) ----------------
+ * Activations are fp32, channels-last [B][samples][C] (conv_pre reads the (B, 80, T) mel through its strides).  frames (device int32
+ * [B]) with a samples-per-frame scale gives each batch row's valid length: input rows at or past it read as the conv's zero padding,
+ * output rows there are written as 0, so batch row b equals what the same row computes alone (bitwise: fixed summation order, no
+ * atomics).  bf16 = 0: exact f32 (v_mfma_f32_16x16x4_f32), 1: bf16 operands (v_mfma_f32_16x16x32_bf16), fp32 accumulate and storage. */
+/* bytes of the weight pack dx_voc_pack writes for one layer (up > 1: a ConvTranspose1d in polyphase form, taps = 2) */
+int dx_voc_pack_size(int Cout, int Cin, int taps, int up, int bf16, long* bytes);
+/* folded weights -> the operand pack of dx_voc_conv / dx_voc_pair.  up == 1: W (Cout, Cin, taps) of a Conv1d; up > 1 (even): W (Cin,
+ * Cout, 2 up) of ConvTranspose1d(stride up, padding up / 2), packed as up phases of 2 taps (output sample s up + r reads input
+ * samples s + base_r and s + base_r + 1, base_r = -1 if r + up / 2 < up else 0). */
+int dx_voc_pack(const float* W, void* Wp, int Cout, int Cin, int taps, int up, int bf16, void* stream);
+/* Y = acc_mode( conv(lrelu?(X)) + bias (+ R) ): a dilated Conv1d ('same' padding dil (taps - 1) / 2; odd taps <= 11) or, with up > 1
+ * and taps = 2, the polyphase ConvTranspose1d (N input rows -> N up output rows).  X element (b, n, c) at X[b sxb + n sxn + c sxc];
+ * Y and R (optional residual, may equal Y; Y must not alias X) are channels-last with batch stride syb; a channels-last X is 16-byte aligned.  Input rows n >= min(frames[b] in_scale, N) are
+ * zero.  acc_mode 0: Y = v, 1: Y += v, 2: Y = (Y + v) / 3 (the generator's stage mean over its three ResBlocks). */
+int dx_voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const float* bias, float* Y, long syb, const float* R,
+                const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in, int acc_mode,
+                int bf16, void* stream);
+/* One ResBlock1 pair in one launch (C in {32, 64}): Y = acc_mode( conv2(lrelu(conv1(lrelu(X)) + b1)) + b2 + X ), conv1 dilation dil,
+ * conv2 dilation 1, both `taps` wide; the intermediate stays in LDS with its halo.  X, Y channels-last [B][N][C] with batch stride
+ * sxb; Y must not alias X. */
+int dx_voc_pair(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y,
+                const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, void* stream);
+/* conv_post: Y[b][s] = clip(tanh(conv7(lrelu(X)) + bias), -1, 1) for s < min(frames[b] scale, N), 0 for the rest of the ncols samples.
+ * X channels-last [B][N][32] (batch stride sxb), W the folded (1, 32, 7) fp32 weight. */
+int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                int B, int N, int ncols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

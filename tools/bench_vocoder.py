@@ -1,0 +1,91 @@
+"""HiFi-GAN V1 vocoder throughput: B = 16 synthetic utterances of up to 850 frames (C4-like lengths), synthetic weights.
+One JSON line: mel frames/s, seconds of 22.05 kHz audio per second and TFLOP/s against 614 MFLOP per frame, for the HIP path (f32, bf16),
+tests/vocoder_torch.py batched on the same GPU (fp32, bf16) and vocoder_torch at B = 1 per utterance (fp32: the reference's way; bf16).
+Every rate divides VALID frames by the time.  The HIP path computes valid frames only (tiles past a row's length write zeros); the batched
+torch rows compute the whole padded (B, 80, T_max) grid ('frames_computed'), the B = 1 rows exactly the valid frames, so
+'hip_bf16_over_torch_bf16_b1' compares equal work and 'hip_bf16_over_torch_bf16' what a caller with a padded batch gets.
+
+    python tools/bench_vocoder.py [--profile]      # --profile: + per-kernel times of one bf16 and one f32 HIP call
+"""
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import torch  # noqa: E402
+
+from tests import vocoder_helpers as vh  # noqa: E402
+from tests import vocoder_torch  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd import profiling, vocoder as voc  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd import _lib  # noqa: E402
+
+MFLOP_PER_FRAME = 614.0
+B, T_MAX = 16, 850
+
+
+def timed(fn, n=5, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n
+
+
+def rates(t, frames, computed=None):
+    """valid-frame rates; ``computed``: frames the path actually computes (padding included), reported with its own TFLOP/s."""
+    r = {'s': round(t, 5), 'frames_per_s': round(frames / t, 1), 'audio_s_per_s': round(frames * 256 / 22050 / t, 1),
+         'tflops': round(frames * MFLOP_PER_FRAME * 1e6 / t / 1e12, 2)}
+    if computed is not None:
+        r.update(frames_computed=computed, tflops_computed=round(computed * MFLOP_PER_FRAME * 1e6 / t / 1e12, 2))
+    return r
+
+
+def main():
+    dev = 'cuda'
+    g = torch.Generator().manual_seed(3)
+    lengths = torch.randint(T_MAX // 2, T_MAX + 1, (B,), generator=g)
+    lengths[0] = T_MAX
+    frames = int(lengths.sum())
+    mels = ((torch.randn(B, 80, T_MAX, generator=g) * 1.5 - 5.0).clamp(-11.5, 2.0)).to(dev)
+    for b, n in enumerate(lengths.tolist()):
+        mels[b, :, n:] = 0
+    lens_dev = lengths.to(dev)
+    sd = vh.state_dict()
+    out = {'workload': f'B={B} utterances, {frames} mel frames (max {T_MAX})', 'mflop_per_frame': MFLOP_PER_FRAME}
+    voc_by = {}
+    with torch.no_grad():
+        for prec in ('f32', 'bf16'):
+            v = voc.HiFiGanVocoder(sd, device=dev, precision=prec)
+            voc_by[prec] = v
+            out[f'hip_{prec}'] = rates(timed(lambda: v.infer_batch(mels, lens_dev)), frames)
+        w32 = vocoder_torch.to(voc_by['f32'].weights, dev)
+        w16 = vocoder_torch.to(voc_by['f32'].weights, dev, torch.bfloat16)
+        padded = B * T_MAX
+        out['torch_fp32_batched'] = rates(timed(lambda: vocoder_torch.generator(mels, w32)), frames, padded)
+        m16 = mels.to(torch.bfloat16)
+        out['torch_bf16_batched'] = rates(timed(lambda: vocoder_torch.generator(m16, w16)), frames, padded)
+        per = [mels[b:b + 1, :, :n].contiguous() for b, n in enumerate(lengths.tolist())]
+        out['torch_fp32_b1'] = rates(timed(lambda: [vocoder_torch.generator(m, w32) for m in per], n=2, warm=1), frames, frames)
+        per16 = [m.to(torch.bfloat16) for m in per]
+        out['torch_bf16_b1'] = rates(timed(lambda: [vocoder_torch.generator(m, w16) for m in per16], n=2, warm=1), frames, frames)
+        out['hip_bf16_over_torch_bf16'] = round(out['torch_bf16_batched']['s'] / out['hip_bf16']['s'], 2)
+        out['hip_bf16_over_torch_bf16_b1'] = round(out['torch_bf16_b1']['s'] / out['hip_bf16']['s'], 2)
+        if '--profile' in sys.argv:
+            geom = profiling.Geometry([lengths.tolist()])
+            for prec in ('bf16', 'f32'):
+                recs = []
+                old = _lib.set_timer(recs)
+                voc_by[prec].infer_batch(mels, lens_dev)
+                _lib.set_timer(old)
+                torch.cuda.synchronize()
+                out[f'profile_{prec}'] = profiling.summarize(recs, geom, prec)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

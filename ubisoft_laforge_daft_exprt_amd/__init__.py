@@ -9,3 +9,4 @@ from .model import DaftExprt  # noqa: F401
 from .loss import DaftExprtLoss  # noqa: F401
 from .functional import manual_seed  # noqa: F401
 from .ops import set_precision, get_precision, Runtime  # noqa: F401
+from .vocoder import HiFiGANGenerator, HiFiGanVocoder, load_hifigan_vocoder  # noqa: F401

@@ -1,0 +1,440 @@
+// HiFi-GAN V1 generator (reference src/daft_exprt/vocoder/hifigan.py) for inference: mel (B, 80, T) -> waveform (B, 256 T).
+//
+// Every convolution of the generator is one MFMA GEMM over a tile of 64 output samples of ONE batch row:
+//   out[m][n] = sum_t sum_c A[m - pad + t*dil][c] * W[t][c][n]
+// A is the input window staged in LDS (64 channels per chunk, leaky-ReLU prologue applied while staging, rows outside the row's
+// valid length read as zero), W a pack of dx_voc_pack read fragment by fragment from L2.  Exact-f32 mode: v_mfma_f32_16x16x4_f32
+// (four per 16-wide k step, each lane's float4 holds k = 4g..4g+3); bf16 mode: v_mfma_f32_16x16x32_bf16 (lane (row, g) holds
+// k = 8g..8g+7), fp32 accumulation, fp32 storage between layers.  A and B use the same k map, so any permutation inside a step cancels.
+//
+// Valid lengths.  Every launch takes frames[b] (device int32) and the samples per frame of its input; rows of batch row b at or
+// past frames[b] * scale do not exist: they are the conv's zero padding when read and are written as 0.  Tiles start at sample 0 of
+// each batch row and every output element is summed in a fixed order, so batch row b is bitwise what the same row computes alone.
+//
+// The transposed convolutions (k = 2u, stride u, padding u/2) run in polyphase form: output sample s*u + r is a 2-tap conv of
+// input samples s + base_r, s + base_r + 1 (base_r = -1 if r + u/2 < u else 0) with the phase's own 2 x Cin x Cout slice of W;
+// grid.z = phase.  ResBlock1 pairs (conv dil d -> conv dil 1) of the 64- and 32-channel stages run fused (dx_voc_pair): the
+// intermediate stays in LDS with its halo.
+#include "dx_common.h"
+
+namespace {
+
+constexpr float VOC_SLOPE = 0.1f;
+constexpr int VT = 64;          // output samples per tile (4 MFMA row blocks)
+constexpr int KC = 64;          // input channels per LDS chunk
+constexpr int MIDR = 80;        // rows of the fused pair's intermediate: 64 + 2 * halo (halo <= 5), rounded up to 16
+constexpr int THREADS = 256;
+
+__device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * VOC_SLOPE; }
+
+template <bool BF> struct VocOp;
+template <> struct VocOp<false> {
+  typedef float T;
+  static constexpr int KS = 16, VEC = 4, PAD = 4;
+  __device__ static __forceinline__ T cvt(float v) { return v; }
+  __device__ static __forceinline__ f32x4 mma(const uint4& a4, const uint4& b4, f32x4 c) {
+    const f32x4 a = __builtin_bit_cast(f32x4, a4), b = __builtin_bit_cast(f32x4, b4);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+    return c;
+  }
+};
+template <> struct VocOp<true> {
+  typedef __bf16 T;
+  static constexpr int KS = 32, VEC = 8, PAD = 8;
+  __device__ static __forceinline__ T cvt(float v) { return (__bf16)v; }
+  __device__ static __forceinline__ f32x4 mma(const uint4& a, const uint4& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dx_bf16x8, a), __builtin_bit_cast(dx_bf16x8, b), c, 0, 0, 0);
+  }
+};
+
+// A[rr][cc] = lrelu?(X[b][row0 + rr][c0 + cc]) for rr < R, cc < kcw; 0 outside [0, len) x [0, Cin).  Channels-last rows (sxc == 1,
+// sxn >= Cin) are read as float4; any other layout (the (B, 80, T) mel, whose channel stride is 1 too when T == 1) element-wise.
+template <bool BF>
+__device__ __forceinline__ void voc_stage(typename VocOp<BF>::T* A, int lda, int R, const float* X, long sxn, long sxc,
+                                          int row0, int len, int c0, int kcw, int Cin, int pro) {
+  typedef VocOp<BF> Op;
+  if (sxc == 1 && sxn >= Cin) {
+    const int q = kcw >> 2;
+    for (int e = threadIdx.x; e < R * q; e += THREADS) {
+      const int rr = e / q, cc = (e - rr * q) * 4, n = row0 + rr, c = c0 + cc;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (n >= 0 && n < len && c < Cin) {
+        v = *reinterpret_cast<const float4*>(X + (long)n * sxn + c);
+        if (pro) { v.x = lrelu(v.x); v.y = lrelu(v.y); v.z = lrelu(v.z); v.w = lrelu(v.w); }
+      }
+      typename Op::T* d = A + rr * lda + cc;
+      d[0] = Op::cvt(v.x); d[1] = Op::cvt(v.y); d[2] = Op::cvt(v.z); d[3] = Op::cvt(v.w);
+    }
+  } else {
+    for (int e = threadIdx.x; e < R * kcw; e += THREADS) {
+      const int cc = e / R, rr = e - cc * R, n = row0 + rr, c = c0 + cc;
+      float v = 0.f;
+      if (n >= 0 && n < len && c < Cin) {
+        v = X[(long)n * sxn + (long)c * sxc];
+        if (pro) v = lrelu(v);
+      }
+      A[rr * lda + cc] = Op::cvt(v);
+    }
+  }
+}
+
+// acc[i][j] += sum_t sum_{k step s < nks} A[(16 mb_j + row + t*dil)][s*KS ...] * W[t][nb_i][ks0 + s]
+// wave (wn, wm) owns column blocks nb_i = wn + i*WN and row blocks mb_j = wm + j*WM (< MB).
+template <bool BF, int NI, int MI>
+__device__ __forceinline__ void voc_mma(const typename VocOp<BF>::T* A, int lda, int MB, int taps, int dil, const uint4* Wp,
+                                        int NB, int KST, int ks0, int nks, int wn, int WN, int wm, int WM, f32x4 (&acc)[NI][MI]) {
+  typedef VocOp<BF> Op;
+  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+  for (int t = 0; t < taps; ++t) {
+    for (int s = 0; s < nks; ++s) {
+      uint4 b[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) b[i] = Wp[((long)(t * NB + wn + i * WN) * KST + ks0 + s) * 64 + lane];
+#pragma unroll
+      for (int j = 0; j < MI; ++j) {
+        const int mb = wm + j * WM;
+        if (mb < MB) {
+          const uint4 a = *reinterpret_cast<const uint4*>(A + (mb * 16 + r + t * dil) * lda + s * Op::KS + g * Op::VEC);
+#pragma unroll
+          for (int i = 0; i < NI; ++i) acc[i][j] = Op::mma(a, b[i], acc[i][j]);
+        }
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ float voc_finish(float v, const float* y, int acc_mode) {
+  if (acc_mode == 1) return *y + v;
+  if (acc_mode == 2) return (*y + v) / 3.0f;
+  return v;
+}
+
+struct ConvArgs {
+  const float* X; long sxb, sxn, sxc;
+  const uint4* Wp; const float* bias;
+  float* Y; long syb; const float* R;
+  const int* frames; int in_scale;
+  int N, Cin, Cout, taps, dil, pad, up, KST, pro, acc_mode;
+};
+
+// One conv (up == 1) or one phase of a transposed conv (up > 1, grid.z = phase) on a 64-sample tile of one batch row.
+template <bool BF, int NI, int MI>
+__global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p) {
+  typedef VocOp<BF> Op;
+  typedef typename Op::T T;
+  extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
+  T* A = reinterpret_cast<T*>(voc_smem);
+  const int b = blockIdx.y, ph = blockIdx.z, m0 = blockIdx.x * VT;
+  const int in_len = min(p.frames[b] * p.in_scale, p.N);
+  const int out_len = in_len * p.up;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  float* Y = p.Y + b * p.syb;
+  const int NB = p.Cout / 16;
+  const int WN = NB < 4 ? NB : 4, WM = 4 / WN, wn = w % WN, wm = w / WN;
+  if (m0 * p.up + ph >= out_len) {                   // no valid output row in this tile: zeros only
+    for (int e = threadIdx.x; e < VT * p.Cout; e += THREADS) {
+      const int m = m0 + e / p.Cout, n = e % p.Cout;
+      if (m < p.N) Y[(long)(m * p.up + ph) * p.Cout + n] = 0.f;
+    }
+    return;
+  }
+  int pad = p.pad;
+  const uint4* Wp = p.Wp;
+  if (p.up > 1) {
+    pad = (ph + p.up / 2 < p.up) ? 1 : 0;
+    Wp += (long)ph * 2 * NB * p.KST * 64;
+  }
+  const int rows = VT + (p.taps - 1) * p.dil, lda = KC + Op::PAD;
+  const float* X = p.X + b * p.sxb;
+  f32x4 acc[NI][MI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < MI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int KP = p.KST * Op::KS;
+  for (int c0 = 0; c0 < KP; c0 += KC) {
+    const int kcw = min(KC, KP - c0);
+    __syncthreads();
+    voc_stage<BF>(A, lda, rows, X, p.sxn, p.sxc, m0 - pad, in_len, c0, kcw, p.Cin, p.pro);
+    __syncthreads();
+    voc_mma<BF, NI, MI>(A, lda, 4, p.taps, p.dil, Wp, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc);
+  }
+  const float* R = p.R ? p.R + b * p.syb : nullptr;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int n = (wn + i * WN) * 16 + r;
+    const float bn = p.bias ? p.bias[n] : 0.f;
+#pragma unroll
+    for (int j = 0; j < MI; ++j) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int m = m0 + (wm + j * WM) * 16 + 4 * g + e;
+        if (m >= p.N) continue;
+        const long o = (long)(m * p.up + ph) * p.Cout + n;
+        float v = 0.f;
+        if (m * p.up + ph < out_len) {
+          v = acc[i][j][e] + bn;
+          if (R) v += R[o];
+          v = voc_finish(v, Y + o, p.acc_mode);
+        }
+        Y[o] = v;
+      }
+    }
+  }
+}
+
+struct PairArgs {
+  const float* X; long sxb;
+  const uint4* W1; const float* b1; const uint4* W2; const float* b2;
+  float* Y;
+  const int* frames; int scale;
+  int N, C, taps, dil, KST, acc_mode;
+};
+
+// Y = acc_mode( conv2(lrelu(conv1(lrelu(X)) + b1)) + b2 + X ): one ResBlock1 pair, intermediate (80 rows with halo) in LDS.
+template <bool BF, int MI1, int MI2>
+__global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p) {
+  typedef VocOp<BF> Op;
+  typedef typename Op::T T;
+  extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
+  const int b = blockIdx.y, s0 = blockIdx.x * VT, C = p.C;
+  const int len = min(p.frames[b] * p.scale, p.N);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  float* Y = p.Y + b * p.sxb;
+  if (s0 >= len) {
+    for (int e = threadIdx.x; e < VT * C; e += THREADS) {
+      const int m = s0 + e / C;
+      if (m < p.N) Y[(long)m * C + e % C] = 0.f;
+    }
+    return;
+  }
+  const int h2 = (p.taps - 1) / 2, h1 = p.dil * h2;
+  const int rows = MIDR + 2 * h1, lda = KC + Op::PAD, ldm = C + Op::PAD;
+  T* A = reinterpret_cast<T*>(voc_smem);
+  T* M = A + rows * lda;
+  const int NB = C / 16, WN = NB < 4 ? NB : 4, WM = 4 / WN, wn = w % WN, wm = w / WN;
+  const float* X = p.X + b * p.sxb;
+  f32x4 acc1[1][MI1];
+#pragma unroll
+  for (int j = 0; j < MI1; ++j) acc1[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int c0 = 0; c0 < C; c0 += KC) {
+    const int kcw = min(KC, C - c0);
+    __syncthreads();
+    voc_stage<BF>(A, lda, rows, X, C, 1, s0 - h2 - h1, len, c0, kcw, C, 1);
+    __syncthreads();
+    voc_mma<BF, 1, MI1>(A, lda, MIDR / 16, p.taps, p.dil, p.W1, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc1);
+  }
+  {
+    const int n = wn * 16 + r;
+    const float bn = p.b1[n];
+#pragma unroll
+    for (int j = 0; j < MI1; ++j) {
+      const int mb = wm + j * WM;
+      if (mb < MIDR / 16) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int q = mb * 16 + 4 * g + e, s = s0 - h2 + q;
+          M[q * ldm + n] = Op::cvt((s >= 0 && s < len) ? lrelu(acc1[0][j][e] + bn) : 0.f);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  f32x4 acc2[1][MI2];
+#pragma unroll
+  for (int j = 0; j < MI2; ++j) acc2[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  voc_mma<BF, 1, MI2>(M, ldm, VT / 16, p.taps, 1, p.W2, NB, p.KST, 0, p.KST, wn, WN, wm, WM, acc2);
+  const int n = wn * 16 + r;
+  const float bn = p.b2[n];
+#pragma unroll
+  for (int j = 0; j < MI2; ++j) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int m = s0 + (wm + j * WM) * 16 + 4 * g + e;
+      if (m >= p.N) continue;
+      const long o = (long)m * C + n;
+      float v = 0.f;
+      if (m < len) v = voc_finish(acc2[0][j][e] + bn + X[o], Y + o, p.acc_mode);
+      Y[o] = v;
+    }
+  }
+}
+
+// conv_post (32 -> 1, k = 7, padding 3) on lrelu(X), then tanh and the clip to [-1, 1]; one output sample per thread.
+// Y row b holds ncols samples: those at or past the row's valid length are written as 0.
+__global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy,
+                                                           const int* frames, int scale, int N, int ncols) {
+  __shared__ float ws[32 * 7];
+  for (int e = threadIdx.x; e < 32 * 7; e += THREADS) ws[e] = W[e];
+  __syncthreads();
+  const int b = blockIdx.y, s = blockIdx.x * THREADS + threadIdx.x;
+  if (s >= ncols) return;
+  const int len = min(frames[b] * scale, N);
+  float v = 0.f;
+  if (s < len) {
+    const float* x = X + b * sxb;
+    float acc = 0.f;
+    for (int t = 0; t < 7; ++t) {
+      const int n = s - 3 + t;
+      if (n < 0 || n >= len) continue;
+      const float4* xr = reinterpret_cast<const float4*>(x + (long)n * 32);
+#pragma unroll
+      for (int c4 = 0; c4 < 8; ++c4) {
+        const float4 q = xr[c4];
+        acc = __builtin_fmaf(lrelu(q.x), ws[(4 * c4 + 0) * 7 + t], acc);
+        acc = __builtin_fmaf(lrelu(q.y), ws[(4 * c4 + 1) * 7 + t], acc);
+        acc = __builtin_fmaf(lrelu(q.z), ws[(4 * c4 + 2) * 7 + t], acc);
+        acc = __builtin_fmaf(lrelu(q.w), ws[(4 * c4 + 3) * 7 + t], acc);
+      }
+    }
+    v = fminf(fmaxf(tanhf(acc + bias[0]), -1.f), 1.f);
+  }
+  Y[(long)b * ldy + s] = v;
+}
+
+// Pack: [phase][t][nb][ks][lane][VEC]; lane (n = l & 15, g = l >> 4) element v holds k = ks*KS + g*VEC + v of column nb*16 + n.
+// up == 1: W (Cout, Cin, taps); up > 1: W (Cin, Cout, 2 up) of a ConvTranspose1d, tap t of phase r = kernel index j0(r) - t*up.
+template <bool BF>
+__global__ void voc_pack_kernel(const float* W, void* out, int Cout, int Cin, int taps, int up, int KST, long total) {
+  typedef VocOp<BF> Op;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int NB = Cout / 16, v = (int)(e % Op::VEC);
+  long f = e / Op::VEC;
+  const int lane = (int)(f % 64); f /= 64;
+  const int ks = (int)(f % KST); f /= KST;
+  const int nb = (int)(f % NB); f /= NB;
+  const int t = (int)(f % taps); f /= taps;
+  const int ph = (int)f;
+  const int k = ks * Op::KS + (lane >> 4) * Op::VEC + v, n = nb * 16 + (lane & 15);
+  float val = 0.f;
+  if (k < Cin) {
+    if (up == 1) {
+      val = W[((long)n * Cin + k) * taps + t];
+    } else {
+      const int q = ph + up / 2, j = (q < up ? q + up : q) - t * up;
+      val = W[((long)k * Cout + n) * (2 * up) + j];
+    }
+  }
+  reinterpret_cast<typename Op::T*>(out)[e] = Op::cvt(val);
+}
+
+long voc_pack_elems(int Cout, int Cin, int taps, int up, int bf16) {
+  const int KS = bf16 ? 32 : 16;
+  return (long)(up > 1 ? up : 1) * taps * (Cout / 16) * dx_cdiv(Cin, KS) * 64 * (bf16 ? 8 : 4);
+}
+
+template <bool BF, int NI, int MI>
+int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
+  typedef VocOp<BF> Op;
+  const size_t smem = (size_t)(VT + (a.taps - 1) * a.dil) * (KC + Op::PAD) * sizeof(typename Op::T);
+  hipLaunchKernelGGL((voc_conv_kernel<BF, NI, MI>), dim3(dx_cdiv(a.N, VT), B, a.up), dim3(THREADS), smem, s, a);
+  DX_LAUNCH_CHECK("dx_voc_conv");
+  return DX_OK;
+}
+
+template <bool BF>
+int dispatch_conv(const ConvArgs& a, int B, hipStream_t s) {
+  switch (a.Cout / 16) {
+    case 32: return launch_conv<BF, 8, 4>(a, B, s);
+    case 16: return launch_conv<BF, 4, 4>(a, B, s);
+    case 8: return launch_conv<BF, 2, 4>(a, B, s);
+    case 4: return launch_conv<BF, 1, 4>(a, B, s);
+    default: return launch_conv<BF, 1, 2>(a, B, s);
+  }
+}
+
+template <bool BF, int MI1, int MI2>
+int launch_pair(const PairArgs& a, int B, hipStream_t s) {
+  typedef VocOp<BF> Op;
+  const int h1 = a.dil * (a.taps - 1) / 2;
+  const size_t smem = ((size_t)(MIDR + 2 * h1) * (KC + Op::PAD) + (size_t)MIDR * (a.C + Op::PAD)) * sizeof(typename Op::T);
+  hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a);
+  DX_LAUNCH_CHECK("dx_voc_pair");
+  return DX_OK;
+}
+
+bool voc_taps_ok(int taps, int dil) { return (taps == 3 || taps == 7 || taps == 11) && (dil == 1 || dil == 3 || dil == 5); }
+
+}  // namespace
+
+extern "C" {
+
+int dx_voc_pack_size(int Cout, int Cin, int taps, int up, int bf16, long* bytes) {
+  DX_REQUIRE(bytes, "dx_voc_pack_size: null output");
+  DX_REQUIRE(Cout > 0 && Cout % 16 == 0 && Cin > 0 && taps > 0 && up >= 1 && (up == 1 || taps == 2) && (bf16 == 0 || bf16 == 1),
+             "dx_voc_pack_size: bad shape (Cout %% 16 == 0; a transposed conv (up > 1) has taps = 2 in polyphase form)");
+  *bytes = voc_pack_elems(Cout, Cin, taps, up, bf16) * (bf16 ? 2 : 4);
+  return DX_OK;
+}
+
+int dx_voc_pack(const float* W, void* Wp, int Cout, int Cin, int taps, int up, int bf16, void* stream) {
+  DX_REQUIRE(W && Wp, "dx_voc_pack: null pointer");
+  DX_REQUIRE(Cout > 0 && Cout % 16 == 0 && Cin > 0 && taps > 0 && up >= 1 && (up == 1 || (taps == 2 && up % 2 == 0)) && (bf16 == 0 || bf16 == 1),
+             "dx_voc_pack: bad shape (Cout %% 16 == 0; a transposed conv (up > 1, even) has taps = 2 in polyphase form)");
+  const long total = voc_pack_elems(Cout, Cin, taps, up, bf16);
+  const int KST = dx_cdiv(Cin, bf16 ? 32 : 16);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (bf16)
+    hipLaunchKernelGGL(voc_pack_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, W, Wp, Cout, Cin, taps, up, KST, total);
+  else
+    hipLaunchKernelGGL(voc_pack_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, W, Wp, Cout, Cin, taps, up, KST, total);
+  DX_LAUNCH_CHECK("dx_voc_pack");
+  return DX_OK;
+}
+
+int dx_voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const float* bias, float* Y, long syb, const float* R,
+                const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in, int acc_mode,
+                int bf16, void* stream) {
+  DX_REQUIRE(X && Wp && Y && frames, "dx_voc_conv: null pointer");
+  DX_REQUIRE(B > 0 && N > 0 && in_scale > 0 && Cin > 0 && (Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512),
+             "dx_voc_conv: bad shape (Cout in {32, 64, 128, 256, 512})");
+  DX_REQUIRE(up == 1 ? (taps % 2 == 1 && taps <= 11 && dil >= 1 && dil <= 5) : (taps == 2 && dil == 1 && up % 2 == 0 && up <= 8),
+             "dx_voc_conv: bad taps / dilation / upsampling (odd taps <= 11 with dilation <= 5, or a polyphase transposed conv: taps 2, even up <= 8)");
+  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_conv: bad acc_mode / bf16");
+  DX_REQUIRE((const void*)X != (const void*)Y, "dx_voc_conv: Y must not alias X (tiles read their neighbours' rows); R may alias Y");
+  DX_REQUIRE(sxc != 1 || sxn < Cin || (Cin % 4 == 0 && sxn % 4 == 0 && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0),
+             "dx_voc_conv: channels-last input needs Cin and strides %% 4 == 0 and a 16-byte aligned X");
+  ConvArgs a;
+  a.X = X; a.sxb = sxb; a.sxn = sxn; a.sxc = sxc;
+  a.Wp = reinterpret_cast<const uint4*>(Wp); a.bias = bias;
+  a.Y = Y; a.syb = syb; a.R = R;
+  a.frames = frames; a.in_scale = in_scale;
+  a.N = N; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.dil = dil; a.pad = dil * (taps - 1) / 2; a.up = up;
+  a.KST = dx_cdiv(Cin, bf16 ? 32 : 16); a.pro = lrelu_in; a.acc_mode = acc_mode;
+  return bf16 ? dispatch_conv<true>(a, B, (hipStream_t)stream) : dispatch_conv<false>(a, B, (hipStream_t)stream);
+}
+
+int dx_voc_pair(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y,
+                const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, void* stream) {
+  DX_REQUIRE(X && W1 && b1 && W2 && b2 && Y && frames, "dx_voc_pair: null pointer");
+  DX_REQUIRE(X != Y, "dx_voc_pair: Y must not alias X (tiles read their neighbours' rows)");
+  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && (C == 32 || C == 64) && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
+             "dx_voc_pair: bad shape (C in {32, 64}; sxb %% 4 == 0 and a 16-byte aligned X)");
+  DX_REQUIRE(voc_taps_ok(taps, dil), "dx_voc_pair: bad taps / dilation (taps 3, 7 or 11; dilation 1, 3 or 5)");
+  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_pair: bad acc_mode / bf16");
+  PairArgs a;
+  a.X = X; a.sxb = sxb;
+  a.W1 = reinterpret_cast<const uint4*>(W1); a.b1 = b1; a.W2 = reinterpret_cast<const uint4*>(W2); a.b2 = b2;
+  a.Y = Y; a.frames = frames; a.scale = scale;
+  a.N = N; a.C = C; a.taps = taps; a.dil = dil; a.KST = C / (bf16 ? 32 : 16); a.acc_mode = acc_mode;
+  hipStream_t s = (hipStream_t)stream;
+  if (C == 64) return bf16 ? launch_pair<true, 5, 4>(a, B, s) : launch_pair<false, 5, 4>(a, B, s);
+  return bf16 ? launch_pair<true, 3, 2>(a, B, s) : launch_pair<false, 3, 2>(a, B, s);
+}
+
+int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                int B, int N, int ncols, void* stream) {
+  DX_REQUIRE(X && W && bias && Y && frames, "dx_voc_post: null pointer");
+  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && ncols >= N && ldy >= ncols && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
+             "dx_voc_post: bad shape (ncols >= N, ldy >= ncols, sxb %% 4 == 0, a 16-byte aligned X)");
+  hipLaunchKernelGGL(voc_post_kernel, dim3(dx_cdiv(ncols, THREADS), B), dim3(THREADS), 0, (hipStream_t)stream,
+                     X, sxb, W, bias, Y, ldy, frames, scale, N, ncols);
+  DX_LAUNCH_CHECK("dx_voc_post");
+  return DX_OK;
+}
+
+}  // extern "C"

@@ -176,6 +176,20 @@ def price(name, a, geom: Geometry):
         return 'relu_bwd', 'hbm', None, 3 * a['n'] * 4
     if name == 'dx_colsum':
         return 'colsum', 'hbm', None, a['rows'] * a['C'] * (2 if a['x_bf16'] else 4)
+    if name in ('dx_voc_conv', 'dx_voc_pair', 'dx_voc_post'):   # HiFi-GAN vocoder: N rows of samples, frames * scale of them valid
+        s = max(1, a['in_scale'] if name == 'dx_voc_conv' else a['scale'])
+        rows = geom.rows(a['B'], a['N'] // s) * s
+        op = 'bf16' if g('bf16') else 'f32'
+        if name == 'dx_voc_conv':                        # conv (up = 1) or polyphase transposed conv: rows in, rows * up out
+            out_rows = rows * a['up']
+            byt = rows * a['Cin'] * 4 + out_rows * a['Cout'] * 4 * (1 + has('R') + (a['acc_mode'] > 0))
+            kind = 'voc_ups' if a['up'] > 1 else 'voc_pre' if a['Cin'] == 80 else 'voc_conv'
+            return f'{kind}<{op}>', 'mfma', 2.0 * a['taps'] * a['Cin'] * a['Cout'] * out_rows, byt
+        if name == 'dx_voc_pair':                        # two convs, X read, Y written (+ read when accumulating)
+            return f'voc_pair<{op}>', 'mfma', 2.0 * 2 * a['taps'] * a['C'] * a['C'] * rows, rows * a['C'] * 4 * (2 + (a['acc_mode'] > 0))
+        return 'voc_post', 'hbm', None, rows * 32 * 4 + a['B'] * a['ncols'] * 4
+    if name == 'dx_voc_pack':
+        return 'voc_pack', 'hbm', None, a['Cout'] * a['Cin'] * a['taps'] * max(1, a['up']) * (4 + (2 if a['bf16'] else 4))
     return name[3:], 'hbm', None, None
 
 

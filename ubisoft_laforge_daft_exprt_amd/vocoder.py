@@ -1,0 +1,293 @@
+"""HiFi-GAN V1 vocoder on gfx950: mel spectrogram -> waveform (reference src/daft_exprt/vocoder/hifigan.py).
+
+``HiFiGANGenerator`` owns the reference generator's weight-normed state-dict layout (234 tensors); ``HiFiGanVocoder`` /
+``load_hifigan_vocoder`` are drop-ins for the reference helpers (``.infer``: one utterance, numpy in or out) and add
+``.infer_batch``: a padded (B, 80, T_max) mel batch on the device -- what ``DaftExprt.inference`` and ``GraphedSynthesizer`` return --
+to (B, 256 T_max) audio on the device, row b bitwise equal to ``mel[b, :, :lengths[b]]`` vocoded alone.
+
+Weight norm is folded once, at load time (``torch._weight_norm`` over dim 0, what ``remove_weight_norm`` computes: per OUTPUT channel
+for the Conv1d layers, per INPUT channel for the ConvTranspose1d ones, whose weight is (Cin, Cout, k)).  Every convolution runs in
+csrc/dx_vocoder.hip; there is no PyTorch fallback.  Checkpoints are read from a local path only: nothing here downloads.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+from torch import nn
+
+from ._lib import lib
+
+NEG_SLOPE = 0.1     # leaky-ReLU slope before every convolution (applied inside the kernels)
+HOP = 256           # waveform samples per mel frame: the product of the four upsampling factors
+
+# HiFi-GAN V1, the one configuration the kernels are built for: 80 mel bins into 512 channels; four (factor, transposed-conv width)
+# stages that halve the channels; three ResBlock1 per stage with kernel widths 3, 7, 11, each at dilations 1, 3, 5; 22.05 kHz.
+N_MELS, WIDTH = 80, 512
+STAGES = ((8, 16), (8, 16), (2, 4), (2, 4))
+RESBLOCK_WIDTHS = (3, 7, 11)
+RESBLOCK_DILATIONS = (1, 3, 5)
+
+
+def v1_config() -> dict:
+    """The V1 configuration in the key names of the reference's generator config dicts."""
+    return dict(sampling_rate=22050, model_in_dim=N_MELS, upsample_initial_channel=WIDTH, resblock='1',
+                upsample_rates=[f for f, _ in STAGES], upsample_kernel_sizes=[k for _, k in STAGES],
+                resblock_kernel_sizes=list(RESBLOCK_WIDTHS), resblock_dilation_sizes=[list(RESBLOCK_DILATIONS) for _ in RESBLOCK_WIDTHS])
+
+
+DEFAULT_CONFIG = v1_config()
+PRECISIONS = {'f32': 0, 'bf16': 1}
+WORKSPACE_BYTES_PER_FRAME = 5 * 8192 * 4    # five fp32 activation buffers of at most 8192 values per mel frame (C x samples per frame)
+DEFAULT_WORKSPACE_BYTES = 4 << 30            # infer_batch's default bound: larger batches run in chunks of utterances
+
+
+def check_config(config) -> dict:
+    """None -> V1; any other configuration than V1 (lists or tuples alike) raises NotImplementedError: there is no fallback."""
+    if config is None:
+        return v1_config()
+
+    def canon(v):
+        return tuple(canon(x) for x in v) if isinstance(v, (list, tuple)) else str(v)
+    want = {k: canon(v) for k, v in v1_config().items()}
+    got = {k: canon(v) for k, v in dict(config).items()}
+    if got != want:
+        raise NotImplementedError(f'the gfx950 HiFi-GAN kernels implement V1 only ({v1_config()}); got {dict(config)}')
+    return dict(config)
+
+
+class _WNConv(nn.Module):
+    """Parameters of one weight-normed (transposed) convolution, named as torch.nn.utils.weight_norm names them."""
+
+    def __init__(self, w_shape, n_bias):
+        super().__init__()
+        self.bias = nn.Parameter(torch.zeros(n_bias))
+        self.weight_g = nn.Parameter(torch.ones(w_shape[0], 1, 1))
+        self.weight_v = nn.Parameter(torch.zeros(*w_shape))
+
+
+class _ResBlock1(nn.Module):
+    def __init__(self, channels, k):
+        super().__init__()
+        self.convs1 = nn.ModuleList([_WNConv((channels, channels, k), channels) for _ in range(3)])
+        self.convs2 = nn.ModuleList([_WNConv((channels, channels, k), channels) for _ in range(3)])
+
+
+class HiFiGANGenerator(nn.Module):
+    """The reference generator's parameters (weight-normed keys and shapes).  It holds weights only: the forward is
+    ``HiFiGanVocoder``, which runs the folded weights through the HIP kernels."""
+
+    def __init__(self, config=None):
+        super().__init__()
+        self.config = check_config(config)
+        c0 = self.config['upsample_initial_channel']
+        self.conv_pre = _WNConv((c0, self.config['model_in_dim'], 7), c0)
+        self.ups = nn.ModuleList([_WNConv((c0 >> i, c0 >> (i + 1), k), c0 >> (i + 1))
+                                  for i, k in enumerate(self.config['upsample_kernel_sizes'])])
+        self.resblocks = nn.ModuleList([_ResBlock1(c0 >> (i + 1), k) for i in range(4) for k in self.config['resblock_kernel_sizes']])
+        self.conv_post = _WNConv((1, c0 >> 4, 7), 1)
+
+    def layer_names(self):
+        return [n[:-len('.bias')] for n, _ in self.named_parameters() if n.endswith('.bias')]
+
+    def folded(self) -> dict:
+        """-> {layer: (weight, bias)} with weight norm folded (CPU fp32)."""
+        return fold_state_dict({k: v.detach().cpu() for k, v in self.state_dict().items()}, self.layer_names())
+
+
+def fold_state_dict(state: dict, layers) -> dict:
+    """Generator state dict, weight-normed (``weight_g`` / ``weight_v``) or already folded (``weight``) -> {layer: (weight, bias)}."""
+    out = {}
+    for name in layers:
+        if name + '.weight' in state:
+            w = state[name + '.weight'].float()
+        elif name + '.weight_v' in state and name + '.weight_g' in state:
+            w = torch._weight_norm(state[name + '.weight_v'].float(), state[name + '.weight_g'].float(), 0)
+        else:
+            raise KeyError(f'generator checkpoint has no weight for {name!r}')
+        if name + '.bias' not in state:
+            raise KeyError(f'generator checkpoint has no bias for {name!r}')
+        out[name] = (w.detach().cpu().contiguous(), state[name + '.bias'].float().detach().cpu().contiguous())
+    return out
+
+
+def _checkpoint_state(checkpoint) -> dict:
+    """The generator state dict from any form the reference's _load_generator accepts: {'generator': sd}, {'state_dict': sd}, sd."""
+    if isinstance(checkpoint, (str, os.PathLike)):
+        checkpoint = torch.load(checkpoint, map_location='cpu')
+    if not isinstance(checkpoint, dict):
+        raise TypeError(f'a generator checkpoint is a dict or a state dict, got {type(checkpoint).__name__}')
+    for wrapper in ('generator', 'state_dict'):         # a training checkpoint nests the generator's weights under one of these
+        if wrapper in checkpoint:
+            return checkpoint[wrapper]
+    return checkpoint
+
+
+class HiFiGanVocoder:
+    """Drop-in for the reference ``HiFiGanVocoder`` on gfx950.  ``checkpoint_path``: a local generator checkpoint (or its loaded dict)."""
+
+    def __init__(self, checkpoint_path=None, config=None, device='cuda', precision='f32'):
+        if checkpoint_path is None:
+            raise ValueError('HiFiGanVocoder: checkpoint_path is required (a local HiFi-GAN generator checkpoint); '
+                             'this package never downloads one')
+        if precision not in PRECISIONS:
+            raise ValueError(f'HiFiGanVocoder: precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
+        generator = HiFiGANGenerator(config)
+        self.config = generator.config
+        self.checkpoint_path = checkpoint_path
+        self.precision = precision
+        self.device = torch.device(device)
+        state = _checkpoint_state(checkpoint_path)
+        layers = generator.layer_names()
+        self.weights = fold_state_dict(state, layers)          # {layer: (folded weight, bias)}, CPU fp32: what the kernels run
+        # ``generator``: the checkpoint's weight-normed parameters (CPU, frozen; no forward -- ``infer`` / ``infer_batch`` are the
+        # forward).  None for a checkpoint that is already folded: there are no weight_g / weight_v to hold.
+        self.generator = None
+        if all(n + '.weight_v' in state for n in layers):
+            generator.load_state_dict(state, strict=True)
+            self.generator = generator.eval().requires_grad_(False)
+        self._packs = None
+
+    # -- device-side weights -------------------------------------------------------------------------------------------------
+    def _pack(self, w, up=1):
+        """folded weight -> dx_voc_pack operand (uint8 device buffer)."""
+        bf16 = PRECISIONS[self.precision]
+        if up > 1:
+            cin, cout, _ = w.shape
+            taps = 2
+        else:
+            cout, cin, taps = w.shape
+        nbytes = torch.zeros(1, dtype=torch.long)
+        lib().dx_voc_pack_size(cout, cin, taps, up, bf16, nbytes.data_ptr())
+        buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=self.device)
+        wd = w.to(self.device).contiguous()
+        lib().dx_voc_pack(wd.data_ptr(), buf.data_ptr(), cout, cin, taps, up, bf16, _stream(self.device))
+        return buf
+
+    def _device_weights(self):
+        if self._packs is None:
+            if self.device.type != 'cuda':
+                raise RuntimeError('HiFiGanVocoder runs on the GPU (gfx950 HIP kernels); there is no CPU path')
+            dev = lambda t: t.to(self.device).contiguous()
+            P = {}
+            w, b = self.weights['conv_pre']
+            P['conv_pre'] = (self._pack(w), dev(b))
+            for i, u in enumerate(self.config['upsample_rates']):
+                w, b = self.weights[f'ups.{i}']
+                P[f'ups.{i}'] = (self._pack(w, up=u), dev(b))
+            for name, (w, b) in self.weights.items():
+                if name.startswith('resblocks.'):
+                    P[name] = (self._pack(w), dev(b))
+            w, b = self.weights['conv_post']
+            P['conv_post'] = (dev(w), dev(b))
+            self._packs = P
+        return self._packs
+
+    # -- reference contract ----------------------------------------------------------------------------------------------------
+    def infer(self, mel_spec):
+        """(80, T) or (1, 80, T) mel (numpy, tensor or nested list) -> numpy waveform clipped to [-1, 1], as the reference's infer."""
+        mel = mel_spec.detach().float() if torch.is_tensor(mel_spec) else torch.as_tensor(np.asarray(mel_spec, dtype=np.float32))
+        if mel.dim() == 3:
+            if mel.shape[0] != 1:
+                raise ValueError(f'infer vocodes one utterance, got a batch of {mel.shape[0]} mels: use infer_batch')
+            mel = mel[0]
+        if mel.dim() != 2:
+            raise ValueError(f'infer takes a ({N_MELS}, T) or (1, {N_MELS}, T) mel, got shape {tuple(mel.shape)}')
+        mel = mel[None]
+        mel = mel.to(self.device).contiguous()
+        with torch.no_grad():
+            audio, _ = self.infer_batch(mel, [mel.shape[-1]])
+            audio = audio.squeeze().cpu().numpy()
+        return np.clip(audio, -1.0, 1.0)
+
+    # -- batched form ----------------------------------------------------------------------------------------------------------
+    def infer_batch(self, mels, lengths, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+        """mels (B, 80, T_max) fp32 on the device; lengths: B frame counts (host ints, or a device tensor such as GraphedSynthesizer's
+        out_lens: one small device-to-host copy sizes the work).  -> (audio (B, 256 T_max) fp32 on the device, sample_lengths).
+        Row b is bitwise ``mel[b, :, :lengths[b]]`` vocoded alone; samples at or past 256 lengths[b] are 0.  max_workspace_bytes
+        bounds the activation workspace: the batch then runs in chunks of consecutive utterances (bitwise the same result).  A chunk
+        of b utterances whose longest has n frames takes b * n * WORKSPACE_BYTES_PER_FRAME (160 KB per frame, sized by the LONGEST row:
+        2.2 GB for 16 rows of 850 frames); one utterance longer than the bound still runs, alone.  None: no bound, one chunk."""
+        if mels.dim() != 3 or mels.shape[1] != self.config['model_in_dim']:
+            raise ValueError(f'infer_batch: mels must be (B, {self.config["model_in_dim"]}, T_max), got {tuple(mels.shape)}')
+        if mels.device != self.device and not (self.device.index is None and mels.device.type == self.device.type):
+            raise ValueError(f'infer_batch: mels are on {mels.device}, the vocoder on {self.device}')
+        mels = mels.float().contiguous()
+        B, n_mel, T = mels.shape
+        dev = mels.device
+        if torch.is_tensor(lengths):
+            host = lengths.tolist()                                       # the one device-to-host copy (sizing only)
+            frames = lengths.to(device=dev, dtype=torch.int32).clamp(0, T).contiguous()
+            sample_lengths = frames.to(torch.long) * HOP
+        else:
+            host = [int(v) for v in lengths]
+            frames = torch.tensor(host, dtype=torch.int32).clamp(0, T).to(dev)
+            sample_lengths = [min(max(v, 0), T) * HOP for v in host]
+        if len(host) != B:
+            raise ValueError(f'infer_batch: {len(host)} lengths for a batch of {B}')
+        host = [min(max(int(v), 0), T) for v in host]
+        P = self._device_weights()
+        audio = torch.empty(B, T * HOP, dtype=torch.float32, device=dev)
+        b0 = 0
+        while b0 < B:
+            b1, n = b0 + 1, max(1, host[b0])
+            while b1 < B:
+                n2 = max(n, host[b1])
+                if max_workspace_bytes is not None and (b1 + 1 - b0) * n2 * WORKSPACE_BYTES_PER_FRAME > max_workspace_bytes:
+                    break
+                b1, n = b1 + 1, n2
+            self._run(P, mels, frames, audio, b0, b1, n)
+            b0 = b1
+        return audio, sample_lengths
+
+    def _run(self, P, mels, frames, audio, b0, b1, N):
+        """Utterances b0 .. b1-1 with N frames of work each (N >= their lengths): 60 launches."""
+        L, st = lib(), _stream(mels.device)
+        bf16 = PRECISIONS[self.precision]
+        B, T = b1 - b0, mels.shape[2]
+        n_mel = mels.shape[1]
+        ws = torch.empty(5, B * N * 8192, dtype=torch.float32, device=mels.device)
+        S, U, Pb, Q, M = (ws[i].data_ptr() for i in range(5))
+        fr = frames.data_ptr() + 4 * b0
+        c = self.config['upsample_initial_channel']
+        w, b = P['conv_pre']
+        L.dx_voc_conv(mels.data_ptr() + 4 * b0 * n_mel * T, n_mel * T, 1, T, w.data_ptr(), b.data_ptr(), S, N * c, None,
+                      fr, 1, B, N, n_mel, c, 7, 1, 1, 0, 0, bf16, st)
+        rows, scale = N, 1
+        ks, ds = self.config['resblock_kernel_sizes'], self.config['resblock_dilation_sizes']
+        for i, u in enumerate(self.config['upsample_rates']):
+            w, b = P[f'ups.{i}']
+            L.dx_voc_conv(S, rows * c, c, 1, w.data_ptr(), b.data_ptr(), U, rows * u * (c // 2), None,
+                          fr, scale, B, rows, c, c // 2, 2, 1, u, 1, 0, bf16, st)
+            rows, scale, c = rows * u, scale * u, c // 2
+            for j, k in enumerate(ks):
+                src = U
+                for p, d in enumerate(ds[j]):
+                    dst = (Pb, Q, S)[p]
+                    acc = min(j, 2) if p == 2 else 0              # the stage sum: first ResBlock writes, second adds, third adds and / 3
+                    name = f'resblocks.{i * len(ks) + j}'
+                    (w1, b1), (w2, b2) = P[f'{name}.convs1.{p}'], P[f'{name}.convs2.{p}']
+                    if c <= 64:
+                        L.dx_voc_pair(src, rows * c, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), dst,
+                                      fr, scale, B, rows, c, k, d, acc, bf16, st)
+                    else:
+                        L.dx_voc_conv(src, rows * c, c, 1, w1.data_ptr(), b1.data_ptr(), M, rows * c, None,
+                                      fr, scale, B, rows, c, c, k, d, 1, 1, 0, bf16, st)
+                        L.dx_voc_conv(M, rows * c, c, 1, w2.data_ptr(), b2.data_ptr(), dst, rows * c, src,
+                                      fr, scale, B, rows, c, c, k, 1, 1, 1, acc, bf16, st)
+                    src = dst
+        w, b = P['conv_post']
+        L.dx_voc_post(S, rows * c, w.data_ptr(), b.data_ptr(), audio.data_ptr() + 4 * b0 * T * HOP, T * HOP,
+                      fr, scale, B, rows, T * HOP, st)
+
+
+def load_hifigan_vocoder(checkpoint_path=None, device=None, precision='f32'):
+    """Drop-in for the reference's load_hifigan_vocoder (scripts/synthesize.py:380-382); ``checkpoint_path`` is required."""
+    if device is None:
+        device = 'cuda'
+    return HiFiGanVocoder(checkpoint_path=checkpoint_path, config=DEFAULT_CONFIG, device=device, precision=precision)
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
