@@ -332,6 +332,21 @@ int dx_voc_pair(const float* X, long sxb, const void* W1, const float* b1, const
 int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
                 int B, int N, int ncols, void* stream);
 
+/* ---- mel front end (reference extract_features.py mel_spectrogram_HiFi, vocoder/dataset.py mel_spectrogram, center = False;
+ * csrc/dx_mel.hip) ------------------------------------------------------------------------------------------------------------
+ * n_fft = win = 1024, hop = 256, reflect padding of 384 samples per side with each row's own first / last samples.  kmax: the bins
+ * [0, kmax) where the filter bank has a non-zero column (rounded up to 64 inside), n_mels % 16 == 0 and <= 128. */
+/* bytes of the DFT basis and of the filter-bank operand dx_mel_pack writes */
+int dx_mel_basis_size(int n_mels, int kmax, long* basis_bytes, long* fb_bytes);
+/* fb (n_mels, n_freq) fp32 filter bank -> the two MFMA operands of dx_mel: the periodic-Hann-windowed cos / sin basis (computed in
+ * double, rounded once to f32) and the packed filter bank (zero past n_freq). */
+int dx_mel_pack(const float* fb, int n_mels, int n_freq, int kmax, void* basis, void* fbp, void* stream);
+/* wav [B][sxb] fp32 (S samples allocated per row), lengths device int32 [B] (samples past min(lengths[b], S) are never read) ->
+ * mel [B][n_mels][T_max] (batch stride smb) = log(max(fb . sqrt(|STFT|^2 + 1e-9), clip)) and energy [B][T_max] = L2 norm of the
+ * clamped mel over channels.  Row b has lengths[b] / 256 frames (none if lengths[b] <= 384); everything past them is written as 0. */
+int dx_mel(const float* wav, long sxb, int S, const int* lengths, const void* basis, const void* fb, float* mel, long smb,
+           float* energy, int B, int T_max, int n_mels, int kmax, float clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

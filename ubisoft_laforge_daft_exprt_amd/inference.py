@@ -188,3 +188,35 @@ class GraphedSynthesizer:
     def accent_embedding(self, frames_energy, frames_pitch, mel_specs, lengths, use_graph=True):
         """The averaged accent embedding (1, 128) of scripts/synthesize.py:446-448."""
         return self.accent_embeddings(frames_energy, frames_pitch, mel_specs, lengths, use_graph).mean(dim=0, keepdim=True)
+
+    # -- accent embedding from reference audio -------------------------------------------------------------------------------
+    def trimmed_audio_features(self, wavs, wav_lengths, frames_pitch, pitch_lengths):
+        """scripts/synthesize.py:424-429 on the device: (R, S) waveforms -> mel and frame energy (``mel.MelSpectrogram`` with this
+        synthesizer's hparams), each row trimmed with its pitch to min(pitch_lengths[r], mel frames) and zero after that.
+        -> (energy (R, T), pitch (R, T), mels (R, n_mel, T), lengths (R,) int64), T = the longest trimmed row."""
+        from .mel import MelSpectrogram
+        if getattr(self, '_mel', None) is None or self._mel.device != wavs.device:
+            self._mel = MelSpectrogram(self.hparams, device=wavs.device)
+        mels, energy, frames = self._mel(wavs, wav_lengths)
+        dev = mels.device
+        pl = torch.as_tensor(pitch_lengths).to(device=dev, dtype=torch.long)
+        lengths = torch.minimum(pl, frames)
+        T = max(1, int(lengths.max()))
+        if frames_pitch.shape[1] < T:
+            raise ValueError(f'frames_pitch has {frames_pitch.shape[1]} frames, pitch_lengths asks for {T}')
+        keep = torch.arange(T, device=dev)[None, :] < lengths[:, None]
+        energy = energy[:, :T].masked_fill(~keep, 0.0).contiguous()
+        pitch = frames_pitch[:, :T].to(dev).float().masked_fill(~keep, 0.0).contiguous()
+        mels = mels[:, :, :T].masked_fill(~keep[:, None, :], 0.0).contiguous()
+        return energy, pitch, mels, lengths
+
+    def accent_embeddings_from_audio(self, wavs, wav_lengths, frames_pitch, pitch_lengths, use_graph=True):
+        """(R, S) reference recordings on the device with their sample lengths, and their frame pitch (R, T_p) with pitch_lengths ->
+        (R, 128) accent embeddings: mel and energy computed on the device, trimmed as scripts/synthesize.py:428-429 does, then
+        ``accent_embeddings``.  Pitch stays an input (the reference tracks it with REAPER)."""
+        energy, pitch, mels, lengths = self.trimmed_audio_features(wavs, wav_lengths, frames_pitch, pitch_lengths)
+        return self.accent_embeddings(energy, pitch, mels, lengths, use_graph)
+
+    def accent_embedding_from_audio(self, wavs, wav_lengths, frames_pitch, pitch_lengths, use_graph=True):
+        """The averaged accent embedding (1, 128) of scripts/synthesize.py:444-447, from audio."""
+        return self.accent_embeddings_from_audio(wavs, wav_lengths, frames_pitch, pitch_lengths, use_graph).mean(dim=0, keepdim=True)

@@ -190,6 +190,12 @@ def price(name, a, geom: Geometry):
         return 'voc_post', 'hbm', None, rows * 32 * 4 + a['B'] * a['ncols'] * 4
     if name == 'dx_voc_pack':
         return 'voc_pack', 'hbm', None, a['Cout'] * a['Cin'] * a['taps'] * max(1, a['up']) * (4 + (2 if a['bf16'] else 4))
+    if name == 'dx_mel':                                 # valid frames only: DFT GEMM (2 kmax outputs of 1024) + mel GEMM per frame
+        frames = geom.rows(a['B'], a['T_max'])
+        flops = 2.0 * frames * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])
+        return 'mel<f32>', 'mfma', flops, frames * (256 * 4 + (a['n_mels'] + 1) * 4)
+    if name == 'dx_mel_pack':
+        return 'mel_pack', 'hbm', None, a['n_mels'] * a['n_freq'] * 4 + (2 * 1024 + a['n_mels']) * a['kmax'] * 4
     return name[3:], 'hbm', None, None
 
 
