@@ -1,5 +1,5 @@
 """Bucketed training (trainer.Trainer(bucket=...), trainer.pad_batch): a micro-batch padded past its longest utterances, with the true maxima
-in ``_dx_rows_exist``, computes what the exact-shape step computes -- forward, the seven loss terms and every parameter gradient -- and one
+in ``Lengths.exist``, computes what the exact-shape step computes -- forward, the seven loss terms and every parameter gradient -- and one
 captured graph serves every batch of a length bucket."""
 import pytest
 import torch
@@ -120,6 +120,53 @@ def test_bucketed_graphs_match_exact_eager_steps(cuts):
     assert len(tg.graphs) == 2 and g.hits == 6
     with pytest.raises(ValueError):
         tg.resident_batch(other)
+
+
+@pytest.mark.parametrize('use_graphs', [False, True])
+def test_bucketed_step_survives_cloned_length_tensors(use_graphs):
+    """The rows that exist travel inside the trainer as ``Lengths.exist``, not as attributes of the caller's tensors: a device-resident batch
+    whose length tensors were cloned (which drops anything stuck onto them, the host-lengths hint included) gives, in bucketed mode, the
+    loss of the exact-shape eager step at the first-step bar of test_bucketed_graphs_match_exact_eager_steps."""
+    hp = helpers.golden_hparams(initial_learning_rate=2e-4, max_learning_rate=2e-3, warmup_steps=10, grad_clip_thresh=5.0)
+    batch = _bucket_batches(1)[0]
+    dev_batch = [t.to(DEV) if torch.is_tensor(t) else t for t in batch]
+    for i in (5, 9):
+        dev_batch[i]._dx_host_lengths = batch[i].tolist()
+        dev_batch[i] = dev_batch[i].clone()
+        assert not hasattr(dev_batch[i], '_dx_host_lengths')
+    _, le, _ = _train(hp, None, False, 0, [batch])
+    tb, lb, _ = _train(hp, (16, 64), use_graphs, 0, [tuple(dev_batch)])
+    print('exact eager', le, 'bucketed, cloned lengths', lb)
+    assert len(tb.graphs) == int(use_graphs)
+    assert abs(le[0] - lb[0]) <= 1e-6 * abs(le[0]), (le, lb)
+
+
+def test_forward_and_loss_with_host_lengths_hint_do_not_sync():
+    """Length tensors that carry the ``_dx_host_lengths`` hint (as bench.py's resident batch does): forward + loss issue no device -> host
+    synchronisation (``torch.cuda.set_sync_debug_mode('error')`` raises on one), after one warm-up call that builds packs and tables."""
+    from ubisoft_laforge_daft_exprt_amd.synth import synthetic_batch
+    import ubisoft_laforge_daft_exprt_amd as pkg
+    hp = pkg.HyperParams(n_speakers=3)                        # dropout on, as in the timed step
+    model, crit = _model('bf16', hp)
+    batch = synthetic_batch(4, (12, 24), seed=311, n_speakers=3)
+    dev_batch = tuple(t.to(DEV) if torch.is_tensor(t) else t for t in batch)
+    for i in (5, 9):
+        dev_batch[i]._dx_host_lengths = batch[i].tolist()
+    inputs, targets = model.parse_batch(DEV, dev_batch)
+    assert inputs[5] is dev_batch[5] and inputs[9] is dev_batch[9]
+
+    def run():
+        total, terms = crit(model(inputs), tuple(targets) + (inputs[6], inputs[7]), 1000)
+        return total, terms
+    run()
+    torch.cuda.synchronize()
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode('error')
+    try:
+        total, terms = run()
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
+    assert torch.isfinite(total).item() and all(v == v for v in terms.values())
 
 
 def test_bucketed_graph_dropout_draws_new_masks():

@@ -46,22 +46,43 @@ def _sink(param, enabled):
 
 
 class Lengths:
-    """Valid lengths of one axis of a padded batch: int32 on the device for the kernels, Python ints for shapes."""
+    """Valid lengths of one axis of a padded batch and the ONE carrier of what is known about that axis, fixed at construction: ``i64`` (the
+    caller's device tensor), ``i32`` (for the kernels; one cast launch unless given), ``host`` (Python ints for shapes; one device -> host
+    sync unless given) and ``exist``: optional device int32 [B], rows n >= exist[b] of utterance b do not exist for the k = 3 convolutions
+    (they read zero) although the tensors have more rows; None = the reference's padded grid (every utterance has max(lengths) rows).
+    Given by inference.GraphedSynthesizer (shape buckets: the batch's true longest length; batched accent encoder: exist = lengths, every
+    recording as if run alone, scripts/synthesize.py:420-448) and trainer.pad_batch (bucketed training; the backward launches take it too).
+    Model and loss take a ``Lengths`` wherever they take a length tensor and hand back the object they were given.  A caller who stays with
+    tensors spares the sync with the input-only hint ``tensor._dx_host_lengths = [ints]``, read by ``Lengths.of`` alone (a ``.clone()`` or
+    ``.to()`` of the tensor drops it: the sync comes back, nothing else changes)."""
 
-    def __init__(self, lengths: torch.Tensor, host=None):
+    def __init__(self, lengths: torch.Tensor, host=None, i32=None, exist=None):
         if not lengths.is_cuda:
             raise RuntimeError('lengths must live on the GPU (the kernels read them as device memory); got a CPU tensor')
-        self.host = [int(v) for v in (lengths.tolist() if host is None else host)]  # one D2H sync unless given
+        self.host = [int(v) for v in (lengths.tolist() if host is None else host)]
         self.max = max(self.host)
-        self.total = sum(self.host)
-        self.i32 = lengths.to(dtype=torch.int32).contiguous()
+        self.i32 = lengths.to(dtype=torch.int32).contiguous() if i32 is None else i32
         self.i64 = lengths
-        # optional device int32 [B]: rows n >= exist[b] of utterance b do not exist for the k = 3 convolutions (they read zero), although
-        # the tensors have more rows.  None = the reference's padded grid (every utterance has max(lengths) rows).  Set by
-        # inference.GraphedSynthesizer: padded-shape buckets (exist = the batch's true longest length) and the batched accent encoder
-        # (exist = lengths: every reference behaves as if it were run alone, scripts/synthesize.py:420-448), and by trainer.Trainer in
-        # bucketed mode (exist = the batch's true longest length; the backward Functions pass it to every k = 3 launch as well).
-        self.exist = None
+        self.exist = exist
+
+    @classmethod
+    def of(cls, x, exist=None):
+        """``x`` itself when it is a ``Lengths``; a length tensor wrapped, with its host-lengths hint if it carries one."""
+        return x if isinstance(x, Lengths) else cls(x, host=getattr(x, '_dx_host_lengths', None), exist=exist)
+
+    def clone(self):
+        return Lengths(self.i64.clone(), self.host, self.i32.clone(), None if self.exist is None else self.exist.clone())
+
+    def copy_(self, other, non_blocking=True):
+        """``other`` into this object's buffers (the static inputs of a captured graph).  What the host knew when the launches were recorded
+        must still hold: batch size and longest length (host lengths only size tensors), and ``exist`` on both sides or on neither."""
+        if (len(self.host), self.max, self.exist is None) != (len(other.host), other.max, other.exist is None):
+            raise ValueError(f'Lengths.copy_: host {other.host} / exist {other.exist is not None} into host {self.host} / exist {self.exist is not None}')
+        self.host = other.host
+        for dst, src in ((self.i64, other.i64), (self.i32, other.i32), (self.exist, other.exist)):
+            if dst is not None and dst.data_ptr() != src.data_ptr():      # (a resident batch already lives in these buffers)
+                dst.copy_(src, non_blocking=non_blocking)
+        return self
 
 
 # ----------------------------------------------------------------------------------------------------------------------

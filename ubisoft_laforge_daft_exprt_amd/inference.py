@@ -66,12 +66,10 @@ class GraphedSynthesizer:
         m = self.model
         spk = m.spk_projection(ops.l2_normalize(st['spk_embs']), need_dx=False)
         film = m.style_adapter(st['accent_emb'] + spk)
-        in_lens = Lengths(st['in_lens'], host=st['in_host'])
-        in_lens.i32, in_lens.exist = st['in_lens_i32'], st.get('in_exist')
+        in_lens = Lengths(st['in_lens'], host=st['in_host'], i32=st['in_lens_i32'], exist=st.get('in_exist'))
         enc = m.phoneme_encoder(st['symbols'], film['phoneme_encoder'], in_lens)
         x, weights = m.gaussian_upsampling(enc, st['dur'], st['dur_int'], st['energy'], st['pitch'], in_lens, n_frames=st['n_frames'])
-        out_lens = Lengths(st['out_lens'], host=st['out_host'])
-        out_lens.i32, out_lens.exist = st['out_lens_i32'], st.get('out_exist')
+        out_lens = Lengths(st['out_lens'], host=st['out_host'], i32=st['out_lens_i32'], exist=st.get('out_exist'))
         mel = m.frame_decoder(x, film['frame_decoder'], out_lens)
         return mel, weights
 
@@ -146,10 +144,8 @@ class GraphedSynthesizer:
         i32 = lengths.to(torch.int32)
 
         def run(e, p, mel, lens_t, lens_i32, host_lens):
-            lens = Lengths(lens_t, host=host_lens)
-            lens.i32 = lens_i32
-            lens.exist = lens_i32                       # rows beyond a recording's own length do not exist: it behaves as if alone
-            return m.accent_encoder(e, p, mel, lens)
+            # exist = lengths: rows beyond a recording's own length do not exist, so it behaves as if alone
+            return m.accent_encoder(e, p, mel, Lengths(lens_t, host=host_lens, i32=lens_i32, exist=lens_i32))
 
         with torch.no_grad():
             if not use_graph:

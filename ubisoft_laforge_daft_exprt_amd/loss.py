@@ -193,10 +193,7 @@ class DaftExprtLoss(nn.Module):
         mel_preds, output_lengths = decoder_preds
         if not mel_preds.is_cuda:
             raise RuntimeError('DaftExprtLoss (MI355X build) runs on the GPU only; there is no CPU path')
-        lens = output_lengths if isinstance(output_lengths, Lengths) else getattr(output_lengths, '_dx_lengths', None)
-        if lens is None or lens.i64 is not output_lengths:     # (the model leaves its Lengths object on the tensor it returns)
-            lens = Lengths(output_lengths, host=getattr(output_lengths, '_dx_host_lengths', None))
-            lens.exist = getattr(output_lengths, '_dx_rows_exist', None)
+        lens = Lengths.of(output_lengths)          # a caller who gave the model a Lengths gets it back in decoder_preds[1]: nothing is built here
         pm = post_multipliers if (self.post_mult_weight != 0.0 and torch.is_tensor(post_multipliers)) else None
         # ``iteration``: the step number, or -- from a trainer that replays captured graphs -- the adversarial weight itself as a
         # device scalar it updates before every replay

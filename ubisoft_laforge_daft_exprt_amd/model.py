@@ -24,7 +24,21 @@ def _xavier_(t, gain_name='linear'):
     return t
 
 
-class _Affine(nn.Module):
+class _RuntimeModule(nn.Module):
+    """A module that launches kernels or packs weights: on the ``ops.Runtime`` its model bound to it, on the package default when alone."""
+    _runtime = None
+
+    @property
+    def runtime(self):
+        return self._runtime or ops.DEFAULT
+
+    def bind_runtime(self, rt):
+        for m in self.modules():
+            if isinstance(m, _RuntimeModule):
+                m._runtime = rt
+
+
+class _Affine(_RuntimeModule):
     """weight/bias holder (Conv1d, Linear, LayerNorm parameters keep the reference's key names)."""
 
     def __init__(self, wshape, bias_len, gain_name=None, layer_norm=False):
@@ -43,7 +57,7 @@ class _Affine(nn.Module):
 
     @property
     def pack(self):
-        rt = getattr(self, '_dx_rt', None) or ops.DEFAULT
+        rt = self.runtime
         if self._pack is None or self._pack.weight is not self.weight or self._pack.rt is not rt:
             self._pack = ops.PackedWeight(self.weight, rt)
         return self._pack
@@ -69,7 +83,7 @@ class LinearNorm(nn.Module):
         return Fx.LinearFn.apply(x, p.weight, p.bias, p.pack, relu, grad_scale, None, need_dx)
 
 
-class _MHAParams(nn.Module):
+class _MHAParams(_RuntimeModule):
     """Parameter names of nn.MultiheadAttention (in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias)."""
 
     def __init__(self, dim):
@@ -82,7 +96,7 @@ class _MHAParams(nn.Module):
 
     @property
     def in_pack(self):
-        rt = getattr(self, '_dx_rt', None) or ops.DEFAULT
+        rt = self.runtime
         if self._pack is None or self._pack.weight is not self.in_proj_weight or self._pack.rt is not rt:
             self._pack = ops.PackedWeight(self.in_proj_weight, rt)
         return self._pack
@@ -163,7 +177,7 @@ def _stack_cfg(hparams, name):
     return cfg
 
 
-class AccentEncoder(nn.Module):
+class AccentEncoder(_RuntimeModule):
     """reference model.py:614-716 (live definition)"""
 
     def __init__(self, hparams):
@@ -183,14 +197,14 @@ class AccentEncoder(nn.Module):
         self.blocks = nn.ModuleList([FFTBlock(cfg) for _ in range(cfg['nb_blocks'])])
 
     def forward(self, frames_energy, frames_pitch, mel_specs, output_lengths):
-        lens = output_lengths if isinstance(output_lengths, Lengths) else Lengths(output_lengths)
+        lens = Lengths.of(output_lengths)
         c = self.convs
         packs = {'p0': c[0].conv.pack, 'p1': c[4].conv.pack, 'p2': c[8].conv.pack,
                  'params': {'c0_w': c[0].conv.weight, 'c0_b': c[0].conv.bias, 'l0_w': c[2].weight, 'l0_b': c[2].bias,
                             'c1_w': c[4].conv.weight, 'c1_b': c[4].conv.bias, 'l1_w': c[6].weight, 'l1_b': c[6].bias,
                             'c2_w': c[8].conv.weight, 'c2_b': c[8].conv.bias, 'l2_w': c[10].weight, 'l2_b': c[10].bias}}
         pe = positional_table(self.cfg['hidden_embed_dim'], mel_specs.device)
-        rt = getattr(self, '_dx_rt', None)
+        rt = self.runtime
         p_drop = self.cfg['conv_dropout']
         y0 = Fx.AccentFront0Fn.apply(mel_specs, lens, packs, p_drop, self.training, c[0].conv.weight, c[0].conv.bias, c[2].weight, c[2].bias)
         y0 = Fx.cut(rt, 3, y0)                     # phase D of a trainer's backward: prenet layer 0 (its 1 MB of gradients is all that is exchanged last)
@@ -201,10 +215,10 @@ class AccentEncoder(nn.Module):
                                      self.pitch_embedding.conv.weight, self.pitch_embedding.conv.bias)
         x = Fx.cut(rt, 2, x)                       # phase C: prenet layers 2, 1 + the prosody embeddings; phase B: the four FFT blocks
         x = _run_blocks(self.blocks, x, None, lens)
-        return Fx.MeanPoolFn.apply(x, lens, getattr(self, '_dx_rt', None))
+        return Fx.MeanPoolFn.apply(x, lens, rt)
 
 
-class SpeakerClassifier(nn.Module):
+class SpeakerClassifier(_RuntimeModule):
     """reference model.py:809-830: gradient reversal (-lambda on the way back) + 3 linears with ReLU"""
 
     def __init__(self, hparams):
@@ -219,7 +233,7 @@ class SpeakerClassifier(nn.Module):
         h = self.classifier[1](x, relu=True, grad_scale=-float(self.lambda_))   # GRL folded into the first input gradient
         h = self.classifier[3](h, relu=True)
         last = self.classifier[5].linear_layer
-        rt = getattr(self, '_dx_rt', None) or ops.DEFAULT
+        rt = self.runtime
         if self._padded is None or self._padded.weight is not last.weight or self._padded.rt is not rt:
             self._padded = Fx.PaddedLinear(last.weight, last.bias, rt)
         return Fx.PaddedLinearFn.apply(h, last.weight, last.bias, self._padded)
@@ -239,7 +253,7 @@ def _film_blocks(film_params):
     return Fx.SplitFilmFn.apply(film_params)
 
 
-class StyleAdapter(nn.Module):
+class StyleAdapter(_RuntimeModule):
     """reference model.py:719-806"""
 
     def __init__(self, hparams):
@@ -265,7 +279,7 @@ class StyleAdapter(nn.Module):
         # tensors are done ONCE for all blocks, one launch forward, one backward (functional.FilmAffineFn)
         nb_all = sum(nb for nb, _ in self.module_params.values())
         pm = self.post_multipliers if self.post_mult_weight != 0.0 else None
-        *blocks, whole = Fx.FilmAffineFn.apply(gammas, betas, pm, nb_all, getattr(self, '_dx_rt', None))
+        *blocks, whole = Fx.FilmAffineFn.apply(gammas, betas, pm, nb_all, self.runtime)
         out, blk = {}, 0
         for name, (nb, _) in self.module_params.items():
             # the (B, nb, 2C) tensor of the reference's return value: a strided view of the block-major buffer
@@ -274,7 +288,7 @@ class StyleAdapter(nn.Module):
         return out
 
 
-class PhonemeEncoder(nn.Module):
+class PhonemeEncoder(_RuntimeModule):
     """reference model.py:567-610"""
 
     def __init__(self, hparams):
@@ -286,14 +300,14 @@ class PhonemeEncoder(nn.Module):
         self.blocks = nn.ModuleList([FFTBlock(cfg) for _ in range(cfg['nb_blocks'])])
 
     def forward(self, x, film_params, input_lengths):
-        lens = input_lengths if isinstance(input_lengths, Lengths) else Lengths(input_lengths)
+        lens = Lengths.of(input_lengths)
         pe = positional_table(self.cfg['hidden_embed_dim'], x.device)
-        h = Fx.EmbedPosFn.apply(x, self.symbols_embedding.weight, pe, lens, getattr(self, '_dx_rt', None))
+        h = Fx.EmbedPosFn.apply(x, self.symbols_embedding.weight, pe, lens, self.runtime)
         film = _film_blocks(film_params)
         return _run_blocks(self.blocks, h, film, lens)
 
 
-class GaussianUpsamplingModule(nn.Module):
+class GaussianUpsamplingModule(_RuntimeModule):
     """reference model.py:385-510 (film_params=None, use_concatenation=False: the only live configuration)"""
 
     def __init__(self, hparams):
@@ -311,12 +325,12 @@ class GaussianUpsamplingModule(nn.Module):
     def forward(self, x, durations_float, durations_int, energies, pitch, input_lengths, film_params=None, n_frames=None):
         if film_params is not None:
             raise NotImplementedError('FiLM on the upsampling projections is never enabled by the reference forward (model.py:930-933)')
-        lens = input_lengths if isinstance(input_lengths, Lengths) else Lengths(input_lengths)
+        lens = Lengths.of(input_lengths)
         if n_frames is None:
             n_frames = int(durations_int.sum(dim=1).max())      # reference: torch.max(cumsum), model.py:497 (host sync)
         d, e, p, r = self.duration_projection.conv, self.energy_projection.conv, self.pitch_projection.conv, self.projection[0].linear_layer
         return Fx.GaussianUpsampleFn.apply(x, durations_float, durations_int, energies, pitch, lens, n_frames,
-                                           getattr(self, '_dx_rt', None), d.weight, d.bias, e.weight, e.bias, p.weight, p.bias, r.weight, r.bias)
+                                           self.runtime, d.weight, d.bias, e.weight, e.bias, p.weight, p.bias, r.weight, r.bias)
 
 
 class FrameDecoder(nn.Module):
@@ -332,7 +346,7 @@ class FrameDecoder(nn.Module):
         self.projection = LinearNorm(D, hparams.n_mel_channels)
 
     def forward(self, x, film_params, output_lengths):
-        lens = output_lengths if isinstance(output_lengths, Lengths) else Lengths(output_lengths)
+        lens = Lengths.of(output_lengths)
         pe = positional_table(self.cfg['hidden_embed_dim'], x.device)
         h = Fx.AddPosFn.apply(x, pe, lens)
         film = _film_blocks(film_params)
@@ -341,7 +355,7 @@ class FrameDecoder(nn.Module):
         return Fx.MelProjectionFn.apply(h, p.weight, p.bias, p.pack, lens)
 
 
-class DaftExprt(nn.Module):
+class DaftExprt(_RuntimeModule):
     """reference model.py:832-1114"""
 
     def __init__(self, hparams, is_training=True):
@@ -357,9 +371,7 @@ class DaftExprt(nn.Module):
         self.spk_projection = LinearNorm(getattr(hparams, 'external_emb_dim', 192), self.hidden_embed_dim)
         # execution state of THIS model (operand precision, pack epoch, gradient sink): shared by all of its sub-modules, read
         # by nobody else.  It starts from the package default (``set_precision``) and is switched with ``model.set_precision``.
-        self.runtime = ops.Runtime(ops.DEFAULT.precision)
-        for m in self.modules():
-            m._dx_rt = self.runtime
+        self.bind_runtime(ops.Runtime(ops.DEFAULT.precision))
 
     def set_precision(self, name: str):
         """'f32' (exact-f32 MFMA operands, parity mode), 'bf16' / 'fp16' (16-bit MFMA operands, fp32 accumulate; throughput modes) or
@@ -369,43 +381,26 @@ class DaftExprt(nn.Module):
 
     # -- batch plumbing ------------------------------------------------------------------------------------------------
     def parse_batch(self, device, batch):
-        """reference model.py:858-887.  Also remembers the (CPU) lengths so that forward needs no device->host sync."""
+        """reference model.py:858-887.  Lengths that arrive on the CPU are left on the device tensors as the ``_dx_host_lengths`` hint
+        (functional.Lengths), so that forward and loss need no device->host sync."""
         if len(batch) != 14:
             raise ValueError(f'Batch must have 14 elements (including speaker embeddings). Got {len(batch)}. '
                              'Run training.py pre_process to compute ECAPA embeddings and ensure .spk_emb.npy files exist.')
         (symbols, durations_float, durations_int, symbols_energy, symbols_pitch, input_lengths, frames_energy, frames_pitch,
          mel_specs, output_lengths, speaker_ids, _feature_dirs, _feature_files, spk_embs) = batch
-        host = {}
-        if not input_lengths.is_cuda:
-            host['in'] = input_lengths.tolist()
-            host['out'] = output_lengths.tolist()
+        host = None if input_lengths.is_cuda else (input_lengths.tolist(), output_lengths.tolist())
         to = lambda t, dt: t.to(device, non_blocking=True).to(dt)
         spk_embs = to(spk_embs, torch.float32)
         symbols, durations_int = to(symbols, torch.long), to(durations_int, torch.long)
         durations_float, symbols_energy, symbols_pitch = (to(t, torch.float32) for t in (durations_float, symbols_energy, symbols_pitch))
         input_lengths, output_lengths, speaker_ids = (to(t, torch.long) for t in (input_lengths, output_lengths, speaker_ids))
         frames_energy, frames_pitch, mel_specs = (to(t, torch.float32) for t in (frames_energy, frames_pitch, mel_specs))
-        if host:                                   # ride along on the tensor objects themselves (no global cache to go stale)
-            input_lengths._dx_host_lengths = host['in']
-            output_lengths._dx_host_lengths = host['out']
+        if host:
+            input_lengths._dx_host_lengths, output_lengths._dx_host_lengths = host
         inputs = (symbols, durations_float, durations_int, symbols_energy, symbols_pitch, input_lengths,
                   frames_energy, frames_pitch, mel_specs, output_lengths, speaker_ids, spk_embs)
         targets = (durations_float, symbols_energy, symbols_pitch, mel_specs, output_lengths, speaker_ids)
         return inputs, targets
-
-    @staticmethod
-    def _lengths(t):
-        """A fresh ``Lengths`` per forward call (never reused across calls: the tensor's contents may have changed), left on the tensor
-        object so that the loss, which is handed the same output-length tensor, does not build a second one (an int64 -> int32 launch).
-        ``t._dx_rows_exist`` (device int32 [B], set by a bucketed trainer.Trainer on its static length tensors): the rows that exist on this
-        axis although the batch tensors are allocated longer (Lengths.exist)."""
-        obj = Lengths(t, host=getattr(t, '_dx_host_lengths', None))
-        obj.exist = getattr(t, '_dx_rows_exist', None)
-        try:
-            t._dx_lengths = obj
-        except AttributeError:
-            pass
-        return obj
 
     @staticmethod
     def _require_gpu(t):
@@ -415,13 +410,14 @@ class DaftExprt(nn.Module):
 
     # -- training forward ----------------------------------------------------------------------------------------------
     def forward(self, inputs, external_accent_emb=None, external_spk_emb=None):
-        """reference model.py:889-948"""
+        """reference model.py:889-948.  ``inputs[5]`` / ``inputs[9]``: length tensors or ``Lengths``, handed back as they came in
+        ``encoder_preds[3]`` / ``decoder_preds[1]`` (a ``Lengths`` reaches the loss with its int32 copy and ``exist``)."""
         if len(inputs) != 12:
             raise ValueError(f'inputs must have 12 elements (including spk_embs). Got {len(inputs)}.')
         (symbols, durations_float, durations_int, symbols_energy, symbols_pitch, input_lengths,
          frames_energy, frames_pitch, mel_specs, output_lengths, _speaker_ids, spk_embs) = inputs
         self._require_gpu(symbols)
-        in_lens, out_lens = self._lengths(input_lengths), self._lengths(output_lengths)
+        in_lens, out_lens = Lengths.of(input_lengths), Lengths.of(output_lengths)
         if external_spk_emb is not None:
             spk_emb = external_spk_emb
         else:
@@ -483,7 +479,7 @@ class DaftExprt(nn.Module):
             raise ValueError('external_accent_emb required for inference. Provide --accent_emb_audios_dir or use a checkpoint '
                              'with memorized_accent_emb (e.g. from adapt_accent).')
         film = self.style_adapter(external_accent_emb + spk_emb)
-        in_lens = self._lengths(input_lengths)
+        in_lens = Lengths.of(input_lengths)
         enc_outputs = self.phoneme_encoder(symbols, film['phoneme_encoder'], in_lens)
         if external_prosody is None:
             raise ValueError('external_prosody must be provided for inference as the internal predictor has been removed.')

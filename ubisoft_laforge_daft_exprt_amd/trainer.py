@@ -30,7 +30,7 @@ MI355X-specific structure of one update (``use_graphs=True``, the default):
   * ``bucket=(l_step, t_step)``: the reference's collate pads every batch to its own longest utterance, so the exact padded shape
     changes almost every step and every new shape costs an eager step plus a capture.  In bucketed mode a micro-batch whose longest
     utterances are (L, T) runs at (L rounded up to l_step, T rounded up to t_step): the padded inputs get zero tails, and device
-    int32 vectors ``exist`` = L / T (Lengths.exist, carried on the length tensors as ``_dx_rows_exist``) tell every k = 3 launch,
+    int32 vectors ``exist`` = L / T (functional.Lengths.exist, in the batch's length slots: pad_batch) tell every k = 3 launch,
     forward and backward, that rows beyond them do not exist.  With dropout off the step computes what the exact-shape step
     computes ("logical rows vs stride"); dropout masks are drawn over the bucket's row stride instead.
 
@@ -48,6 +48,8 @@ import torch
 
 from . import ops
 from .ddp import GradientReducer
+from .functional import Lengths
+from .loss import LossTerms
 from .optim import FusedAdam, update_learning_rate
 
 
@@ -67,9 +69,9 @@ def group_of(name: str, levels: int = 3) -> int:
 
 def pad_batch(inputs, Lb, Tb):
     """A parsed micro-batch (DaftExprt.parse_batch) whose longest utterances are (L, T), padded with zeros to (Lb >= L, Tb >= T) rows:
-    -> (inputs, targets) of the padded shape.  Its two length tensors are fresh objects carrying ``_dx_rows_exist`` (device int32 [B] =
-    L / T: rows beyond them do not exist for the k = 3 launches, Lengths.exist) and the PADDED shape's host lengths (``_dx_host_lengths``:
-    host metadata only sizes tensors, so a graph captured on one batch serves every batch of its bucket)."""
+    -> (inputs, targets) of the padded shape.  Its length slots hold ``Lengths`` with ``exist`` (device int32 [B]) = L / T: rows beyond
+    them do not exist for the k = 3 launches; and with the PADDED shape's host lengths (host metadata only sizes tensors, so a graph
+    captured on one batch serves every batch of its bucket)."""
     B, L = inputs[0].shape
     T = inputs[8].shape[2]
     if Lb < L or Tb < T:
@@ -81,12 +83,12 @@ def pad_batch(inputs, Lb, Tb):
     for i in (6, 7, 8):                               # frame energy / pitch (B, T), mels (B, n_mel, T)
         padded[i] = pad(inputs[i], Tb)
     for i, n, e in ((5, Lb, L), (9, Tb, T)):
-        lt = inputs[i].clone()                        # a fresh tensor object: no Lengths cached on it by an earlier call
-        lt._dx_host_lengths = [n] * B
-        lt._dx_rows_exist = torch.full((B,), e, dtype=torch.int32, device=lt.device)
-        padded[i] = lt
-    padded = tuple(padded)
-    return padded, (padded[1], padded[3], padded[4], padded[8], padded[9], padded[10])      # the targets alias the inputs, as parse_batch builds them
+        padded[i] = Lengths(inputs[i], host=[n] * B, exist=torch.full((B,), e, dtype=torch.int32, device=inputs[i].device))
+    return _with_targets(tuple(padded))
+
+
+def _with_targets(inputs):
+    return inputs, (inputs[1], inputs[3], inputs[4], inputs[8], inputs[9], inputs[10])      # the targets alias the inputs, as parse_batch builds them
 
 
 PHASE_NAMES = ('A: forward, loss, backward of decoder / upsampler / phoneme encoder / style adapter / classifier',
@@ -168,14 +170,18 @@ class Trainer:
         return {'groups': plan, 'total_bytes': total, 'exposed_bytes': plan[-1]['bytes'], 'exposed_fraction': round(plan[-1]['bytes'] / total, 4)}
 
     # -- device work of one update ----------------------------------------------------------------------------------------
-    def _forward_loss(self, inputs, targets, iteration):
-        """train.py:405-422 on parsed device tensors: RAW frame prosody for the consistency losses, conditioning, forward, loss."""
+    def _forward_loss(self, inputs, targets, iteration, keep=None):
+        """train.py:405-422 on a parsed micro-batch: RAW frame prosody for the consistency losses, conditioning, forward, loss."""
         raw_frames_energy, raw_frames_pitch = inputs[6], inputs[7]       # the frozen pitch predictor outputs RAW pitch
         if self.conditioner is not None:
-            inputs = self.conditioner.process_batch(inputs, self.device)   # length tensors pass through (host lengths ride along)
+            inputs = self.conditioner.process_batch(inputs, self.device)   # the length slots pass through untouched
         targets = (targets[0], inputs[3], inputs[4], targets[3], targets[4], targets[5], raw_frames_energy, raw_frames_pitch)
         outputs = self.model(inputs)
-        return self.criterion(outputs, targets, iteration)
+        result = self.criterion(outputs, targets, iteration)
+        if keep is not None:                         # validate(keep_outputs=True): (targets, outputs) with tensors in the length slots
+            outputs[2][3], outputs[3][1] = outputs[2][3].i64, outputs[3][1].i64
+            keep.append((targets[:4] + (targets[4].i64,) + targets[5:], outputs))
+        return result
 
     def _phases(self, parsed, iteration, launch):
         """zero the buckets; per micro-batch: forward, loss, backward phase A (everything downstream of the accent embedding).
@@ -225,30 +231,22 @@ class Trainer:
         return tot, terms, [phase(level) for level in range(1, self.cut_levels + 1)]
 
     def _parse(self, batches):
-        parsed = [self._bucketed(*self.model.parse_batch(self.device, b)) for b in batches]
+        parsed = [self._parse_one(b) for b in batches]
         key = (self.model.runtime.precision,) + tuple((tuple(i[0].shape), tuple(i[8].shape)) for i, _ in parsed)   # (B, L_max), (B, n_mel, T_max) per micro-batch
         return parsed, key
 
-    def _bucketed(self, inputs, targets):
-        """Bucketed mode: the parsed micro-batch padded up to its bucket (pad_batch); without a bucket it is returned as it is."""
+    def _parse_one(self, batch):
+        """parse_batch -> (inputs, targets) with ONE ``Lengths`` per axis in the length slots (inputs[5], inputs[9] = targets[4]): model,
+        loss and every backward Function of the micro-batch share it.  Bucketed mode: padded up to its bucket (pad_batch)."""
+        inputs, _ = self.model.parse_batch(self.device, batch)
         if self.bucket is None:
-            return inputs, targets
+            return _with_targets(inputs[:5] + (Lengths.of(inputs[5]),) + inputs[6:9] + (Lengths.of(inputs[9]),) + inputs[10:])
         L, T = inputs[0].shape[1], inputs[8].shape[2]
         return pad_batch(inputs, -(-L // self.bucket[0]) * self.bucket[0], -(-T // self.bucket[1]) * self.bucket[1])
 
-    def _static_inputs(self, parsed):
-        static = []
-        for inputs, targets in parsed:
-            si = tuple(t.clone() for t in inputs)
-            for i in (5, 9):                                  # host lengths ride along: shapes / maxima are part of the key
-                h = getattr(inputs[i], '_dx_host_lengths', None)
-                si[i]._dx_host_lengths = h if h is not None else inputs[i].tolist()   # (a sync, at capture time only)
-                e = getattr(inputs[i], '_dx_rows_exist', None)
-                if e is not None:                             # bucketed: rewritten before every replay (_copy_static)
-                    si[i]._dx_rows_exist = e.clone()
-            st = (si[1], si[3], si[4], si[8], si[9], si[10])  # the targets alias the inputs, as parse_batch builds them
-            static.append((si, st))
-        return static
+    @staticmethod
+    def _static_inputs(parsed):
+        return [_with_targets(tuple(t.clone() for t in inputs)) for inputs, _ in parsed]      # (Lengths.clone: ``i32`` and ``exist`` too)
 
     def _capture(self, parsed, key):
         """One graph per backward phase for this padded shape.  One eager step on a side stream first (kernel attributes, weight
@@ -289,14 +287,10 @@ class Trainer:
 
     @staticmethod
     def _copy_static(si, inputs):
-        """A micro-batch into the static input buffers of a graph (inputs of the same shapes), with its existence vectors."""
-        for dst, src in zip(si, inputs):
-            if dst.data_ptr() != src.data_ptr():      # a batch built by resident_batch() already lives in the static buffers
+        """A micro-batch into the static input buffers of a graph (inputs of the same shapes; Lengths.copy_ for the length slots)."""
+        for i, (dst, src) in enumerate(zip(si, inputs)):
+            if i in (5, 9) or dst.data_ptr() != src.data_ptr():      # a batch built by resident_batch() already lives in the static buffers
                 dst.copy_(src, non_blocking=True)
-        for i in (5, 9):
-            e = getattr(si[i], '_dx_rows_exist', None)
-            if e is not None:
-                e.copy_(inputs[i]._dx_rows_exist, non_blocking=True)
 
     def resident_batch(self, batch):
         """The batch copied into the static input buffers of its shape's graphs (captured now if need be) and handed back as a
@@ -313,7 +307,11 @@ class Trainer:
         si = g.inputs[0][0]
         for dst, src in zip(si, parsed[0][0]):
             dst.copy_(src)
-        return (si[0], si[1], si[2], si[3], si[4], si[5], si[6], si[7], si[8], si[9], si[10], batch[11], batch[12], si[11])
+        out = list(si[:11]) + [batch[11], batch[12], si[11]]
+        for i in (5, 9):                                      # a reference 14-tuple carries tensors: the host lengths go along as the hint
+            out[i] = si[i].i64
+            out[i]._dx_host_lengths = si[i].host
+        return tuple(out)
 
     def train_step(self, batches):
         """``batches``: the ``accumulation_steps`` micro-batches (reference 14-tuples) of one parameter update.
@@ -339,7 +337,6 @@ class Trainer:
             for gid, graph in enumerate(g.graphs):
                 graph.replay()
                 red.launch_group(gid)                         # exchanged (RCCL, its own stream) while the next phase's graph runs
-            from .loss import LossTerms
             tot, terms = g.loss, [LossTerms(t) for t in g.terms_dev]
         else:
             tot, terms, rest = self._phases(parsed, self.iteration, red.launch_group)
@@ -353,9 +350,9 @@ class Trainer:
         return tot, terms, grad_norm
 
     # -- validation: train.py:163-209 ---------------------------------------------------------------------------------------
-    def _val_forward(self, inputs, targets):
+    def _val_forward(self, inputs, targets, keep=None):
         with torch.no_grad():
-            return self._forward_loss(inputs, targets, self.val_adv_weight)
+            return self._forward_loss(inputs, targets, self.val_adv_weight, keep)
 
     def validate(self, batches, keep_outputs=False):
         """The reference's ``validate`` (train.py:163-209, called at :474-491) on this rank's validation batches: eval mode (dropout
@@ -363,7 +360,6 @@ class Trainer:
         averaged over the batches; every rank runs it, nothing is exchanged.  The device work of a batch is ONE captured graph per
         padded shape (forward + loss); the per-batch losses are summed on the device and fetched with one transfer at the end.
         Returns (val_loss, dict of the 7 averaged terms[, list of (targets, outputs) when ``keep_outputs``])."""
-        from .loss import LossTerms
         model = self.model
         was_training = model.training
         model.eval()
@@ -374,16 +370,9 @@ class Trainer:
         kept, n = [], 0
         try:
             for batch in batches:
-                (inputs, targets), = [self._bucketed(*model.parse_batch(self.device, batch))]
+                inputs, targets = self._parse_one(batch)
                 if keep_outputs or not self.use_graphs:      # the caller wants the tensors themselves: eager
-                    raw = (inputs[6], inputs[7])
-                    cin = self.conditioner.process_batch(inputs, self.device) if self.conditioner is not None else inputs
-                    tg = (targets[0], cin[3], cin[4], targets[3], targets[4], targets[5], raw[0], raw[1])
-                    with torch.no_grad():
-                        outputs = model(cin)
-                        loss, indiv = self.criterion(outputs, tg, self.val_adv_weight)
-                    if keep_outputs:
-                        kept.append((tg, outputs))
+                    loss, indiv = self._val_forward(inputs, targets, kept if keep_outputs else None)
                     tot += loss
                     terms += indiv._device_terms
                 else:
@@ -435,7 +424,6 @@ class Trainer:
                 'optimizer': self.optimizer.state_dict(), 'config_params': cfg}
 
     def save_checkpoint(self, filepath):
-        import os
         os.makedirs(os.path.dirname(os.path.abspath(filepath)), exist_ok=True)
         torch.save(self.checkpoint(), filepath)
 
