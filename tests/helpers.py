@@ -1,4 +1,5 @@
-"""Shared fixture loading for the parity tests (data only; nothing here touches /root/reference)."""
+"""Shared helpers of the tests: fixture loading for the parity tests (data only; nothing here touches the reference project), and the
+host side of the attention dropout checks (the counter hash in numpy, the mask read-out, float64 and rounding references)."""
 import json
 import os
 
@@ -80,6 +81,129 @@ def write_synthetic_features(root, seed=21, n=5):
     with open(list_file, 'w', encoding='utf-8') as f:
         f.writelines(f'{d}|{n_}|{s}\n' for d, n_, s in rows)
     return list_file, rows
+
+
+def dx_rand64_fields(seed, idx):
+    """csrc/dx_common.h ``dx_rand64`` restated in numpy (uint32 arithmetic): ``idx`` is a uint64 array of draw counters; returns the four
+    16-bit fields of each 64-bit draw, lowest first (field i decides element 4 * counter + i)."""
+    M = np.uint32
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    with np.errstate(over='ignore'):
+        x = (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32) ^ M(seed & 0xFFFFFFFF)
+        hi = (idx >> np.uint64(32)).astype(np.uint32) ^ M(seed >> 32)
+        x ^= hi * M(0x9E3779B1)
+        x ^= x >> M(16); x = x * M(0x7FEB352D); x ^= x >> M(15); x = x * M(0x846CA68B); x ^= x >> M(16)
+        y = (x ^ M(0x85EBCA6B)) * M(0xC2B2AE35); y ^= y >> M(15)
+    return [x & M(0xFFFF), x >> M(16), y & M(0xFFFF), y >> M(16)]
+
+
+def host_attention_keep(seed, B, H, N, p):
+    """The documented attention dropout mask, rebuilt on the host: bool (B, H, N, N), True = kept.  The draw counter of
+    (utterance b, head h, query q, key) is ``(((b * H + h) * N + q) << 14) | (key >> 2)``, its field is ``key & 3``, and the element is
+    kept iff ``field >= round(p * 65536)`` (csrc/dx_attention.hip ``drop_index``, csrc/dx_common.h ``dx_dropout_scale``)."""
+    thr = int(round(float(np.float32(p)) * 65536))
+    rows = np.arange(B * H * N, dtype=np.uint64)[:, None]
+    groups = np.arange((N + 3) // 4, dtype=np.uint64)[None, :]
+    fields = dx_rand64_fields(seed, (rows << np.uint64(14)) | groups)
+    keep = np.stack([f >= thr for f in fields], axis=-1).reshape(B * H * N, -1)[:, :N]
+    return torch.from_numpy(np.ascontiguousarray(keep)).view(B, H, N, N)
+
+
+def attention_valid(lens, heads, N):
+    """bool (B, H, N, N): query and key both inside the utterance"""
+    inside = torch.arange(N)[None, :] < torch.as_tensor(lens, dtype=torch.long)[:, None]
+    return (inside[:, None, :, None] & inside[:, None, None, :]).expand(-1, heads, -1, -1)
+
+
+def recover_keep(fwd, B, N, heads, lens, p, tol=1e-4):
+    """Reads the attention dropout mask out of a forward.  ``fwd(qkv)`` takes a float32 CPU (B, N, 3 * 64 * heads) tensor and returns
+    the context (B, N, 64 * heads) of ONE fixed (seed, lengths, p); it is called ceil(N / 64) times.  In call j, q = k = 0 (every valid
+    key has probability 1 / len) and V is the identity on key block j (key 64 j + c -> channel c of every head), zero elsewhere, so
+    ``ctx[b, q, h * 64 + c] * len_b * (1 - p)`` is keep[b, h, q, 64 j + c].  The mask depends on the counter, not on the values, so
+    the calls tile the whole mask.  Asserted, not assumed: every decoded value is within ``tol`` of 0 or of 1, channels of keys beyond
+    the utterance and all padded query rows are exactly zero, and every valid (b, h, q, key) has been decoded.
+    Returns bool (B, heads, N, N) on the CPU, False outside the valid region."""
+    D = 64 * heads
+    lens = [int(n) for n in lens]
+    assert len(lens) == B and all(1 <= n <= N for n in lens)
+    keep = torch.zeros(B, heads, N, N, dtype=torch.bool)
+    seen = torch.zeros(B, heads, N, N, dtype=torch.bool)
+    for j in range((N + 63) // 64):
+        k0, k1 = 64 * j, min(64 * j + 64, N)
+        qkv = torch.zeros(B, N, 3 * D)
+        for h in range(heads):
+            qkv[:, k0:k1, 2 * D + 64 * h:2 * D + 64 * h + (k1 - k0)] = torch.eye(k1 - k0)
+        ctx = fwd(qkv).detach().double().cpu()
+        assert ctx.shape == (B, N, D) and bool(torch.isfinite(ctx).all())
+        for b, n in enumerate(lens):
+            assert not ctx[b, n:].any(), ('padded query rows must be zero', b, j)
+            val = ctx[b, :n].view(n, heads, 64).transpose(0, 1) * (n * (1.0 - p))      # (heads, q, c)
+            nk = max(0, min(k1, n) - k0)                                              # keys of this block inside the utterance
+            assert not val[:, :, nk:].any(), ('probability on a key beyond the utterance', b, j)
+            if nk == 0:
+                continue
+            val = val[:, :, :nk]
+            bit = val.round()
+            off = (val - bit).abs().max().item()
+            assert off <= tol and bool(((bit == 0) | (bit == 1)).all()), ('not a 0 / 1 mask value', b, j, off, val.min().item(), val.max().item())
+            keep[b, :, :n, k0:k0 + nk] = bit.bool()
+            seen[b, :, :n, k0:k0 + nk] = True
+    assert torch.equal(seen, attention_valid(lens, heads, N)), 'a valid position was left out'
+    return keep
+
+
+def attention_reference64(qkv, dctx, lens, heads, keep=None, p=0.0):
+    """float64 attention through autograd on the device of ``qkv``: keep / (1 - p) on the probabilities, padded queries zeroed, dctx zeroed
+    on padded queries (the model's contract).  Returns ctx (B, N, D), lse (B, H, N; natural log, pre-dropout, 0 on padded queries) and
+    the three gradients dq, dk, dv (B, N, D each)."""
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    x = qkv.detach().double().clone().requires_grad_(True)
+    sp = lambda t: t.reshape(B, N, heads, 64).transpose(1, 2)
+    q, k, v = (sp(t) for t in x.split(D, dim=2))
+    lens = torch.as_tensor(lens, dtype=torch.long, device=qkv.device)
+    pad = torch.arange(N, device=qkv.device)[None, :] >= lens[:, None]
+    s = ((q * 0.125) @ k.transpose(-1, -2)).masked_fill(pad[:, None, None, :], float('-inf'))
+    lse = torch.logsumexp(s, dim=-1) * (~pad)[:, None, :]
+    pr = torch.softmax(s, dim=-1)
+    if keep is not None:
+        pr = pr * keep.to(qkv.device, torch.float64) / (1.0 - p)
+    valid = (~pad)[:, :, None].double()
+    ctx = (pr @ v).transpose(1, 2).reshape(B, N, D) * valid
+    ctx.backward(dctx.detach().double() * valid)
+    dq, dk, dv = x.grad.split(D, dim=2)
+    return ctx.detach(), lse.detach(), dq, dk, dv
+
+
+def attention_emulation(qkv, lens, heads, keep=None, p=0.0, h16=None, dctx=None):
+    """Plain torch restatement of the attention kernels' arithmetic, reference-only (any device, fp32): with ``h16`` (torch.bfloat16 /
+    torch.float16) every matrix operand -- q, k, v, the unnormalised probabilities, dctx, dS -- is rounded to that type before its
+    product, products accumulate in fp32, and a context stored in 16 bits is rounded once more by the caller.  ``keep``: bool or 0 / 1
+    (B, H, N, N), applied as keep / (1 - p).  Returns ctx (padded queries zero), or (ctx, dq, dk, dv) when ``dctx`` is given."""
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    rd = (lambda t: t.to(h16).float()) if h16 is not None else (lambda t: t)
+    sp = lambda t: t.reshape(B, N, heads, 64).transpose(1, 2)
+    q, k, v = (sp(rd(t.float())) for t in qkv.split(D, dim=2))
+    lens = torch.as_tensor(lens, dtype=torch.long, device=qkv.device)
+    pad = torch.arange(N, device=qkv.device)[None, :] >= lens[:, None]
+    s = (q @ k.transpose(-1, -2) * 0.125).masked_fill(pad[:, None, None, :], float('-inf'))
+    e = torch.exp(s - s.amax(-1, keepdim=True))
+    l = e.sum(-1, keepdim=True)
+    scale = 1.0 if keep is None else 1.0 / (1.0 - p)
+    km = torch.ones_like(e) if keep is None else keep.to(e.device, e.dtype)
+    qvalid = (~pad)[:, None, :, None].float()
+    ctx = (rd(e * km) @ v) * (scale / l) * qvalid
+    merge = lambda t: t.transpose(1, 2).reshape(B, N, D)
+    if dctx is None:
+        return merge(ctx)
+    g = sp(rd(dctx.float())) * qvalid
+    pn = e / l                                                                  # the backward recomputes P from the saved lse
+    dv = rd(pn * km).transpose(-1, -2) @ g * scale
+    delta = (g * ctx).sum(-1, keepdim=True)
+    ds = rd(pn * ((g @ v.transpose(-1, -2)) * km * scale - delta) * qvalid)
+    dq, dk = ds @ k * 0.125, ds.transpose(-1, -2) @ q * 0.125
+    return merge(ctx), merge(dq), merge(dk), merge(dv)
 
 
 FEATURE_STATS = {'spk 0': {'energy': {'mean': 2.0, 'std': 1.5}, 'pitch': {'mean': 2.5, 'std': 1.2}},

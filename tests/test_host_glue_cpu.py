@@ -44,21 +44,13 @@ def test_exchange_groups_leave_at_most_a_quarter_of_the_gradient_bytes_exposed()
 
 
 def test_dropout_counter_hash_statistics():
-    """csrc/dx_common.h ``dx_rand64`` restated in numpy (uint32 arithmetic): four 16-bit fields per 64-bit draw decide keep / drop
-    by ``field >= round(p * 65536)``.  On attention-shaped counters ((row << 14) | key group) and on consecutive counters: keep rate
+    """csrc/dx_common.h ``dx_rand64`` restated in numpy (``helpers.dx_rand64_fields``, uint32 arithmetic): four 16-bit fields per 64-bit
+    draw decide keep / drop by ``field >= round(p * 65536)``.  On attention-shaped counters ((row << 14) | key group) and on consecutive counters: keep rate
     per field, cross-field, lag-1 along keys / rows, seed vs seed + 1 correlation at noise level, top-byte uniformity, and the
     variance of the number of dropped elements per row against the binomial's."""
     import numpy as np
+    from tests.helpers import dx_rand64_fields as rand64
     M = np.uint32
-
-    def rand64(seed, idx):
-        with np.errstate(over='ignore'):
-            x = (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32) ^ M(seed & 0xFFFFFFFF)
-            hi = (idx >> np.uint64(32)).astype(np.uint32) ^ M(seed >> 32)
-            x ^= hi * M(0x9E3779B1)
-            x ^= x >> M(16); x = x * M(0x7FEB352D); x ^= x >> M(15); x = x * M(0x846CA68B); x ^= x >> M(16)
-            y = (x ^ M(0x85EBCA6B)) * M(0xC2B2AE35); y ^= y >> M(15)
-        return [x & M(0xFFFF), x >> M(16), y & M(0xFFFF), y >> M(16)]
 
     thr = int(round(0.1 * 65536))
     corr = lambda a, b: abs(float(np.corrcoef(a.ravel(), b.ravel())[0, 1]))
