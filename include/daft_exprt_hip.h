@@ -346,6 +346,20 @@ int dx_mel_pack(const float* fb, int n_mels, int n_freq, int kmax, void* basis, 
  * clamped mel over channels.  Row b has lengths[b] / 256 frames (none if lengths[b] <= 384); everything past them is written as 0. */
 int dx_mel(const float* wav, long sxb, int S, const int* lengths, const void* basis, const void* fb, float* mel, long smb,
            float* energy, int B, int T_max, int n_mels, int kmax, float clip, void* stream);
+/* The two extra operands of dx_mel_bwd: the basis packed with samples as columns and the filter bank packed with bins as columns.
+ * Their sizes are those dx_mel_basis_size returns (basisT: basis_bytes, fbT: fb_bytes). */
+int dx_mel_bwd_pack(const float* fb, int n_mels, int n_freq, int kmax, void* basisT, void* fbT, void* stream);
+/* Waveform gradient of sum(gmel . mel) for the mel of dx_mel (fp32; the energy output has no gradient here).  wav, lengths, basis, fb,
+ * T_max, n_mels, kmax, clip as in the forward call; gmel [B][n_mels][T_max] (batch stride sgb) -> dwav [B][sxb], all S samples of
+ * every row written.  Nothing was saved by the forward: each valid frame's spectrum and linear mel are recomputed with the forward's
+ * own arithmetic, then dlin = gmel / lin where lin >= clip (else 0), dmag = fb^T dlin, dre = dmag re / mag, dim = dmag im / mag,
+ * dframe = [dre | dim] . basis^T, overlap-added over the four frames that cover a padded sample, the 384 reflected samples of each
+ * end folded back onto the samples they mirror.  Samples at or past lengths[b] get 0 (all of a row with lengths[b] <= 384); wav and
+ * gmel are never read past a row's samples / frames.  One launch, no workspace, no atomics: every element is summed in a fixed order,
+ * so two runs, and a batch row and the utterance alone, are bitwise equal.  dwav must not alias wav. */
+int dx_mel_bwd(const float* wav, long sxb, int S, const int* lengths, const void* basis, const void* fb, const void* basisT,
+               const void* fbT, const float* gmel, long sgb, float* dwav, int B, int T_max, int n_mels, int kmax, float clip,
+               void* stream);
 
 #ifdef __cplusplus
 }

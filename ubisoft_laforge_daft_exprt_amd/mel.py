@@ -7,6 +7,10 @@ Per utterance of ``len`` samples: reflect-pad by (n_fft - hop) / 2 = 384 with th
 energy = L2 norm of ``max(mel, min_clipping)`` over channels.  ``MelSpectrogram`` runs a padded (B, S_max) device batch in one launch
 (csrc/dx_mel.hip); row b is bitwise that utterance run alone, and everything at or past a row's frame count is 0.  The filter bank is
 ``mel_filter_bank``, a restatement of librosa's default ``filters.mel`` (Slaney scale and area normalisation).  There is no CPU path.
+
+The log-mel is differentiable with respect to the waveform: when ``wavs`` requires grad, ``mels`` carries a ``grad_fn`` whose backward
+is one ``dx_mel_bwd`` launch (the forward saves only the waveform; the spectrum is recomputed).  ``MelL1Loss`` is the mel term of the
+vocoder's generator loss (reference vocoder/finetune_hifigan.py:211-231) on that gradient.  Energy and frame counts carry no gradient.
 """
 from __future__ import annotations
 
@@ -103,6 +107,7 @@ class MelSpectrogram:
             raise NotImplementedError('a filter bank with weight on the Nyquist bin is not supported')
         self.device = torch.device(device)
         self._ops = None
+        self._bwd_ops = None
         self._lengths = {}                              # host lengths -> (int32 lengths, frames) on the device
 
     def _operands(self):
@@ -119,10 +124,44 @@ class MelSpectrogram:
             self._ops = (basis, fbp, fb)
         return self._ops
 
+    def _backward_operands(self):
+        if self._bwd_ops is None:
+            basis, fbp, fb = self._operands()
+            basis_t, fb_t = torch.empty_like(basis), torch.empty_like(fbp)      # the transposed packs have the forward packs' sizes
+            lib().dx_mel_bwd_pack(fb.data_ptr(), self.n_mels, fb.shape[1], self.kmax, basis_t.data_ptr(), fb_t.data_ptr(),
+                                  torch.cuda.current_stream(self.device).cuda_stream)
+            self._bwd_ops = (basis_t, fb_t)
+        return self._bwd_ops
+
+    def _launch(self, wavs, lens_i32, T):
+        B, S = wavs.shape
+        basis, fbp, _ = self._operands()
+        mels = torch.empty(B, self.n_mels, T, dtype=torch.float32, device=wavs.device)
+        energy = torch.empty(B, T, dtype=torch.float32, device=wavs.device)
+        lib().dx_mel(wavs.data_ptr(), S, S, lens_i32.data_ptr(), basis.data_ptr(), fbp.data_ptr(), mels.data_ptr(), self.n_mels * T,
+                     energy.data_ptr(), B, T, self.n_mels, self.kmax, self.min_clipping, torch.cuda.current_stream(wavs.device).cuda_stream)
+        return mels, energy
+
+    def _launch_backward(self, wavs, lens_i32, gmel):
+        B, S = wavs.shape
+        T = gmel.shape[2]
+        basis, fbp, _ = self._operands()
+        basis_t, fb_t = self._backward_operands()
+        gmel = gmel.float().contiguous()
+        dwav = torch.empty_like(wavs)
+        lib().dx_mel_bwd(wavs.data_ptr(), S, S, lens_i32.data_ptr(), basis.data_ptr(), fbp.data_ptr(), basis_t.data_ptr(), fb_t.data_ptr(),
+                         gmel.data_ptr(), self.n_mels * T, dwav.data_ptr(), B, T, self.n_mels, self.kmax, self.min_clipping,
+                         torch.cuda.current_stream(wavs.device).cuda_stream)
+        return dwav
+
     def __call__(self, wavs, lengths):
         """wavs (B, S_max) fp32 on the device; lengths: B sample counts, host ints (no host sync: capturable once the same lengths
         have run eagerly) or a device tensor (one small device-to-host copy sizes the output).  -> (mels (B, n_mels, T_max),
-        energy (B, T_max), frames (B,) int64 on the device), T_max = max(lengths) // 256."""
+        energy (B, T_max), frames (B,) int64 on the device), T_max = max(lengths) // 256.
+
+        If ``wavs`` requires grad (and grad mode is on), ``mels`` is differentiable once with respect to it: same launch, same bits,
+        and a backward of one launch with no host sync (capturable like the forward once a forward and backward have run eagerly).
+        ``energy`` and ``frames`` carry no gradient."""
         if wavs.dim() != 2:
             raise ValueError(f'MelSpectrogram: wavs must be (B, S_max), got shape {tuple(wavs.shape)}')
         if wavs.device.type != 'cuda':
@@ -146,12 +185,31 @@ class MelSpectrogram:
         if len(host) != B:
             raise ValueError(f'MelSpectrogram: {len(host)} lengths for a batch of {B}')
         T = max(n_frames(n) for n in host)
-        basis, fbp, _ = self._operands()
-        mels = torch.empty(B, self.n_mels, T, dtype=torch.float32, device=dev)
-        energy = torch.empty(B, T, dtype=torch.float32, device=dev)
-        lib().dx_mel(wavs.data_ptr(), S, S, lens_i32.data_ptr(), basis.data_ptr(), fbp.data_ptr(), mels.data_ptr(), self.n_mels * T,
-                     energy.data_ptr(), B, T, self.n_mels, self.kmax, self.min_clipping, torch.cuda.current_stream(dev).cuda_stream)
+        if wavs.requires_grad and torch.is_grad_enabled():
+            mels, energy = _MelFunction.apply(wavs, self, lens_i32, T)
+        else:
+            mels, energy = self._launch(wavs, lens_i32, T)
         return mels, energy, frames
+
+
+class _MelFunction(torch.autograd.Function):
+    """mels with the waveform gradient of csrc/dx_mel.hip's backward kernel; energy (and the integer frame counts, which never enter
+    here) are not differentiable.  Saves the waveform and the lengths only."""
+
+    @staticmethod
+    def forward(ctx, wavs, frontend, lens_i32, T):
+        mels, energy = frontend._launch(wavs, lens_i32, T)
+        frontend._backward_operands()                    # packed now, so that a captured backward launches nothing but the kernel
+        ctx.frontend = frontend
+        ctx.save_for_backward(wavs, lens_i32)
+        ctx.mark_non_differentiable(energy)
+        return mels, energy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gmel, _genergy):
+        wavs, lens_i32 = ctx.saved_tensors
+        return ctx.frontend._launch_backward(wavs, lens_i32, gmel), None, None, None
 
 
 _FRONTENDS = {}
@@ -179,7 +237,8 @@ def mel_spectrogram_HiFi(wav, hparams):
 
 def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False):
     """Drop-in for the reference's vocoder/dataset.mel_spectrogram: (B, S) waveforms -> (B, num_mels, S // 256) log-mel (clip 1e-5),
-    on the GPU; the result is on ``y``'s device."""
+    on the GPU; the result is on ``y``'s device.  Differentiable with respect to ``y`` as ``MelSpectrogram`` is, so the reference's
+    ``F.l1_loss(y_mel, mel_spectrogram(y_g_hat.squeeze(1), ...))`` back-propagates into the generated waveform."""
     check_stft(n_fft, win_size, hop_size, center)
     y2 = y.reshape(1, -1) if y.dim() == 1 else y
     check_lengths([y2.shape[1]], y2.shape[1])
@@ -187,3 +246,26 @@ def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin,
     fe = _frontend(sampling_rate, num_mels, fmin, fmax, 1e-5, dev)
     mels, _, _ = fe(y2.to(dev), [y2.shape[1]] * y2.shape[0])
     return mels.to(y.device)
+
+
+class MelL1Loss:
+    """The mel term of the vocoder's generator loss (reference vocoder/finetune_hifigan.py:211-231, ``F.l1_loss(y_mel, y_g_hat_mel) *
+    45`` on the full-band mel): ``scale * sum_valid |mel(wav_hat) - target_mel| / (n_mels * sum_b frames[b])``, differentiable with
+    respect to ``wav_hat`` through the HIP backward.  With equal lengths this is the reference's mean over the whole tensor.  With
+    ragged lengths the cells at or past a row's frame count are left out of both the sum and the count (they are padding in both
+    mels, and whatever ``target_mel`` holds there is ignored), so a short row weighs by its own frames only."""
+
+    def __init__(self, fmax=None, scale=45.0, device='cuda'):
+        self.frontend = MelSpectrogram(fmax=fmax, device=device)
+        self.scale = float(scale)
+
+    def __call__(self, wav_hat, lengths, target_mel):
+        """wav_hat (B, S_max), lengths as for ``MelSpectrogram``, target_mel (B, n_mels, >= T_max) log-mel -> scalar."""
+        mels, _, frames = self.frontend(wav_hat, lengths)
+        T = mels.shape[2]
+        if target_mel.dim() != 3 or target_mel.shape[0] != mels.shape[0] or target_mel.shape[1] != mels.shape[1] or target_mel.shape[2] < T:
+            raise ValueError(f'MelL1Loss: target_mel {tuple(target_mel.shape)} does not cover the mel {tuple(mels.shape)}')
+        keep = (torch.arange(T, device=mels.device)[None, :] < frames[:, None])[:, None, :]
+        delta = mels - target_mel[:, :, :T].to(mels.dtype)
+        total = torch.where(keep, delta, torch.zeros((), dtype=delta.dtype, device=delta.device)).abs().sum()   # masked before abs: no NaN leaks back
+        return total * self.scale / (frames.sum() * mels.shape[1])

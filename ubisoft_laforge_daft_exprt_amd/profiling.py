@@ -194,8 +194,12 @@ def price(name, a, geom: Geometry):
         frames = geom.rows(a['B'], a['T_max'])
         flops = 2.0 * frames * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])
         return 'mel<f32>', 'mfma', flops, frames * (256 * 4 + (a['n_mels'] + 1) * 4)
-    if name == 'dx_mel_pack':
-        return 'mel_pack', 'hbm', None, a['n_mels'] * a['n_freq'] * 4 + (2 * 1024 + a['n_mels']) * a['kmax'] * 4
+    if name == 'dx_mel_bwd':                             # valid frames only: the forward's two GEMMs recomputed + their two transposes
+        frames = geom.rows(a['B'], a['T_max'])
+        flops = 2.0 * frames * 2 * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])
+        return 'mel_bwd<f32>', 'mfma', flops, frames * (2 * 256 * 4 + a['n_mels'] * 4)
+    if name in ('dx_mel_pack', 'dx_mel_bwd_pack'):
+        return name[3:], 'hbm', None, a['n_mels'] * a['n_freq'] * 4 + (2 * 1024 + a['n_mels']) * a['kmax'] * 4
     return name[3:], 'hbm', None, None
 
 
