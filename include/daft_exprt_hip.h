@@ -361,6 +361,33 @@ int dx_mel_bwd(const float* wav, long sxb, int S, const int* lengths, const void
                const void* fbT, const float* gmel, long sgb, float* dwav, int B, int T_max, int n_mels, int kmax, float clip,
                void* stream);
 
+/* ---- prosody transfer and PCM (reference generate.py generate_batch_mel_specs; csrc/dx_prosody.hip) --------------------------------
+ * fp32 and integers only.  One launch each, no workspace, no atomics, every reduction in a fixed order that depends on the row alone:
+ * a batch row is bitwise that utterance run alone.  dur_int is int64 (as dx_duration_scan takes it), in_lens device int32 [B];
+ * positions l >= in_lens[b] of every (B, L) output are written as 0. */
+/* extract_features.py:287-342 (get_symbols_energy / get_symbols_pitch): symbol l with d = dur_int[b][l] > 0 covers the frames
+ * [off, off + d), off = the sum of the row's earlier durations.  sym_energy = their mean, sym_pitch = the mean of those > 0 (0 if
+ * none); d == 0: both 0, no frame consumed.  frames_* [B][ldt], T frames valid per row; frames at or past T are never read, so a row
+ * whose durations sum past T (a caller error, checked by the Python wrapper) yields wrong means and nothing worse. */
+int dx_symbol_prosody(const float* frames_energy, const float* frames_pitch, long ldt, const long* dur_int, const int* in_lens,
+                      float* sym_energy, float* sym_pitch, int B, int T, int L, void* stream);
+/* generate.py:165-185 (_normalize_external_feature), :265-269 (alpha scaling), model.py:1077-1087 (factors, zero where dur_int == 0)
+ * and model.py:975-1024 (pitch_shift / pitch_multiply), per element in that order, each operation rounded on its own:
+ *   normalize != 0: v == 0 stays 0; else [has_source: v = (v - src_mean) / src_std * tgt_std + tgt_mean;] v = (v - tgt_mean) / tgt_std;
+ *                   v *= alpha
+ *   energy *= energy_factors (NULL: skipped); energy = pitch = 0 where dur_int == 0 (NULL: skipped)
+ *   mode 0: pitch unchanged; 1 (add): p = (log(exp(std p + mean) + factor) - mean) / std; 2 (multiply): p += (p - m) factor, m = the
+ *   mean of the row's non-zero p at this point; p == 0 (unvoiced) stays exactly 0 in both, and an all-unvoiced row is all zeros.
+ * stats [B][4] = the row's target {energy mean, energy std, pitch mean, pitch std} (needed by normalize and by mode 1), source [4] the
+ * same four of the source speaker (read iff has_source).  normalize == 0 is model.inference's own pre-processing in the same launch.
+ * All tensors [B][L] contiguous; the outputs may not alias the inputs. */
+int dx_prosody_condition(const float* energy, const float* pitch, const long* dur_int, const int* in_lens, const float* energy_factors,
+                         const float* pitch_factors, const float* stats, const float* source, int has_source, float alpha_energy,
+                         float alpha_pitch, int mode, int normalize, float* energy_out, float* pitch_out, int B, int L, void* stream);
+/* generate.py:327 ((audio * 32767.5).clip(-32768, 32767).astype(np.int16)): fp32 multiply, clamp, truncation toward zero.
+ * audio [B][S] fp32 -> pcm [B][S] int16, 0 at or past sample_lengths[b] (device int32 [B]); both 16-byte aligned, B <= 65535. */
+int dx_pcm16(const float* audio, const int* sample_lengths, short* pcm, int B, long S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,130 @@
+"""Prosody-transfer synthesis, reference prosody to 16-bit PCM, for B = 16 utterances of about 100 symbols.  One JSON line:
+
+  speech_synthesizer_ms   ``SpeechSynthesizer.__call__`` on raw reference prosody (host durations, one conditioning launch, graph
+                          replay, batched vocoder, PCM on the device), wall clock with a device sync at the end
+  composed_ms             the same work from the pieces that existed before it: the reference's per-utterance host conditioning in
+                          torch (generate.py:226-272), ``GraphedSynthesizer``, ``infer_batch``, a device-to-host copy of the audio and
+                          the numpy int16 rule
+  kernels_us              the three kernels of csrc/dx_prosody.hip alone (event-bracketed means): symbol means for the batch's frames,
+                          conditioning, PCM of the batch's audio
+
+    python tools/bench_synthesis.py [--precision bf16]
+"""
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import ubisoft_laforge_daft_exprt_amd as dx  # noqa: E402
+from tests import helpers, vocoder_helpers as vh  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd import speech  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd.inference import GraphedSynthesizer  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd.synth import synthetic_inference_batch  # noqa: E402
+
+DEV = 'cuda'
+STATS = {'spk 0': {'energy': {'mean': 2.0, 'std': 1.5}, 'pitch': {'mean': 5.0, 'std': 0.25}},
+         'spk 1': {'energy': {'mean': 1.7, 'std': 1.1}, 'pitch': {'mean': 4.6, 'std': 0.3}}}
+SOURCE = {'energy': {'mean': 2.4, 'std': 1.3}, 'pitch': {'mean': 4.8, 'std': 0.28}}
+ALPHAS = dict(alpha_dur=1.1, alpha_pitch=1.3, alpha_energy=1.2)
+
+
+def wall(fn, n=10, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n
+
+
+def gpu_time(fn, n=50, warm=5):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / 1e3 / n
+
+
+def host_conditioning(entries, speaker_ids, hp):
+    """generate.py:213-278 as the reference runs it: a Python loop over utterances on the CPU, then the upload."""
+    B, L = len(entries), max(len(e['energy']) for e in entries)
+    dur, dur_int, energy, pitch = torch.zeros(B, L), torch.zeros(B, L, dtype=torch.long), torch.zeros(B, L), torch.zeros(B, L)
+    for b, entry in enumerate(entries):
+        n = len(entry['energy'])
+        dur[b, :n], dur_int[b, :n] = speech.host_durations(entry['durations_frames'], ALPHAS['alpha_dur'], hp)
+        st = hp.stats.get(f'spk {speaker_ids[b]}', hp.stats['spk 0'])
+        for out, key, alpha in ((energy, 'energy', ALPHAS['alpha_energy']), (pitch, 'pitch', ALPHAS['alpha_pitch'])):
+            v = torch.FloatTensor(entry[key])
+            zero = v == 0.
+            v = ((v - SOURCE[key]['mean']) / SOURCE[key]['std']) * st[key]['std'] + st[key]['mean']
+            v = (v - st[key]['mean']) / st[key]['std'] * alpha
+            v[zero] = 0.
+            out[b, :n] = v
+    return {'duration_preds': dur.to(DEV), 'durations_int': dur_int.to(DEV), 'energy_preds': energy.to(DEV), 'pitch_preds': pitch.to(DEV)}
+
+
+def main():
+    precision = sys.argv[sys.argv.index('--precision') + 1] if '--precision' in sys.argv else 'f32'
+    dx.set_precision(precision)
+    hp = helpers.golden_hparams(stats=STATS)
+    model = dx.DaftExprt(hp).to(DEV)
+    model.load_state_dict(helpers.golden_state_dict(), strict=True)
+    vocoder = dx.HiFiGanVocoder(vh.state_dict(), device=DEV, precision='bf16' if precision != 'f32' else 'f32')
+    inputs, prosody, spk, accent = synthetic_inference_batch(batch_size=16, sym_len_range=(80, 100), seed=1238)
+    lens = inputs[4].tolist()
+    frames = prosody['duration_preds'] * hp.sampling_rate / hp.hop_length
+    energy = torch.where(prosody['energy_preds'] != 0, prosody['energy_preds'].abs() * 1.3 + 0.3, torch.zeros(()))
+    pitch = torch.where(prosody['pitch_preds'] != 0, prosody['pitch_preds'] * 0.28 + 4.8, torch.zeros(()))
+    entries = [{'durations_frames': frames[b, :n].tolist(), 'energy': energy[b, :n].tolist(), 'pitch': pitch[b, :n].tolist()} for b, n in enumerate(lens)]
+    speaker_ids = inputs[5].tolist()
+    inputs = tuple(t.to(DEV) for t in inputs)
+    spk, accent = spk.to(DEV), accent.to(DEV)
+    synth = dx.SpeechSynthesizer(model, hp, vocoder)
+    plain = GraphedSynthesizer(model, hp)
+
+    def new():
+        return synth(inputs, 'add', entries, spk, accent, source_stats=SOURCE, **ALPHAS)
+
+    def composed():
+        ext = host_conditioning(entries, speaker_ids, hp)
+        _, (mel, out_lens), _ = plain(inputs, 'add', ext, spk, accent)
+        audio, _ = vocoder.infer_batch(mel, out_lens)
+        audio = audio.cpu().numpy()
+        return [(audio[b, :256 * n] * 32767.5).clip(min=-32768, max=32767).astype(np.int16) for b, n in enumerate(out_lens.tolist())]
+
+    out0 = new()
+    ref = composed()
+    agree = all(np.abs(out0['pcm'][b, :len(r)].cpu().numpy().astype(np.int32) - r).max() <= 1 for b, r in enumerate(ref))
+    T, S = out0['mel'].shape[2], out0['audio'].shape[1]
+    result = {'workload': f'B=16, L={inputs[0].shape[1]} (lengths {min(lens)}-{max(lens)}), T_max={T}, {int(out0["sample_lengths"].sum())} samples, {precision}',
+              'speech_synthesizer_ms': round(wall(new) * 1e3, 3), 'composed_ms': round(wall(composed) * 1e3, 3), 'pcm_within_one_lsb_of_composed': bool(agree)}
+    result['composed_over_new'] = round(result['composed_ms'] / result['speech_synthesizer_ms'], 3)
+    # the three kernels alone
+    enc = out0['encoder_preds']
+    fe, fp = torch.rand(16, T, device=DEV) + 0.1, torch.rand(16, T, device=DEV)
+    raw_e, raw_p = energy.to(DEV), pitch.to(DEV)
+    stats, source = speech.speaker_stats_table(speaker_ids, hp).to(DEV), speech.source_stats_row(SOURCE).to(DEV)
+    lens32 = inputs[4].to(torch.int32)
+    result['kernels_us'] = {
+        'symbol_prosody': round(gpu_time(lambda: speech.symbol_prosody(fe, fp, enc[1], lens)) * 1e6, 2),
+        'prosody_condition': round(gpu_time(lambda: speech._condition(raw_e, raw_p, enc[1], lens32, inputs[2], inputs[3], stats, source, 1.2, 1.3, 1, 1)) * 1e6, 2),
+        'pcm16': round(gpu_time(lambda: speech.to_pcm16(out0['audio'], out0['sample_lengths'])) * 1e6, 2)}
+    result['kernels_us_note'] = 'event-bracketed means of the Python wrappers: launch plus output allocation, not kernel time alone'
+    result['pcm16_gbps'] = round(S * 16 * 6 / (result['kernels_us']['pcm16'] * 1e-6) / 1e9, 1)
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()

@@ -80,7 +80,11 @@ class GraphedSynthesizer:
 
     def __call__(self, inputs, pitch_transform, external_prosody, external_embeddings, external_accent_emb, use_graph=True):
         """Same arguments as ``DaftExprt.inference``; returns the same triple."""
-        prep = self.prepare(inputs, pitch_transform, external_prosody)
+        return self.run(self.prepare(inputs, pitch_transform, external_prosody), external_embeddings, external_accent_emb, use_graph)
+
+    def run(self, prep, external_embeddings, external_accent_emb, use_graph=True):
+        """The device forward for a prosody stage that is already done: ``prep`` is what ``prepare`` returns (``speech.SpeechSynthesizer``
+        builds it with one conditioning launch instead).  Returns ``DaftExprt.inference``'s triple."""
         dev = prep['symbols'].device
         out_lens = torch.tensor(prep['out_host'], dtype=torch.long, device=dev)
         B, L = prep['symbols'].shape

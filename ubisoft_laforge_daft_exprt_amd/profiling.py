@@ -200,6 +200,12 @@ def price(name, a, geom: Geometry):
         return 'mel_bwd<f32>', 'mfma', flops, frames * (2 * 256 * 4 + a['n_mels'] * 4)
     if name in ('dx_mel_pack', 'dx_mel_bwd_pack'):
         return name[3:], 'hbm', None, a['n_mels'] * a['n_freq'] * 4 + (2 * 1024 + a['n_mels']) * a['kmax'] * 4
+    if name == 'dx_symbol_prosody':                      # two frame rows in, int64 durations in, two symbol rows out
+        return 'symbol_prosody', 'hbm', None, a['B'] * (2 * a['T'] * 4 + a['L'] * (8 + 2 * 4))
+    if name == 'dx_prosody_condition':                   # energy, pitch, two factor rows in, int64 durations in, two rows out
+        return 'prosody_condition', 'hbm', None, a['B'] * a['L'] * (6 * 4 + 8)
+    if name == 'dx_pcm16':
+        return 'pcm16', 'hbm', None, a['B'] * a['S'] * (4 + 2)
     return name[3:], 'hbm', None, None
 
 
