@@ -263,6 +263,12 @@ int dx_energy_diff(const float* ep, const float* et, const int* lens, float* des
 /* e_per_total = 1: c_e is divided by sum_b lens[b] on the device (loss.py:129 normalises the energy term by the batch's valid frames) */
 int dx_mel_grad(const float* mel_pred, const float* mel_target, const float* ep, const float* des, const int* lens,
                 float c_l1, float c_l2, float c_e, int e_per_total, float* dmel, int B, int M, int T, void* stream);
+/* Dynamic loss scale (see "dynamic loss scaling" below): dx_mel_grad_dyn, dx_pitch_grad_dyn and dx_loss_finalize_dyn are the launches
+ * of the same names with one more argument, scale_dev (device float, required): c_l1 / c_l2 / c_e, scale and grad_scale are multiplied
+ * by *scale_dev on the device, so a captured graph follows a scale that changes between replays.  *scale_dev is a power of two: the
+ * product is exact and the results are bitwise those of the static launch given the host product. */
+int dx_mel_grad_dyn(const float* mel_pred, const float* mel_target, const float* ep, const float* des, const int* lens,
+                    float c_l1, float c_l2, float c_e, int e_per_total, const float* scale_dev, float* dmel, int B, int M, int T, void* stream);
 /* loss.py:85-157 assembled on the device: terms[7] = {speaker_loss, speaker_ce_raw, post_mult_loss, mel_l1, mel_l2, energy, pitch},
  * total[1] = speaker + post_mult + l1 + l2 + ecw * energy + pcw * pitch; d_spk = dlogits * w; d_pm = pmw * pm / ||pm||_2.
  * w = *spk_w_dev if given (device scalar, re-read by every replay of a captured graph) else spk_w.  NULL ce / pm / esum / psum: term off.
@@ -273,6 +279,13 @@ int dx_loss_finalize(const float* ce, const float* spk_w_dev, float spk_w, const
                      const float* esum, float ecw, const float* psum, float pcw, float* terms, float* total, float grad_scale, void* stream);
 int dx_pitch_mse(const float* pp, int ldp, const float* gt, const int* lens, float* sums, int B, int T, void* stream);   /* ldp / ldd: element stride between consecutive frames of pp / dpp (the predictor's last conv writes 4-wide rows, channel 0 is the prediction) */
 int dx_pitch_grad(const float* pp, int ldp, const float* gt, const int* lens, const float* sums, float scale, float* dpp, int ldd, int B, int T, void* stream);
+int dx_pitch_grad_dyn(const float* pp, int ldp, const float* gt, const int* lens, const float* sums, float scale, const float* scale_dev,
+                      float* dpp, int ldd, int B, int T, void* stream);
+int dx_loss_finalize_dyn(const float* ce, const float* spk_w_dev, float spk_w, const float* dlogits, float* d_spk, int n_logits,
+                         const float* pm, float* d_pm, int n_pm, float pmw,
+                         const float* l1sum, const float* l2sum, const int* lens, int B, int M, float msw,
+                         const float* esum, float ecw, const float* psum, float pcw, float* terms, float* total, float grad_scale,
+                         const float* scale_dev, void* stream);
 /* The frozen pitch predictor of the pitch-consistency term, one launch per direction (layers/pitch_predictor.py:38-74 applied in loss.py:131-140):
  * mel (B, M = 80, T) fp32 -> pp (B, T), and its input-gradient chain dpp (B, T) -> dmel (B, M, T) +=.  w0..w2: the 16-bit packs of the three
  * 256-wide k = 3 convolutions written by dx_pack_weights (fwd takes the forward packs, bwd the backward packs); b*: biases; s* / t*: eval-mode
@@ -303,6 +316,28 @@ int dx_sumsq(const float* x, long n, float* out, void* stream);
 int dx_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, const float* normsq, float max_norm, float grad_scale, int* skipped,
                  float* norm_out, float* zero_after, void* stream);
+/* ---- dynamic loss scaling (fp16 operand mode; the rules of torch.amp.GradScaler, no reference counterpart) -------------------------
+ * The scaler state is eight 32-bit words in device memory, 4-byte aligned, owned by the caller:
+ *   [0] scale          float, a power of two: what the NEXT backward multiplies its loss gradients by (the *_dyn loss launches)
+ *   [1] inv_scale_used float, 1 / the scale the gradients now in the buckets were produced with
+ *   [2] apply          int, 1: this update is applied, 0: skipped (non-finite norm)
+ *   [3] applied        int, updates applied so far = the bias-correction step
+ *   [4] good_steps     int, consecutive applied updates since the scale last changed
+ *   [5] skipped        int, updates skipped so far
+ *   [6] bc1            float, 1 - beta1^applied        [7] bc2_sqrt  float, sqrt(1 - beta2^applied)   (double arithmetic, rounded once)
+ * The caller initialises [0], [3], [4], [5]; the rest is written before it is read.
+ * dx_scaler_update (one workgroup, after dx_sumsq / the all-reduce, before dx_adam_step_dyn) reads *normsq and first sets
+ * inv_scale_used = 1 / scale.  Non-finite: apply = 0, skipped += 1, good_steps = 0, scale = max(scale * backoff, min_scale).  Finite:
+ * apply = 1, applied += 1, bc1 / bc2_sqrt from the new applied, good_steps += 1 and, when it reaches growth_interval, scale =
+ * min(scale * growth, max_scale) and good_steps = 0.  growth >= 1 and backoff <= 1 must be powers of two.  A pure function of the
+ * norm and the state: ranks that hold the same state and the same all-reduced norm agree without communication. */
+int dx_scaler_update(void* state, const float* normsq, float beta1, float beta2, float growth, float backoff, int growth_interval,
+                     float min_scale, float max_scale, void* stream);
+/* dx_adam_step with grad_scale = inv_scale_used, the bias corrections and the skip decision read from the scaler state (apply == 0:
+ * p, m, v untouched); normsq is required; norm_out / zero_after as in dx_adam_step (written whether or not the update is applied). */
+int dx_adam_step_dyn(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, const float* normsq, float max_norm, const void* scaler, float* norm_out, float* zero_after,
+                     void* stream);
 
 /* ---- HiFi-GAN V1 vocoder, inference (reference vocoder/hifigan.py HiFiGANGenerator.forward; csrc/dx_vocoder.hip) ----------------
  * Activations are fp32, channels-last [B][samples][C] (conv_pre reads the (B, 80, T) mel through its strides).  frames (device int32

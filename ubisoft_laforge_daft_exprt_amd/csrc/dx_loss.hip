@@ -75,7 +75,12 @@ __global__ __launch_bounds__(256) void energy_diff_kernel(const float* __restric
 // dmel[b,m,t] = c_l1/len_b * sign(d) + c_l2/len_b * 2 d + c_e * (sum_{|k|<=2} des[t+k] / 5) * exp(p)^2 / ep[t]
 __global__ __launch_bounds__(256) void mel_grad_kernel(const float* __restrict__ mp, const float* __restrict__ mt,
                                                        const float* __restrict__ ep, const float* __restrict__ des, const int* __restrict__ lens,
-                                                       float c_l1, float c_l2, float c_e, int e_per_total, float* __restrict__ dmel, int M, int T) {
+                                                       float c_l1, float c_l2, float c_e, int e_per_total, float* __restrict__ dmel, int M, int T,
+                                                       const float* __restrict__ scale_dev) {
+  if (scale_dev) {                                      // dynamic loss scale: a power of two, so s * c is the host's float(s * c) bit for bit
+    const float s = *scale_dev;
+    c_l1 *= s; c_l2 *= s; c_e *= s;
+  }
   const int b = blockIdx.y, mg = threadIdx.x / MEL_TT, t = blockIdx.x * MEL_TT + (threadIdx.x & (MEL_TT - 1));
   if (e_per_total) {                                    // energy term normalised by the batch's total valid length (loss.py:129):
     __shared__ float scratch[4];                        // summed here, on the device, so that no host value is frozen into a graph
@@ -123,9 +128,11 @@ __global__ __launch_bounds__(256) void pitch_mse_kernel(const float* __restrict_
 
 // dpp = scale * 2 (pp - gt) mask / (count + 1e-5)
 __global__ __launch_bounds__(256) void pitch_grad_kernel(const float* __restrict__ pp, int ldp, const float* __restrict__ gt, const int* __restrict__ lens,
-                                                         const float* __restrict__ sums, float scale, float* __restrict__ dpp, int ldd, int T) {
+                                                         const float* __restrict__ sums, float scale, float* __restrict__ dpp, int ldd, int T,
+                                                         const float* __restrict__ scale_dev) {
   const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
+  if (scale_dev) scale *= *scale_dev;
   const float g = gt[(size_t)b * T + t];
   float v = 0.f;
   if (t < lens[b] && g != 0.f) v = scale * 2.f * (pp[((size_t)b * T + t) * ldp] - g) / (sums[1] + 1e-5f);
@@ -142,10 +149,12 @@ struct LossFinalizeArgs {
   const float* esum; float ecw; const float* psum; float pcw;
   float* terms; float* total;
   float grad_scale;   // the two small gradients leave multiplied by it (a trainer's loss scale / accumulation factor); terms and total do not
+  const float* scale_dev;   // optional device scalar (the dynamic loss scale, a power of two) that multiplies grad_scale
 };
-__global__ __launch_bounds__(256) void loss_finalize_kernel(const LossFinalizeArgs a) {
+__global__ __launch_bounds__(256) void loss_finalize_kernel(LossFinalizeArgs a) {
   __shared__ float scratch[4];
   const int tid = threadIdx.x;
+  if (a.scale_dev) a.grad_scale *= *a.scale_dev;
   const float w = a.spk_w_dev ? *a.spk_w_dev : a.spk_w;
   for (int i = tid; i < a.n_logits; i += 256) a.d_spk[i] = a.dlogits[i] * (w * a.grad_scale);
   float sq = 0.f;
@@ -193,8 +202,18 @@ int dx_mel_grad(const float* mel_pred, const float* mel_target, const float* ep,
                 float c_l1, float c_l2, float c_e, int e_per_total, float* dmel, int B, int M, int T, void* stream) {
   DX_REQUIRE(mel_pred && mel_target && lens && dmel && B > 0 && M > 0 && T > 0, "dx_mel_grad: bad arguments");
   DX_REQUIRE(c_e == 0.f || (ep && des), "dx_mel_grad: energy term needs ep and des");
-  hipLaunchKernelGGL(mel_grad_kernel, dim3(dx_cdiv(T, MEL_TT), B), dim3(256), 0, (hipStream_t)stream, mel_pred, mel_target, ep, des, lens, c_l1, c_l2, c_e, e_per_total, dmel, M, T);
+  hipLaunchKernelGGL(mel_grad_kernel, dim3(dx_cdiv(T, MEL_TT), B), dim3(256), 0, (hipStream_t)stream, mel_pred, mel_target, ep, des, lens, c_l1, c_l2, c_e, e_per_total, dmel, M, T, (const float*)nullptr);
   DX_LAUNCH_CHECK("dx_mel_grad");
+  return DX_OK;
+}
+
+// dx_mel_grad with c_l1, c_l2 and c_e multiplied by *scale_dev on the device (the dynamic loss scale: a captured graph re-reads it)
+int dx_mel_grad_dyn(const float* mel_pred, const float* mel_target, const float* ep, const float* des, const int* lens,
+                    float c_l1, float c_l2, float c_e, int e_per_total, const float* scale_dev, float* dmel, int B, int M, int T, void* stream) {
+  DX_REQUIRE(mel_pred && mel_target && lens && dmel && scale_dev && B > 0 && M > 0 && T > 0, "dx_mel_grad_dyn: null pointer or non-positive size");
+  DX_REQUIRE(c_e == 0.f || (ep && des), "dx_mel_grad_dyn: energy term needs ep and des");
+  hipLaunchKernelGGL(mel_grad_kernel, dim3(dx_cdiv(T, MEL_TT), B), dim3(256), 0, (hipStream_t)stream, mel_pred, mel_target, ep, des, lens, c_l1, c_l2, c_e, e_per_total, dmel, M, T, scale_dev);
+  DX_LAUNCH_CHECK("dx_mel_grad_dyn");
   return DX_OK;
 }
 
@@ -208,9 +227,24 @@ int dx_loss_finalize(const float* ce, const float* spk_w_dev, float spk_w, const
   DX_REQUIRE(l1sum && l2sum && lens && terms && total && B > 0 && M > 0, "dx_loss_finalize: bad arguments");
   DX_REQUIRE(n_logits == 0 || (dlogits && d_spk && ce), "dx_loss_finalize: speaker term needs ce, dlogits, d_spk");
   DX_REQUIRE(n_pm == 0 || (pm && d_pm), "dx_loss_finalize: post-multiplier term needs pm, d_pm");
-  LossFinalizeArgs a{ce, spk_w_dev, spk_w, dlogits, d_spk, n_logits, pm, d_pm, n_pm, pmw, l1sum, l2sum, lens, B, M, msw, esum, ecw, psum, pcw, terms, total, grad_scale};
+  LossFinalizeArgs a{ce, spk_w_dev, spk_w, dlogits, d_spk, n_logits, pm, d_pm, n_pm, pmw, l1sum, l2sum, lens, B, M, msw, esum, ecw, psum, pcw, terms, total, grad_scale, nullptr};
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   DX_LAUNCH_CHECK("dx_loss_finalize");
+  return DX_OK;
+}
+
+// dx_loss_finalize with grad_scale multiplied by *scale_dev on the device (d_spk, d_pm; the terms and the total stay unscaled)
+int dx_loss_finalize_dyn(const float* ce, const float* spk_w_dev, float spk_w, const float* dlogits, float* d_spk, int n_logits,
+                         const float* pm, float* d_pm, int n_pm, float pmw,
+                         const float* l1sum, const float* l2sum, const int* lens, int B, int M, float msw,
+                         const float* esum, float ecw, const float* psum, float pcw, float* terms, float* total, float grad_scale,
+                         const float* scale_dev, void* stream) {
+  DX_REQUIRE(l1sum && l2sum && lens && terms && total && scale_dev && B > 0 && M > 0, "dx_loss_finalize_dyn: null pointer or non-positive size");
+  DX_REQUIRE(n_logits == 0 || (dlogits && d_spk && ce), "dx_loss_finalize_dyn: speaker term needs ce, dlogits, d_spk");
+  DX_REQUIRE(n_pm == 0 || (pm && d_pm), "dx_loss_finalize_dyn: post-multiplier term needs pm, d_pm");
+  LossFinalizeArgs a{ce, spk_w_dev, spk_w, dlogits, d_spk, n_logits, pm, d_pm, n_pm, pmw, l1sum, l2sum, lens, B, M, msw, esum, ecw, psum, pcw, terms, total, grad_scale, scale_dev};
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  DX_LAUNCH_CHECK("dx_loss_finalize_dyn");
   return DX_OK;
 }
 
@@ -223,8 +257,17 @@ int dx_pitch_mse(const float* pp, int ldp, const float* gt, const int* lens, flo
 
 int dx_pitch_grad(const float* pp, int ldp, const float* gt, const int* lens, const float* sums, float scale, float* dpp, int ldd, int B, int T, void* stream) {
   DX_REQUIRE(pp && ldp >= 1 && gt && lens && sums && dpp && ldd >= 1 && B > 0 && T > 0, "dx_pitch_grad: bad arguments");
-  hipLaunchKernelGGL(pitch_grad_kernel, dim3(dx_cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, pp, ldp, gt, lens, sums, scale, dpp, ldd, T);
+  hipLaunchKernelGGL(pitch_grad_kernel, dim3(dx_cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, pp, ldp, gt, lens, sums, scale, dpp, ldd, T, (const float*)nullptr);
   DX_LAUNCH_CHECK("dx_pitch_grad");
+  return DX_OK;
+}
+
+// dx_pitch_grad with scale multiplied by *scale_dev on the device
+int dx_pitch_grad_dyn(const float* pp, int ldp, const float* gt, const int* lens, const float* sums, float scale, const float* scale_dev,
+                      float* dpp, int ldd, int B, int T, void* stream) {
+  DX_REQUIRE(pp && ldp >= 1 && gt && lens && sums && scale_dev && dpp && ldd >= 1 && B > 0 && T > 0, "dx_pitch_grad_dyn: null pointer or non-positive size");
+  hipLaunchKernelGGL(pitch_grad_kernel, dim3(dx_cdiv(T, 256), B), dim3(256), 0, (hipStream_t)stream, pp, ldp, gt, lens, sums, scale, dpp, ldd, T, scale_dev);
+  DX_LAUNCH_CHECK("dx_pitch_grad_dyn");
   return DX_OK;
 }
 

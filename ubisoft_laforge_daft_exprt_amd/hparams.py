@@ -13,6 +13,7 @@ own ``HyperParams`` instance, or an ``argparse.Namespace`` built from a
 from __future__ import annotations
 
 import copy
+import math
 
 N_SYMBOLS_ENGLISH = 76  # len(symbols_english), reference symbols.py:16-36 (pad '_' at index 0)
 
@@ -27,6 +28,37 @@ def _fft_stack(nb_blocks=4, hidden=128, heads=2, conv_channels=1024, kernel=3, a
         'conv_channels': conv_channels,
         'conv_dropout': conv_dropout,
     }
+
+
+def _power_of_two(x) -> bool:
+    x = float(x)
+    return x > 0.0 and math.isfinite(x) and math.frexp(x)[0] == 0.5
+
+
+def loss_scale_config(hparams) -> dict:
+    """The fp16 loss-scaling keys of any hparams object, with the defaults for those it lacks, checked (ValueError):
+    ``dynamic_loss_scale`` (False: the static scale ``loss_scale``), ``loss_scale`` (4096; the initial value in dynamic mode, where it
+    must be a power of two), ``loss_scale_growth_interval`` (2000), ``loss_scale_growth`` (2.0) and ``loss_scale_backoff`` (0.5) -- the
+    defaults of torch.amp.GradScaler, both powers of two -- and the bounds ``loss_scale_min`` (1.0) <= scale <= ``loss_scale_max``
+    (2**24).  Every scale the dynamic scaler can reach is then a power of two: multiplying by it is exact."""
+    g = lambda k, d: getattr(hparams, k, d)
+    cfg = {'dynamic': bool(g('dynamic_loss_scale', False)), 'loss_scale': float(g('loss_scale', 4096.0)),
+           'growth_interval': int(g('loss_scale_growth_interval', 2000)), 'growth': float(g('loss_scale_growth', 2.0)),
+           'backoff': float(g('loss_scale_backoff', 0.5)), 'min': float(g('loss_scale_min', 1.0)), 'max': float(g('loss_scale_max', 2.0 ** 24))}
+    if not (_power_of_two(cfg['growth']) and cfg['growth'] >= 1.0):
+        raise ValueError(f"loss_scale_growth must be a power of two >= 1, got {cfg['growth']!r}")
+    if not (_power_of_two(cfg['backoff']) and cfg['backoff'] <= 1.0):
+        raise ValueError(f"loss_scale_backoff must be a power of two <= 1, got {cfg['backoff']!r}")
+    if cfg['growth_interval'] < 1 or cfg['growth_interval'] != g('loss_scale_growth_interval', 2000):
+        raise ValueError(f"loss_scale_growth_interval must be a positive integer, got {g('loss_scale_growth_interval', 2000)!r}")
+    if not (0.0 < cfg['min'] <= cfg['max'] < math.inf):
+        raise ValueError(f"need 0 < loss_scale_min <= loss_scale_max < inf, got {cfg['min']!r}, {cfg['max']!r}")
+    if cfg['dynamic']:
+        if not _power_of_two(cfg['loss_scale']):
+            raise ValueError(f"dynamic_loss_scale: loss_scale must be a power of two, got {cfg['loss_scale']!r}")
+        if not cfg['min'] <= cfg['loss_scale'] <= cfg['max']:
+            raise ValueError(f"dynamic_loss_scale: loss_scale {cfg['loss_scale']!r} lies outside [loss_scale_min, loss_scale_max] = [{cfg['min']!r}, {cfg['max']!r}]")
+    return cfg
 
 
 class HyperParams:
@@ -59,6 +91,9 @@ class HyperParams:
         self.grad_clip_thresh = float('inf')
         self.initial_learning_rate = 1e-4
         self.max_learning_rate = 1e-3
+        # fp16 loss scaling (no reference counterpart) is read through loss_scale_config(), which holds the defaults: ``loss_scale``,
+        # ``dynamic_loss_scale``, ``loss_scale_growth_interval`` / ``_growth`` / ``_backoff`` / ``_min`` / ``_max``.  They are attributes only
+        # when given, so the ``config_params`` of a checkpoint are what they were unless a run sets one.
         # gradient reversal strength (model.py:51; not defined by the reference defaults)
         self.lambda_reversal = 1.0
         # module shapes (hparams.py:106-127)
@@ -71,11 +106,13 @@ class HyperParams:
         self.stats = {}
         for key, value in kwargs.items():
             setattr(self, key, value)
+        loss_scale_config(self)
 
     def clone(self, **overrides):
         new = copy.deepcopy(self)
         for key, value in overrides.items():
             setattr(new, key, value)
+        loss_scale_config(new)
         return new
 
     def without_dropout(self):

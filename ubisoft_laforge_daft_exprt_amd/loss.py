@@ -12,6 +12,7 @@ from torch import nn
 
 from . import ops
 from .functional import Lengths
+from .lazy import DeviceDict
 
 
 def pitch_predictor_shapes(n_mel_channels=80, hidden_dim=256, kernel_size=3):
@@ -90,9 +91,14 @@ class _LossFn(torch.autograd.Function):
         # ``grad_scale``: d(what the caller differentiates) / d(total), known up front (a trainer: loss scale / accumulation steps).  Every
         # gradient produced here is multiplied by it on the way out and ``backward`` then hands them on as they are: no ``total * c`` launch,
         # no three ``* g_total`` launches (one of them a 14 MB read-modify-write of the mel gradient).
-        gs = float(cfg.get('grad_scale', 1.0))
+        # A pair (host factor, device scalar) is a loss scale that lives on the device (a trainer's dynamic fp16 loss scale, a power of two):
+        # the host factor goes into the launch arguments, the three gradient launches multiply by the scalar themselves.
+        gs, sdev = cfg.get('grad_scale', 1.0), None
+        if isinstance(gs, tuple):
+            gs, sdev = gs
+        gs = float(gs)
         dmel = ops.mel_grad(mel_pred, mel_target, ep, des, lens.i32, gs * cfg['msw'] / (M * B), gs * cfg['msw'] / (M * B),
-                            gs * cfg['ecw'] if des is not None else 0.0, e_per_total=True) if need_grad else None
+                            gs * cfg['ecw'] if des is not None else 0.0, e_per_total=True, scale_dev=sdev) if need_grad else None
         psum = None
         if pitch_layers is not None and frames_pitch is not None and cfg['pcw'] > 0:
             prec = pitch_layers[0]['pack'].rt.precision                          # one value for the whole chain
@@ -102,7 +108,7 @@ class _LossFn(torch.autograd.Function):
                 pp, masks = ops.pitch_chain_fwd(mel_pred, pitch_layers, lens.i32, prec, arena=arena, rows_exist=lens.exist)
                 psum = ops.pitch_mse(pp, frames_pitch, lens.i32, arena=arena)
                 if need_grad:
-                    g = ops.pitch_grad(pp, frames_pitch, lens.i32, psum, gs * cfg['pcw'], out=ops._zeros(arena, B, T, device=dev))
+                    g = ops.pitch_grad(pp, frames_pitch, lens.i32, psum, gs * cfg['pcw'], out=ops._zeros(arena, B, T, device=dev), scale_dev=sdev)
                     ops.pitch_chain_bwd(g, masks, pitch_layers, lens.i32, prec, dmel, rows_exist=lens.exist)   # dmel: this function's own fresh tensor
             else:
                 # layer by layer (the exact-fp32 mode, other architectures): channels-last; gradient flows through it to the mel only
@@ -119,7 +125,7 @@ class _LossFn(torch.autograd.Function):
                 pp = ops.conv_gemm(x, last['pack'], last['b'], lens=lens.i32, halo=0, prec=prec, rows_exist=lens.exist)   # (B, T, 4): channel 0 = the prediction
                 psum = ops.pitch_mse(pp, frames_pitch, lens.i32, arena=arena)                          # (read and written in place: no slice copies)
                 if need_grad:
-                    g = ops.pitch_grad(pp, frames_pitch, lens.i32, psum, gs * cfg['pcw'], out=ops._zeros(arena, B, T, 4, device=dev))
+                    g = ops.pitch_grad(pp, frames_pitch, lens.i32, psum, gs * cfg['pcw'], out=ops._zeros(arena, B, T, 4, device=dev), scale_dev=sdev)
                     # each input-gradient GEMM applies the previous layer's BatchNorm scale and ReLU mask in its epilogue
                     for k in range(len(pitch_layers) - 1, 0, -1):
                         prev = pitch_layers[k - 1]
@@ -129,7 +135,7 @@ class _LossFn(torch.autograd.Function):
                     dmel = ops.transpose(d, add_to=dmel)                                   # dmel is this function's own fresh tensor
         # the seven terms, the total and the two small gradients: one launch (was ~30 one-element ATen launches)
         terms, total, d_spk, d_pm = ops.loss_finalize(ce, dlogits, cfg['spk_weight'], pm, cfg['pmw'], sums, lens.i32, M, cfg['msw'],
-                                                      esum, cfg['ecw'], psum, cfg['pcw'], grad_scale=gs)
+                                                      esum, cfg['ecw'], psum, cfg['pcw'], grad_scale=gs, scale_dev=sdev)
         if d_pm is not None:
             d_pm = d_pm.view_as(post_multipliers)
         if need_grad:
@@ -161,7 +167,8 @@ class DaftExprtLoss(nn.Module):
         self.pitch_consistency_weight = getattr(hparams, 'pitch_consistency_weight', 0.0)
         self.pitch_layers = None
         # None: ``backward`` multiplies by the incoming gradient, as autograd expects.  A float (set by trainer.Trainer): the loss's gradients
-        # are produced pre-multiplied by it and the trainer calls ``loss.backward(gradient=1)``
+        # are produced pre-multiplied by it and the trainer calls ``loss.backward(gradient=1)``.  A pair (float, one-element float32 device
+        # tensor): pre-multiplied by the float times the tensor's value at the time the launches run (the dynamic loss scale)
         self.grad_scale = None
         self.runtime = ops.Runtime(ops.DEFAULT.precision)     # this object's own execution state (see ops.Runtime)
         pp_path = getattr(hparams, 'pitch_predictor_path', '')
@@ -206,54 +213,10 @@ class DaftExprtLoss(nn.Module):
         return total, LossTerms(terms)
 
 
-class LossTerms(dict):
+class LossTerms(DeviceDict):
     """The reference's ``individual_loss`` dict of 7 floats (loss.py:149-157).  The values live in one device tensor and are
     fetched with a single host transfer on FIRST ACCESS, so a training loop that only logs every n-th step never stalls
     the stream between forward and backward (the reference does seven ``.item()`` syncs per step)."""
 
     KEYS = ('speaker_loss', 'speaker_ce_raw', 'post_mult_loss', 'mel_spec_l1_loss', 'mel_spec_l2_loss',
             'energy_consistency_loss', 'pitch_consistency_loss')
-
-    def __init__(self, device_terms):
-        super().__init__()
-        self._device_terms = device_terms
-
-    def _fetch(self):
-        if self._device_terms is not None:
-            values = self._device_terms.tolist()
-            self._device_terms = None
-            super().update(zip(self.KEYS, values))
-
-    def __getitem__(self, k):
-        self._fetch()
-        return super().__getitem__(k)
-
-    def __iter__(self):
-        self._fetch()
-        return super().__iter__()
-
-    def __len__(self):
-        return len(self.KEYS)
-
-    def __contains__(self, k):
-        return k in self.KEYS
-
-    def keys(self):
-        self._fetch()
-        return super().keys()
-
-    def items(self):
-        self._fetch()
-        return super().items()
-
-    def values(self):
-        self._fetch()
-        return super().values()
-
-    def get(self, k, default=None):
-        self._fetch()
-        return super().get(k, default)
-
-    def __repr__(self):
-        self._fetch()
-        return super().__repr__()

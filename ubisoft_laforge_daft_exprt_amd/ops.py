@@ -818,25 +818,42 @@ def energy_diff(ep, et, lens, arena=None, rows_exist=None):
     return des, esum
 
 
-def mel_grad(mel_pred, mel_target, ep, des, lens, c_l1, c_l2, c_e, e_per_total=False):
+def _scale_dev(t):
+    """The dynamic loss scale: ONE float32 on the GPU (trainer.Trainer hands the loss a view of its scaler state)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+        raise TypeError('the device-side loss scale must be a one-element float32 tensor on the GPU')
+    return t
+
+
+def mel_grad(mel_pred, mel_target, ep, des, lens, c_l1, c_l2, c_e, e_per_total=False, scale_dev=None):
+    """``scale_dev`` (device float scalar, a power of two): the three coefficients are multiplied by it on the device."""
     B, M, T = mel_pred.shape
     dmel = torch.empty_like(mel_pred)
+    if scale_dev is not None:
+        lib().dx_mel_grad_dyn(_p(mel_pred), _p(mel_target), _p(ep), _p(des), _p(lens), float(c_l1), float(c_l2), float(c_e), int(e_per_total),
+                              _p(_scale_dev(scale_dev)), _p(dmel), B, M, T, _stream())
+        return dmel
     lib().dx_mel_grad(_p(mel_pred), _p(mel_target), _p(ep), _p(des), _p(lens), float(c_l1), float(c_l2), float(c_e), int(e_per_total), _p(dmel),
                       B, M, T, _stream())
     return dmel
 
 
-def loss_finalize(ce, dlogits, spk_w, pm, pmw, sums, lens, M, msw, esum, ecw, psum, pcw, grad_scale=1.0):
-    """-> (terms[7], total[1], d_spk or None, d_pm or None); ``spk_w``: python float or device scalar tensor"""
+def loss_finalize(ce, dlogits, spk_w, pm, pmw, sums, lens, M, msw, esum, ecw, psum, pcw, grad_scale=1.0, scale_dev=None):
+    """-> (terms[7], total[1], d_spk or None, d_pm or None); ``spk_w``: python float or device scalar tensor;
+    ``scale_dev`` (device float scalar, a power of two): multiplies ``grad_scale`` on the device"""
     dev = sums.device
     B = sums.shape[1]
     out = torch.empty(8, dtype=torch.float32, device=dev)
     d_spk = torch.empty_like(dlogits) if dlogits is not None else None
     d_pm = torch.empty_like(pm) if pm is not None else None
     w_dev = spk_w if torch.is_tensor(spk_w) else None
-    lib().dx_loss_finalize(_p(ce), _p(w_dev), 0.0 if w_dev is not None else float(spk_w), _p(dlogits), _p(d_spk), 0 if dlogits is None else dlogits.numel(),
-                           _p(pm), _p(d_pm), 0 if pm is None else pm.numel(), float(pmw), _p(sums[0]), _p(sums[1]), _p(lens), B, M, float(msw),
-                           _p(esum), float(ecw), _p(psum), float(pcw), _p(out), _p(out[7:]), float(grad_scale), _stream())
+    args = (_p(ce), _p(w_dev), 0.0 if w_dev is not None else float(spk_w), _p(dlogits), _p(d_spk), 0 if dlogits is None else dlogits.numel(),
+            _p(pm), _p(d_pm), 0 if pm is None else pm.numel(), float(pmw), _p(sums[0]), _p(sums[1]), _p(lens), B, M, float(msw),
+            _p(esum), float(ecw), _p(psum), float(pcw), _p(out), _p(out[7:]), float(grad_scale))
+    if scale_dev is not None:
+        lib().dx_loss_finalize_dyn(*args, _p(_scale_dev(scale_dev)), _stream())
+    else:
+        lib().dx_loss_finalize(*args, _stream())
     return out[:7], out[7], d_spk, d_pm
 
 
@@ -853,10 +870,15 @@ def pitch_mse(pp, gt, lens, arena=None):
     return sums
 
 
-def pitch_grad(pp, gt, lens, sums, scale, out=None):
-    """``out``: optional (B, T, C) tensor whose channel 0 receives the gradient (the other channels are left as they are)."""
+def pitch_grad(pp, gt, lens, sums, scale, out=None, scale_dev=None):
+    """``out``: optional (B, T, C) tensor whose channel 0 receives the gradient (the other channels are left as they are).
+    ``scale_dev`` (device float scalar, a power of two): multiplies ``scale`` on the device."""
     B, T = gt.shape
     dpp = out if out is not None else torch.empty(B, T, dtype=torch.float32, device=gt.device)
+    if scale_dev is not None:
+        lib().dx_pitch_grad_dyn(_p(pp), _frame_stride(pp), _p(gt), _p(lens), _p(sums), float(scale), _p(_scale_dev(scale_dev)), _p(dpp),
+                                _frame_stride(dpp), B, T, _stream())
+        return dpp
     lib().dx_pitch_grad(_p(pp), _frame_stride(pp), _p(gt), _p(lens), _p(sums), float(scale), _p(dpp), _frame_stride(dpp), B, T, _stream())
     return dpp
 

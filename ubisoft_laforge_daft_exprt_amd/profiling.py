@@ -147,13 +147,15 @@ def price(name, a, geom: Geometry):
         return 'upsample_bwd (dsigma + dxs)', 'hbm', None, B * T * D * 4 + B * L * T * 4 + 2 * B * L * D * 4 + 3 * B * L * 4
     if name in ('dx_upsample_prep', 'dx_upsample_sym_bwd'):
         return name[3:], 'hbm', None, 2 * a['B'] * a['L'] * a['D'] * 4 + 6 * a['B'] * a['L'] * 4
-    if name == 'dx_adam_step':
-        return 'adam_kernel', 'hbm', None, a['n'] * 28
+    if name in ('dx_adam_step', 'dx_adam_step_dyn'):
+        return ('adam_kernel' if name == 'dx_adam_step' else 'adam_dyn_kernel'), 'hbm', None, a['n'] * 28
+    if name == 'dx_scaler_update':                       # one lane: the eight state words read and written, the squared norm read
+        return 'scaler_update', 'hbm', None, 2 * 8 * 4 + 4
     if name == 'dx_sumsq':
         return 'sumsq_kernel', 'hbm', None, a['n'] * 4
     if name == 'dx_mel_stats':
         return 'mel_stats', 'hbm', None, 2 * a['B'] * a['M'] * a['T'] * 4
-    if name == 'dx_mel_grad':
+    if name in ('dx_mel_grad', 'dx_mel_grad_dyn'):
         return 'mel_grad', 'hbm', None, 3 * a['B'] * a['M'] * a['T'] * 4
     if name == 'dx_add_pos':
         rows = geom.rows(a['B'], a['N'])

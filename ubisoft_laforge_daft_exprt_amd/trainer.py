@@ -34,6 +34,19 @@ MI355X-specific structure of one update (``use_graphs=True``, the default):
     forward and backward, that rows beyond them do not exist.  With dropout off the step computes what the exact-shape step
     computes ("logical rows vs stride"); dropout masks are drawn over the bucket's row stride instead.
 
+fp16 operand mode (no reference counterpart: the reference trains in fp32): gradients that live in 16-bit tensors would underflow, so the
+backward runs on loss * scale and the fused Adam multiplies by 1 / scale.  A non-finite gradient norm SKIPS the update -- parameters and
+both moments untouched -- where the reference steps anyway (train.py:443-450); that is the one deliberate deviation.  Two modes:
+  * static (the default): ``hparams.loss_scale`` (4096) for the whole run, a host value in the launch arguments.  ``skipped_steps()``
+    counts the skipped updates (a host sync); nothing lowers the scale, and the bias-correction step counts skipped updates too.
+  * dynamic (``hparams.dynamic_loss_scale = True``; active only when the model runs in fp16, inert in every other precision): the
+    scale is a power of two in device memory (optim.LossScaler) with torch.amp.GradScaler's rules -- halved (``loss_scale_backoff``)
+    on a skipped update, doubled (``loss_scale_growth``) after ``loss_scale_growth_interval`` applied ones in a row, kept within
+    [``loss_scale_min``, ``loss_scale_max``].  The captured graphs read it through a pointer and the optimiser's launch sequence
+    (norm, decision, Adam) updates it: no host sync, no re-capture when it changes.  The bias-correction step is the number of
+    APPLIED updates.  ``iteration`` -- and with it the LR schedule and the adversarial warm-up -- advances on a skipped update too,
+    as it does when a GradScaler is used with a scheduler.  ``scaler_state()`` reports it, ``checkpoint()`` stores it (``loss_scaler``).
+
 Like the reference, a NaN loss does not stop the update (train.py:445-450 only skips LOGGING); ``nan_steps`` counts them.
 The iteration counter starts at 1 (train.py:286) and the learning rate of step ``i`` is ``update_learning_rate(hparams, i)``.
 ``save_checkpoint`` / ``load_checkpoint`` use the reference's dict layout (train.py:63-145) including the torch.optim.Adam
@@ -50,7 +63,8 @@ from . import ops
 from .ddp import GradientReducer
 from .functional import Lengths
 from .loss import LossTerms
-from .optim import FusedAdam, update_learning_rate
+from .hparams import loss_scale_config
+from .optim import FusedAdam, LossScaler, update_learning_rate
 
 
 def group_of(name: str, levels: int = 3) -> int:
@@ -130,7 +144,10 @@ class Trainer:
         # backward runs on loss * loss_scale and the fused Adam multiplies by 1 / loss_scale (static scale; bf16 needs none).
         # An overflow (non-finite gradient norm) SKIPS the update on every rank (the norm is computed after the all-reduce, so all
         # ranks see the same value): ``skipped_steps()`` counts them, ``hparams.loss_scale`` lowers the scale.
-        self._fp16_loss_scale = float(getattr(hparams, 'loss_scale', 4096.0))
+        # ``hparams.dynamic_loss_scale``: the scale lives on the device and follows GradScaler's rules (module docstring); only in fp16.
+        scale_cfg = loss_scale_config(hparams)
+        self._fp16_loss_scale = scale_cfg['loss_scale']
+        self.scaler = LossScaler(scale_cfg, self.device) if scale_cfg['dynamic'] and model.runtime.precision == 'fp16' else None
         self.graphs = {}
         self.val_graphs = {}
         self._conditioner_generation = getattr(conditioner, 'generation', None)
@@ -140,7 +157,7 @@ class Trainer:
         if model.runtime.seed_offset is None:
             model.runtime.seed_offset = torch.zeros((), dtype=torch.int64, device=self.device)
         self.optimizer = FusedAdam(self.reducer, lr=hparams.initial_learning_rate, betas=hparams.betas, eps=hparams.epsilon,
-                                   weight_decay=hparams.weight_decay, grad_clip_thresh=hparams.grad_clip_thresh)
+                                   weight_decay=hparams.weight_decay, grad_clip_thresh=hparams.grad_clip_thresh, scaler=self.scaler)
         self.accumulation_steps = int(getattr(hparams, 'accumulation_steps', 1))
         self.iteration = 1
         self.learning_rate = update_learning_rate(hparams, self.iteration)
@@ -151,11 +168,23 @@ class Trainer:
 
     @property
     def loss_scale(self):
+        """The scale the next backward runs on (dynamic mode: its current value, one host transfer); 1 outside fp16."""
+        if self.scaler is not None:
+            return self.scaler.state()['scale']
         return self._fp16_loss_scale if self.model.runtime.precision == 'fp16' else 1.0
 
     def skipped_steps(self) -> int:
         """Updates the fused Adam skipped because the gradient norm was not finite (one host sync)."""
         return self.optimizer.skipped_steps()
+
+    def scaler_state(self):
+        """``{scale, applied, good_steps, skipped}``: the scale of the next backward, the updates applied so far (the bias-correction
+        step), the applied updates in a row since the scale last changed, the updates skipped so far.  Dynamic mode: a snapshot of the
+        device state taken now, fetched with a single transfer on first access (optim.ScalerState).  Otherwise the static view (scale
+        ``loss_scale``, every optimiser call counted as applied, the skipped count read from the device)."""
+        if self.scaler is not None:
+            return self.scaler.state()
+        return {'scale': self.loss_scale, 'applied': self.optimizer.step_count, 'good_steps': 0, 'skipped': self.optimizer.skipped_steps()}
 
     def exchange_plan(self):
         """Per gradient-exchange group: its bytes and the point of the step at which its all-reduces are launched.  The LAST group is
@@ -195,7 +224,8 @@ class Trainer:
         rt.backward_split, rt.cut_levels = [], self.cut_levels
         tot, terms = None, []
         # d(what is differentiated) / d(loss) = loss scale / accumulation steps is folded into the loss kernels' own gradient outputs
-        self.criterion.grad_scale = self.loss_scale / k
+        # (dynamic mode: the host part 1 / k, and the scale as the device scalar the loss launches multiply by)
+        self.criterion.grad_scale = (1.0 / k, self.scaler.scale) if self.scaler is not None else self.loss_scale / k
         try:
             for inputs, targets in parsed:
                 loss, indiv = self._forward_loss(inputs, targets, iteration)
@@ -343,7 +373,10 @@ class Trainer:
             for run in rest:
                 run()
         red.finish()
-        grad_norm = self.optimizer.step(lr=self.learning_rate, grad_scale=1.0 / self.loss_scale)
+        if self.scaler is not None:                               # 1 / scale is read from the scaler state on the device
+            grad_norm = self.optimizer.step(lr=self.learning_rate)
+        else:
+            grad_norm = self.optimizer.step(lr=self.learning_rate, grad_scale=1.0 / self.loss_scale)
         self.last_learning_rate = self.learning_rate
         self.iteration += 1
         self.learning_rate = update_learning_rate(self.hparams, self.iteration)
@@ -419,9 +452,12 @@ class Trainer:
     # -- checkpoints: train.py:63-85 / :88-145 ---------------------------------------------------------------------------
     def checkpoint(self):
         cfg = {k: v for k, v in self.hparams.__dict__.items()}
-        return {'iteration': self.iteration - 1, 'learning_rate': self.last_learning_rate, 'best_val_loss': self.best_val_loss,
-                'state_dict': {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-                'optimizer': self.optimizer.state_dict(), 'config_params': cfg}
+        ck = {'iteration': self.iteration - 1, 'learning_rate': self.last_learning_rate, 'best_val_loss': self.best_val_loss,
+              'state_dict': {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+              'optimizer': self.optimizer.state_dict(), 'config_params': cfg}
+        if self.scaler is not None:                               # beside the reference's keys: four plain numbers
+            ck['loss_scaler'] = dict(self.scaler.state().items())
+        return ck
 
     def save_checkpoint(self, filepath):
         os.makedirs(os.path.dirname(os.path.abspath(filepath)), exist_ok=True)
@@ -437,6 +473,10 @@ class Trainer:
         opt = checkpoint.get('optimizer')
         if opt is not None and len(opt['param_groups']) == len(self.optimizer.param_groups):
             self.optimizer.load_state_dict(opt)                          # else: keep the blank optimiser (train.py:127-133)
+        if self.scaler is not None:
+            # a checkpoint without the entry (an older one, the reference's own): the scale starts from hparams.loss_scale, the
+            # bias-correction step from the optimiser state
+            self.scaler.load(checkpoint.get('loss_scaler') or {'applied': self.optimizer.step_count})
         self.iteration = int(checkpoint['iteration']) + 1                # "next iteration is iteration + 1" (train.py:289)
         self.learning_rate = update_learning_rate(self.hparams, self.iteration)   # recomputed from the schedule (train.py:294)
         self.best_val_loss = checkpoint.get('best_val_loss', float('inf'))
