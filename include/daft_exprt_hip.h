@@ -423,6 +423,48 @@ int dx_prosody_condition(const float* energy, const float* pitch, const long* du
  * audio [B][S] fp32 -> pcm [B][S] int16, 0 at or past sample_lengths[b] (device int32 [B]); both 16-byte aligned, B <= 65535. */
 int dx_pcm16(const float* audio, const int* sample_lengths, short* pcm, int B, long S, void* stream);
 
+/* ---- HiFi-GAN discriminators, forward (reference vocoder/discriminators.py; csrc/dx_disc.hip) -------------------------------------
+ * Activations are fp32, channels-last.  A "row" is one independent 1-D signal: a batch row of the Multi-Scale Discriminator
+ * ([B][T][C]: rdiv = 1) or one column of the Multi-Period Discriminator's period-folded tensor ([B][H][p][C]: rdiv = p, row = b p + w).
+ * Element (row, n, c) is at X[(row / rdiv) sxb + (row % rdiv) sxr + n sxn + c].  There are no lengths: every row has N positions, as
+ * in the reference.  Real and generated audio are rows of one batch.  No atomics: every output element and every loss is summed in
+ * an order fixed by the shapes alone, so two runs, and a batch row and that row alone, are bitwise equal.  bf16 = 0: exact f32
+ * (v_mfma_f32_16x16x4_f32), 1: bf16 operands (v_mfma_f32_16x16x32_bf16), fp32 accumulate and storage. */
+/* bytes of the pack dx_disc_pack writes for a folded weight (Cout, Cin_g, taps), Cin_g = input channels per group */
+int dx_disc_pack_size(int Cout, int Cin_g, int taps, int bf16, long* bytes);
+/* folded fp32 weight (Cout, Cin_g, taps) of a (grouped) Conv1d, or of a Conv2d with a (taps, 1) kernel, -> dx_disc_conv's operand:
+ * [column block][64-channel chunk][k step][lane] MFMA fragments, k = tap * chunk width + channel, zero-padded to the k step. */
+int dx_disc_pack(const float* W, void* Wp, int Cout, int Cin_g, int taps, int bf16, void* stream);
+/* Y = lrelu_0.1?(conv(X) + bias): DiscriminatorP.convs[1:] (discriminators.py:39-46: (5, 1) kernels, stride (3, 1) or 1, along H for
+ * each of the p columns) and DiscriminatorS.convs[1:] (:106-111: k = 41 grouped with strides 1, 2, 4, and the dense k = 5).  N input
+ * positions per row -> (N + 2 pad - taps) / stride + 1 output positions; Y is addressed like X with (syb, syr, syn) and Cout
+ * channels.  taps <= 41, stride <= 4, pad <= 20; channels per group: in 8, 16, 32 or a multiple of 64, out 16, 32 or a multiple of
+ * 64; Cout % 64 == 0.  X 16-byte aligned with strides % 4 == 0; Y must not alias X. */
+int dx_disc_conv(const float* X, long sxb, long sxr, long sxn, const void* Wp, const float* bias, float* Y, long syb, long syr, long syn,
+                 int rows, int rdiv, int N, int Cin, int Cout, int groups, int taps, int stride, int pad, int act, int bf16,
+                 void* stream);
+/* The Cin = 1 first layers, fp32 FMAs (DiscriminatorP.forward :52-60 with convs[0], p > 1; DiscriminatorS.convs[0] :105, p = 1):
+ * x [B][sxb] with T samples per row is read through the period view x[b][h p + w], h < H = ceil(T / p); samples at or past T are the
+ * reference's right reflect padding (F.pad(x, (0, p - T % p), 'reflect'): index 2 (T - 1) - i), applied while reading.
+ * Y [B][Hout][p][Cout] = lrelu_0.1(conv along h + bias), Hout = (H + 2 pad - taps) / stride + 1; W is the folded (Cout, 1, taps). */
+int dx_disc_first(const float* x, long sxb, int T, const float* W, const float* bias, float* Y, int B, int p, int Cout, int taps,
+                  int stride, int pad, void* stream);
+/* The Cout = 1 last layers (conv_post, :48 and :113; no activation), fp32: Y[(row / rdiv) syb + (row % rdiv) syr + n syn] =
+ * sum_t sum_c X(row, n - (taps - 1) / 2 + t, c) W[c][t] + bias[0]; X addressed as in dx_disc_conv, W the folded (1, C, taps). */
+int dx_disc_post(const float* X, long sxb, long sxr, long sxn, const float* W, const float* bias, float* Y, long syb, long syr, long syn,
+                 int rows, int rdiv, int N, int C, int taps, void* stream);
+/* MultiScaleDiscriminator.meanpools (:139-142): AvgPool1d(4, 2, padding = 2), padding counted; x [R][T] -> y [R][T / 2 + 1] */
+int dx_disc_pool(const float* x, float* y, int R, int T, void* stream);
+/* floats of the partial-sum workspace dx_disc_losses needs for n entries of at most max_count elements */
+int dx_disc_losses_workspace(long max_count, int n, long* floats);
+/* discriminator_loss, generator_loss and feature_loss (:163-194) in one call, no host synchronisation.  table: n device entries of
+ * {const float* r, const float* g, long count, long code}, code = kind + 2 set; kind 0 is a score pair (dr, dg), kind 1 a feature-map
+ * pair.  out[3 n_sets + 3 e + {0, 1, 2}] = entry e's mean (1 - dr)^2, mean dg^2, mean (1 - dg)^2 (kind 0) or mean |r - g|, 0, 0
+ * (kind 1); out[3 s + {0, 1, 2}] = set s's discriminator_loss (sum of r_loss + g_loss), generator_loss and feature_loss (x 2)
+ * totals, the entries added in table order.  Each entry is summed in chunks of 16384 elements, the chunk sums then in a fixed order.
+ * max_count: the largest count, total_count: their sum. */
+int dx_disc_losses(const void* table, int n, int n_sets, long max_count, long total_count, float* partial, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,73 @@
+"""HiFi-GAN discriminators at the fine-tuning shape: B = 16 segments of 8192 samples, real and generated, synthetic weights.
+One JSON line: the time of ``HiFiGanDiscriminators.losses`` (both discriminators on both inputs + the six losses; f32 and bf16), of the
+plain-torch restatement tests/disc_torch.py on the same GPU (fp32, and bf16 tensors), the FLOPs of one pass recomputed by
+profiling.price() from the launches themselves, and per-kernel times with TFLOP/s (MFMA kernels) or GB/s (the others).
+
+Times are host clocks around work that ends in a device synchronise, after warm-up; the per-kernel figures bracket each launch with
+events (profiling.py), in a pass of their own.  Needs a GPU: there is no fallback.
+
+    python tools/bench_discriminators.py
+"""
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import torch  # noqa: E402
+
+from tests import disc_helpers as dh  # noqa: E402
+from tests import disc_torch  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd import _lib, discriminators as disc, profiling  # noqa: E402
+
+B, T = 16, 8192
+
+
+def timed(fn, n=10, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n
+
+
+def main():
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_discriminators needs a GPU')
+    dev = 'cuda'
+    y, y_hat = (t.to(dev) for t in dh.make_inputs(T, 9, batch=B))
+    states = dh.state_dicts()
+    out = {'workload': f'B={B} segments of {T} samples, real + generated'}
+    geom = profiling.Geometry([[1]])
+    with torch.no_grad():
+        for prec in ('f32', 'bf16'):
+            D = disc.HiFiGanDiscriminators(states, device=dev, precision=prec)
+            t = timed(lambda: D.losses(y, y_hat))
+            recs = []
+            old = _lib.set_timer(recs)
+            D.losses(y, y_hat)
+            _lib.set_timer(old)
+            torch.cuda.synchronize()
+            flops = sum(profiling.price(name, args, geom)[2] or 0.0 for name, args, _, _ in recs)
+            out[f'hip_{prec}'] = {'s': round(t, 6), 'launches': len(recs), 'tflop_per_pass': round(flops / 1e12, 4),
+                                  'tflops': round(flops / t / 1e12, 2)}
+            out[f'profile_{prec}'] = profiling.summarize(recs, geom, prec)
+        folded = {'mpd': {k: (w.reshape(w.shape[0], w.shape[1], w.shape[2]).to(dev), b.to(dev)) for k, (w, b) in disc.fold_state_dict(states['mpd']).items()},
+                  'msd': {k: (w.to(dev), b.to(dev)) for k, (w, b) in disc.fold_state_dict(states['msd']).items()}}
+        for tag, dtype in (('torch_fp32', torch.float32), ('torch_bf16', torch.bfloat16)):
+            yy, yh = y.to(dtype), y_hat.to(dtype)
+
+            def run():
+                return disc_torch.six_losses(disc_torch.mpd(yy, yh, folded['mpd'], dtype), disc_torch.msd(yy, yh, folded['msd'], dtype))
+            out[tag] = {'s': round(timed(run, n=5, warm=2), 6)}
+        out['hip_f32_over_torch_fp32'] = round(out['torch_fp32']['s'] / out['hip_f32']['s'], 2)
+        out['hip_bf16_over_torch_bf16'] = round(out['torch_bf16']['s'] / out['hip_bf16']['s'], 2)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

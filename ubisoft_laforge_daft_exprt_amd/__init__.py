@@ -12,3 +12,5 @@ from .ops import set_precision, get_precision, Runtime  # noqa: F401
 from .vocoder import HiFiGANGenerator, HiFiGanVocoder, load_hifigan_vocoder  # noqa: F401
 from .mel import MelSpectrogram, mel_filter_bank, mel_spectrogram, mel_spectrogram_HiFi  # noqa: F401
 from .speech import SpeechSynthesizer, condition_external_prosody, symbol_prosody, to_pcm16  # noqa: F401
+from .discriminators import (DiscriminatorP, DiscriminatorS, HiFiGanDiscriminators, MultiPeriodDiscriminator,  # noqa: F401
+                             MultiScaleDiscriminator, discriminator_loss, feature_loss, generator_loss)

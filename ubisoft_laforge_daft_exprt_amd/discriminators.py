@@ -1,0 +1,477 @@
+"""HiFi-GAN discriminators on gfx950, forward only (reference src/daft_exprt/vocoder/discriminators.py).
+
+``MultiPeriodDiscriminator`` / ``DiscriminatorP`` and ``MultiScaleDiscriminator`` / ``DiscriminatorS`` own exactly the reference's
+state-dict keys and shapes (90 and 80 tensors), so ``load_state_dict(strict=True)`` takes the ``['mpd']`` / ``['msd']`` entries of a
+reference ``do_*`` checkpoint.  ``forward(y, y_hat)`` returns ``(y_d_rs, y_d_gs, fmap_rs, fmap_gs)`` as the reference does; every layer
+runs in csrc/dx_disc.hip (there is no PyTorch fallback and no CPU path), real and generated audio as one batch of 2B rows, one launch
+per layer.  The feature maps are permuted VIEWS of the kernels' channels-last buffers ((B, C, H, p) and (B, C, N)), not copies.
+
+Weight folding, once and lazily (``refresh_weights()`` drops the folded copies; ``load_state_dict`` calls it):
+  * weight norm (``weight_g`` / ``weight_v``): ``torch._weight_norm(v, g, 0)``;
+  * spectral norm (the first MSD sub-discriminator: ``weight_orig`` / ``weight_u`` / ``weight_v``; told apart by ``weight_orig``):
+    EVAL-mode semantics, ``W = weight_orig / (u . (W_mat v))`` with the stored ``u`` and ``v``.  The reference's train-mode power
+    iteration is NOT done and ``.train()`` does not change the forward.
+
+There is no backward: with grad mode on, an input (or a parameter of the module) that requires grad raises instead of returning a
+silently detached result.  The parameters are created with ``requires_grad=False``.
+
+``discriminator_loss``, ``generator_loss`` and ``feature_loss`` keep the reference signatures and run through ``dx_disc_losses``.
+The one deviation: the per-sub-discriminator entries are 0-d device tensors where the reference returns ``.item()`` floats (no host
+synchronisation happens here).  ``HiFiGanDiscriminators.losses`` computes the six totals of finetune_hifigan.py:218-241 in one call.
+"""
+from __future__ import annotations
+
+import os
+
+import torch
+from torch import nn
+
+from ._lib import lib
+
+LRELU_SLOPE = 0.1
+PERIODS = (2, 3, 5, 7, 11)
+PRECISIONS = {'f32': 0, 'bf16': 1}
+# (Cin, Cout, taps, stride, groups, padding)
+MPD_LAYERS = ((1, 32, 5, 3, 1, 2), (32, 128, 5, 3, 1, 2), (128, 512, 5, 3, 1, 2), (512, 1024, 5, 3, 1, 2), (1024, 1024, 5, 1, 1, 2))
+MSD_LAYERS = ((1, 128, 15, 1, 1, 7), (128, 128, 41, 2, 4, 20), (128, 256, 41, 2, 16, 20), (256, 512, 41, 4, 16, 20),
+              (512, 1024, 41, 4, 16, 20), (1024, 1024, 41, 1, 16, 20), (1024, 1024, 5, 1, 1, 2))
+POST = (1024, 1, 3, 1, 1, 1)
+LOSS_NAMES = ('loss_disc_f', 'loss_gen_f', 'loss_fm_f', 'loss_disc_s', 'loss_gen_s', 'loss_fm_s')
+
+
+def conv_out(n, taps, stride, pad):
+    return (n + 2 * pad - taps) // stride + 1
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _frozen(t):
+    return nn.Parameter(t, requires_grad=False)
+
+
+class _WNConv(nn.Module):
+    """Parameters of one weight-normed convolution, named as torch.nn.utils.weight_norm names them."""
+
+    def __init__(self, w_shape):
+        super().__init__()
+        self.bias = _frozen(torch.zeros(w_shape[0]))
+        self.weight_g = _frozen(torch.ones(w_shape[0], *([1] * (len(w_shape) - 1))))
+        self.weight_v = _frozen(torch.zeros(*w_shape))
+
+
+class _SNConv(nn.Module):
+    """Parameters and buffers of one spectral-normed convolution, named as torch.nn.utils.spectral_norm names them."""
+
+    def __init__(self, w_shape):
+        super().__init__()
+        cols = 1
+        for s in w_shape[1:]:
+            cols *= s
+        self.bias = _frozen(torch.zeros(w_shape[0]))
+        self.weight_orig = _frozen(torch.zeros(*w_shape))
+        self.register_buffer('weight_u', torch.zeros(w_shape[0]))
+        self.register_buffer('weight_v', torch.zeros(cols))
+
+
+def fold_weight(state: dict, name: str) -> torch.Tensor:
+    """The convolution weight of layer ``name`` of a discriminator state dict: folded weight norm, or eval-mode spectral norm."""
+    if name + '.weight_orig' in state:
+        w = state[name + '.weight_orig'].float()
+        u, v = state[name + '.weight_u'].float(), state[name + '.weight_v'].float()
+        sigma = torch.dot(u, torch.mv(w.reshape(w.shape[0], -1), v))
+        return w / sigma
+    if name + '.weight_v' in state and name + '.weight_g' in state:
+        return torch._weight_norm(state[name + '.weight_v'].float(), state[name + '.weight_g'].float(), 0)
+    raise KeyError(f'discriminator state dict has no weight for {name!r}')
+
+
+def layer_names(state: dict):
+    return [k[:-len('.bias')] for k in state if k.endswith('.bias')]
+
+
+def fold_state_dict(state: dict) -> dict:
+    """-> {layer: (weight, bias)}, fp32, on the tensors' own device."""
+    return {n: (fold_weight(state, n).detach().contiguous(), state[n + '.bias'].float().detach().contiguous()) for n in layer_names(state)}
+
+
+def _check_inputs(*xs):
+    x = xs[0]
+    for t in xs:
+        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[1] != 1 or t.shape[2] < 1 or t.shape[0] < 1:
+            raise ValueError(f'the discriminators take (B, 1, T) waveforms, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}')
+        if t.shape != x.shape or t.device != x.device:
+            raise ValueError(f'y and y_hat must agree in shape and device, got {tuple(x.shape)} on {x.device} and {tuple(t.shape)} on {t.device}')
+        if t.dtype != torch.float32:
+            raise ValueError(f'the discriminators take fp32 waveforms, got {t.dtype}')
+
+
+def _check_reflect(T, periods):
+    for p in periods:
+        if T % p and p - T % p >= T:
+            raise ValueError(f'period {p}: the reflect padding ({p - T % p} samples) must be shorter than the signal ({T} samples)')
+
+
+def _check_run(module, *xs):
+    if torch.is_grad_enabled() and (any(t.requires_grad for t in xs) or any(q.requires_grad for q in module.parameters())):
+        raise RuntimeError('the discriminators are forward only: their backward is not built, and an input or parameter requires grad '
+                           '(run under torch.no_grad() or detach the input)')
+    if xs[0].device.type != 'cuda':
+        raise RuntimeError('the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels); there is no CPU path')
+
+
+class _Arena:
+    """Hands out the same buffers, in the same order, on every pass (``reset()`` starts a pass)."""
+
+    def __init__(self):
+        self.bufs, self.i = [], 0
+
+    def reset(self):
+        self.i = 0
+
+    def __call__(self, shape, device):
+        if self.i == len(self.bufs):
+            self.bufs.append(torch.empty(shape, dtype=torch.float32, device=device))
+        t = self.bufs[self.i]
+        assert tuple(t.shape) == tuple(shape)
+        self.i += 1
+        return t
+
+
+def _fresh(shape, device):
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+class _SubDiscriminator(nn.Module):
+    LAYERS = ()
+
+    def _init_layers(self, conv_cls, two_d, precision):
+        if precision not in PRECISIONS:
+            raise ValueError(f'precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
+        self.precision = precision
+        tail = (1,) if two_d else ()
+        self.convs = nn.ModuleList([conv_cls((cout, cin // g, k) + tail) for cin, cout, k, _, g, _ in self.LAYERS])
+        self.conv_post = conv_cls((POST[1], POST[0], POST[2]) + tail)
+        self._packs = None
+
+    def refresh_weights(self):
+        """Drop the folded, packed device weights: the next forward folds the current parameters again."""
+        self._packs = None
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        self.refresh_weights()
+        return out
+
+    def _apply(self, fn, *args, **kwargs):
+        self._packs = None                      # .to() / .cuda(): the packs follow the parameters
+        return super()._apply(fn, *args, **kwargs)
+
+    def folded(self) -> dict:
+        """-> {layer: (weight (Cout, Cin / groups, taps), bias)} on the parameters' device."""
+        out = fold_state_dict({k: v.detach() for k, v in self.state_dict().items()})
+        return {n: (w.reshape(w.shape[0], w.shape[1], w.shape[2]).contiguous(), b) for n, (w, b) in out.items()}
+
+    def _device_weights(self):
+        if self._packs is None:
+            L, bf16 = lib(), PRECISIONS[self.precision]
+            F = self.folded()
+            dev = self.conv_post.bias.device
+            P = {'convs.0': F['convs.0'], 'conv_post': F['conv_post']}
+            for i, (cin, cout, k, _, g, _) in enumerate(self.LAYERS[1:], 1):
+                w, b = F[f'convs.{i}']
+                nbytes = torch.zeros(1, dtype=torch.long)
+                L.dx_disc_pack_size(cout, cin // g, k, bf16, nbytes.data_ptr())
+                buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=dev)
+                L.dx_disc_pack(w.data_ptr(), buf.data_ptr(), cout, cin // g, k, bf16, _stream(dev))
+                P[f'convs.{i}'] = (buf, b)
+            self._packs = P
+        return self._packs
+
+    def _run(self, x2, p, alloc):
+        """x2 (R, T) fp32 contiguous on the device, period p (1: no folding) -> (scores (R, N, p), [channels-last feature maps
+        (R, N_i, p, C_i)]): one launch per layer."""
+        L, st, bf16 = lib(), _stream(x2.device), PRECISIONS[self.precision]
+        P = self._device_weights()
+        R, T = x2.shape
+        dev = x2.device
+        cin, cout, k, s, _, pad = self.LAYERS[0]
+        N = conv_out(-(-T // p), k, s, pad)
+        w, b = P['convs.0']
+        cur = alloc((R, N, p, cout), dev)
+        L.dx_disc_first(x2.data_ptr(), T, T, w.data_ptr(), b.data_ptr(), cur.data_ptr(), R, p, cout, k, s, pad, st)
+        fmaps = [cur]
+        for i, (cin, cout, k, s, g, pad) in enumerate(self.LAYERS[1:], 1):
+            w, b = P[f'convs.{i}']
+            nout = conv_out(N, k, s, pad)
+            out = alloc((R, nout, p, cout), dev)
+            L.dx_disc_conv(cur.data_ptr(), N * p * cin, cin, p * cin, w.data_ptr(), b.data_ptr(), out.data_ptr(), nout * p * cout, cout,
+                           p * cout, R * p, p, N, cin, cout, g, k, s, pad, 1, bf16, st)
+            fmaps.append(out)
+            cur, N = out, nout
+        w, b = P['conv_post']
+        score = alloc((R, N, p), dev)
+        C = POST[0]
+        L.dx_disc_post(cur.data_ptr(), N * p * C, C, p * C, w.data_ptr(), b.data_ptr(), score.data_ptr(), N * p, 1, p, R * p, p, N, C, POST[2], st)
+        return score, fmaps
+
+
+def _views_p(score, fmaps):
+    """channels-last buffers -> the reference's (x (R, N p), [fmap (R, C, H, p)])."""
+    R = score.shape[0]
+    return score.view(R, -1), [f.permute(0, 3, 1, 2) for f in fmaps] + [score.unsqueeze(1)]
+
+
+def _views_s(score, fmaps):
+    """channels-last buffers -> the reference's (x (R, N), [fmap (R, C, N)])."""
+    R = score.shape[0]
+    return score.view(R, -1), [f.squeeze(2).permute(0, 2, 1) for f in fmaps] + [score.view(R, 1, -1)]
+
+
+class DiscriminatorP(_SubDiscriminator):
+    """One period sub-discriminator (discriminators.py:28-66): (5, 1) convolutions over the period-folded signal."""
+    LAYERS = MPD_LAYERS
+
+    def __init__(self, period, precision='f32'):
+        super().__init__()
+        self.period = int(period)
+        self._init_layers(_WNConv, True, precision)
+
+    def forward(self, x):
+        """x (B, 1, T) -> (scores (B, n), [6 feature maps (B, C, H, p)])."""
+        _check_inputs(x)
+        _check_reflect(x.shape[2], (self.period,))
+        _check_run(self, x)
+        return _views_p(*self._run(x.reshape(x.shape[0], -1).contiguous(), self.period, _fresh))
+
+
+class DiscriminatorS(_SubDiscriminator):
+    """One scale sub-discriminator (discriminators.py:98-124): grouped k = 41 Conv1d layers."""
+    LAYERS = MSD_LAYERS
+
+    def __init__(self, use_spectral_norm=False, precision='f32'):
+        super().__init__()
+        self.use_spectral_norm = bool(use_spectral_norm)
+        self._init_layers(_SNConv if use_spectral_norm else _WNConv, False, precision)
+
+    def forward(self, x):
+        """x (B, 1, T) -> (scores (B, n), [8 feature maps (B, C, N)])."""
+        _check_inputs(x)
+        _check_run(self, x)
+        return _views_s(*self._run(x.reshape(x.shape[0], -1).contiguous(), 1, _fresh))
+
+
+class _MultiDiscriminator(nn.Module):
+    def refresh_weights(self):
+        for d in self.discriminators:
+            d.refresh_weights()
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        self.refresh_weights()
+        return out
+
+    def forward(self, y, y_hat):
+        """y, y_hat (B, 1, T) fp32 on the device -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs) as the reference returns them."""
+        _check_inputs(y, y_hat)
+        self._check_shape(y.shape[2])
+        _check_run(self, y, y_hat)
+        B = y.shape[0]
+        x2 = torch.cat([y.detach().reshape(B, -1), y_hat.detach().reshape(B, -1)], 0)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        for score, fmaps in (self._views(*raw) for raw in self._run(x2, _fresh)):
+            y_d_rs.append(score[:B])
+            y_d_gs.append(score[B:])
+            fmap_rs.append([f[:B] for f in fmaps])
+            fmap_gs.append([f[B:] for f in fmaps])
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+    def _check_shape(self, T):
+        pass
+
+
+class MultiPeriodDiscriminator(_MultiDiscriminator):
+    """Five period sub-discriminators, periods 2, 3, 5, 7, 11 (discriminators.py:69-91): 30 launches for both inputs."""
+
+    def __init__(self, precision='f32'):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorP(p, precision) for p in PERIODS])
+
+    def _check_shape(self, T):
+        _check_reflect(T, PERIODS)
+
+    _views = staticmethod(_views_p)
+
+    def _run(self, x2, alloc):
+        """-> per sub-discriminator (scores, feature maps) as the kernels' channels-last buffers."""
+        return [d._run(x2, d.period, alloc) for d in self.discriminators]
+
+
+class MultiScaleDiscriminator(_MultiDiscriminator):
+    """Three scale sub-discriminators, the first spectral-normed, the others fed through AvgPool1d(4, 2, padding=2)
+    (discriminators.py:127-156): 26 launches for both inputs."""
+
+    def __init__(self, precision='f32'):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorS(True, precision), DiscriminatorS(False, precision),
+                                             DiscriminatorS(False, precision)])
+        self.meanpools = nn.ModuleList([nn.Module(), nn.Module()])      # the reference's two AvgPool1d: no parameters
+
+    _views = staticmethod(_views_s)
+
+    def _run(self, x2, alloc):
+        out = []
+        for i, d in enumerate(self.discriminators):
+            if i:
+                R, T = x2.shape
+                pooled = alloc((R, T // 2 + 1), x2.device)
+                lib().dx_disc_pool(x2.data_ptr(), pooled.data_ptr(), R, T, _stream(x2.device))
+                x2 = pooled
+            out.append(d._run(x2, 1, alloc))
+        return out
+
+
+# ---- losses -----------------------------------------------------------------------------------------------------------------------
+def _dense_pair(r, g):
+    """Two equally shaped fp32 tensors -> the same element pairs as two dense blocks of memory (views where possible: a permuted view of
+    a contiguous buffer is un-permuted, not copied; the means below do not depend on the element order)."""
+    if r.shape != g.shape:
+        raise ValueError(f'real and generated tensors differ in shape: {tuple(r.shape)} and {tuple(g.shape)}')
+    r, g = r.detach(), g.detach()
+    if r.dtype != torch.float32 or g.dtype != torch.float32:
+        r, g = r.float(), g.float()
+    if not (r.is_contiguous() and g.is_contiguous()):
+        order = sorted(range(r.dim()), key=lambda d: (-r.stride(d), d))
+        rp, gp = r.permute(order), g.permute(order)
+        r, g = (rp, gp) if rp.is_contiguous() and gp.is_contiguous() else (r.contiguous(), g.contiguous())
+    return r, g
+
+
+def _loss_rows(pairs, kind, set_id, keep):
+    rows = []
+    for r, g in pairs:
+        r, g = _dense_pair(r, g)
+        if r.numel() == 0:
+            raise ValueError('a loss over an empty tensor')
+        keep += [r, g]
+        rows.append([r.data_ptr(), g.data_ptr(), r.numel(), kind + 2 * set_id])
+    return rows
+
+
+class _LossPlan:
+    """The device table of dx_disc_losses for a fixed list of tensors, and its workspace."""
+
+    def __init__(self, rows, n_sets, device):
+        if device.type != 'cuda':
+            raise RuntimeError('the GAN losses run on the GPU (csrc/dx_disc.hip); there is no CPU path')
+        self.n, self.n_sets = len(rows), n_sets
+        self.max_count, self.total = max(r[2] for r in rows), sum(r[2] for r in rows)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(device)
+        nfl = torch.zeros(1, dtype=torch.long)
+        lib().dx_disc_losses_workspace(self.max_count, self.n, nfl.data_ptr())
+        self.partial = torch.empty(int(nfl.item()), dtype=torch.float32, device=device)
+        self.device = device
+
+    def run(self):
+        """-> fp32 device vector: 3 totals per set, then 3 terms per entry."""
+        out = torch.empty(3 * self.n_sets + 3 * self.n, dtype=torch.float32, device=self.device)
+        lib().dx_disc_losses(self.table.data_ptr(), self.n, self.n_sets, self.max_count, self.total, self.partial.data_ptr(),
+                             out.data_ptr(), _stream(self.device))
+        return out
+
+
+def _check_loss_inputs(tensors):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError('the GAN losses are forward only: their backward is not built, and an input requires grad')
+
+
+def discriminator_loss(disc_real_outputs, disc_generated_outputs):
+    """-> (loss, r_losses, g_losses) as discriminators.py:163-174; the list entries are 0-d device tensors, not floats."""
+    pairs = list(zip(disc_real_outputs, disc_generated_outputs))
+    _check_loss_inputs([t for p in pairs for t in p])
+    keep = []
+    out = _LossPlan(_loss_rows(pairs, 0, 0, keep), 1, pairs[0][0].device).run()
+    return out[0], [out[3 + 3 * i] for i in range(len(pairs))], [out[3 + 3 * i + 1] for i in range(len(pairs))]
+
+
+def generator_loss(disc_outputs):
+    """-> (loss, gen_losses) as discriminators.py:177-185."""
+    outs = list(disc_outputs)
+    _check_loss_inputs(outs)
+    keep = []
+    out = _LossPlan(_loss_rows([(t, t) for t in outs], 0, 0, keep), 1, outs[0].device).run()
+    return out[1], [out[3 + 3 * i + 2] for i in range(len(outs))]
+
+
+def feature_loss(fmap_r, fmap_g):
+    """-> 2 x the sum over all feature maps of mean |r - g| (discriminators.py:188-194)."""
+    pairs = [(rl, gl) for dr, dg in zip(fmap_r, fmap_g) for rl, gl in zip(dr, dg)]
+    _check_loss_inputs([t for p in pairs for t in p])
+    keep = []
+    return _LossPlan(_loss_rows(pairs, 1, 0, keep), 1, pairs[0][0].device).run()[2]
+
+
+def _checkpoint(checkpoint) -> dict:
+    if isinstance(checkpoint, (str, os.PathLike)):
+        checkpoint = torch.load(checkpoint, map_location='cpu')
+    if not isinstance(checkpoint, dict) or 'mpd' not in checkpoint or 'msd' not in checkpoint:
+        raise TypeError("a discriminator checkpoint is a dict with 'mpd' and 'msd' state dicts (the reference's do_* files)")
+    return checkpoint
+
+
+class HiFiGanDiscriminators:
+    """Both discriminators from a reference ``do_*`` checkpoint (a local path or its loaded dict; nothing here downloads).
+
+    ``losses(y, y_hat)`` -> the six totals of finetune_hifigan.py:218-241 as 0-d device tensors, no host synchronisation:
+    ``loss_disc_f``, ``loss_disc_s`` (discriminator_loss of the MPD / MSD scores), ``loss_gen_f``, ``loss_gen_s`` (generator_loss),
+    ``loss_fm_f``, ``loss_fm_s`` (feature_loss).  56 layer launches and one ``dx_disc_losses`` call.  The activation workspace and the
+    loss table are kept per (B, T), so after one eager call ``losses`` can be captured in a ``torch.cuda.graph``.
+    """
+
+    def __init__(self, checkpoint=None, device='cuda', precision='f32'):
+        if checkpoint is None:
+            raise ValueError('HiFiGanDiscriminators: checkpoint is required (a local do_* checkpoint or its dict); this package never downloads one')
+        if precision not in PRECISIONS:
+            raise ValueError(f'HiFiGanDiscriminators: precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
+        state = _checkpoint(checkpoint)
+        self.precision = precision
+        self.device = torch.device(device)
+        self.mpd = MultiPeriodDiscriminator(precision)
+        self.msd = MultiScaleDiscriminator(precision)
+        self.mpd.load_state_dict(state['mpd'], strict=True)
+        self.msd.load_state_dict(state['msd'], strict=True)
+        self.mpd.to(self.device).eval()
+        self.msd.to(self.device).eval()
+        self._plans = {}
+
+    def _pass(self, y, y_hat):
+        _check_inputs(y, y_hat)
+        _check_reflect(y.shape[2], PERIODS)
+        _check_run(self.mpd, y, y_hat)
+        B, _, T = y.shape
+        key = (B, T, y.device)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = {'f': _Arena(), 's': _Arena(), 'loss': None}
+        x2 = torch.cat([y.detach().reshape(B, -1), y_hat.detach().reshape(B, -1)], 0)
+        plan['f'].reset()
+        plan['s'].reset()
+        mpd = self.mpd._run(x2, plan['f'])
+        msd = self.msd._run(x2, plan['s'])
+        return plan, B, mpd, msd
+
+    def losses(self, y, y_hat) -> dict:
+        plan, B, mpd, msd = self._pass(y, y_hat)
+        if plan['loss'] is None:
+            rows, keep = [], []
+            for s, outs in enumerate((mpd, msd)):
+                rows += _loss_rows([(sc[:B], sc[B:]) for sc, _ in outs], 0, s, keep)
+                rows += _loss_rows([(f[:B], f[B:]) for sc, fm in outs for f in fm + [sc]], 1, s, keep)
+            plan['loss'] = _LossPlan(rows, 2, y.device)
+        out = plan['loss'].run()
+        return {name: out[i] for i, name in enumerate(LOSS_NAMES)}
+
+
+__all__ = ['DiscriminatorP', 'DiscriminatorS', 'MultiPeriodDiscriminator', 'MultiScaleDiscriminator', 'HiFiGanDiscriminators',
+           'discriminator_loss', 'generator_loss', 'feature_loss']

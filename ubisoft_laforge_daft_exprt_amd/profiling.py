@@ -192,6 +192,25 @@ def price(name, a, geom: Geometry):
         return 'voc_post', 'hbm', None, rows * 32 * 4 + a['B'] * a['ncols'] * 4
     if name == 'dx_voc_pack':
         return 'voc_pack', 'hbm', None, a['Cout'] * a['Cin'] * a['taps'] * max(1, a['up']) * (4 + (2 if a['bf16'] else 4))
+    if name == 'dx_disc_conv':                           # HiFi-GAN discriminators: rows of N positions, no lengths
+        nout = (a['N'] + 2 * a['pad'] - a['taps']) // a['stride'] + 1
+        cin_g = a['Cin'] // a['groups']
+        op = 'bf16' if g('bf16') else 'f32'
+        byt = a['rows'] * (a['N'] * a['Cin'] + nout * a['Cout']) * 4 + a['Cout'] * cin_g * a['taps'] * (2 if g('bf16') else 4)
+        kind = 'disc_conv_grouped' if a['groups'] > 1 else 'disc_conv'
+        return f'{kind}<{op}>', 'mfma', 2.0 * a['rows'] * nout * a['taps'] * cin_g * a['Cout'], byt
+    if name == 'dx_disc_first':                          # Cin = 1: the waveform read once, the feature map written once
+        h = -(-a['T'] // a['p'])
+        hout = (h + 2 * a['pad'] - a['taps']) // a['stride'] + 1
+        return 'disc_first', 'hbm', None, a['B'] * (a['T'] + hout * a['p'] * a['Cout']) * 4
+    if name == 'dx_disc_post':
+        return 'disc_post', 'hbm', None, a['rows'] * a['N'] * (a['C'] + 1) * 4
+    if name == 'dx_disc_pool':
+        return 'disc_pool', 'hbm', None, a['R'] * (a['T'] + a['T'] // 2 + 1) * 4
+    if name == 'dx_disc_losses':                         # both tensors of every entry read once
+        return 'disc_losses', 'hbm', None, 2 * a['total_count'] * 4 + (3 * a['n_sets'] + 3 * a['n']) * 4
+    if name == 'dx_disc_pack':
+        return 'disc_pack', 'hbm', None, a['Cout'] * a['Cin_g'] * a['taps'] * (4 + (2 if a['bf16'] else 4))
     if name == 'dx_mel':                                 # valid frames only: DFT GEMM (2 kmax outputs of 1024) + mel GEMM per frame
         frames = geom.rows(a['B'], a['T_max'])
         flops = 2.0 * frames * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])
