@@ -465,6 +465,40 @@ int dx_disc_losses_workspace(long max_count, int n, long* floats);
  * max_count: the largest count, total_count: their sum. */
 int dx_disc_losses(const void* table, int n, int n_sets, long max_count, long total_count, float* partial, float* out, void* stream);
 
+/* ---- HiFi-GAN discriminators, backward to the generated waveform (csrc/dx_disc_bwd.hip) ---------------------------
+ * The gradient of loss_gen + loss_fm with respect to the generated rows only: no gradient to the real rows or to any weight.  Buffers
+ * and row addressing are the forward's.  R / G are the real / generated halves of a stored feature map; gw_* point to ONE device float
+ * each, the upstream gradient of the generator loss / the feature loss of this discriminator (read on the device, no host sync).
+ * "Epilogue" (epilogue = 1): out = (acc + gw_fm fm_scale sign(G - R)) * (G > 0 ? 1 : 0.1) with fm_scale = 2 / numel(G), sign(0) = 0:
+ * the pre-activation gradient of the layer whose output G is; epilogue = 0 writes acc (R, G, gw_fm may be null).  No atomics. */
+/* bytes of the transposed, per-stride-phase pack of a folded weight (Cout, Cin / groups, taps) */
+int dx_disc_dgrad_pack_size(int Cin, int Cout, int groups, int taps, int stride, int bf16, long* bytes);
+/* -> [phase][16 input channels][chunk][k step][lane] MFMA fragments, k = (tap index inside the phase) * chunk width + output channel;
+ * zero past a phase's taps; 8-channel groups: two groups per column block, block-diagonal */
+int dx_disc_dgrad_pack(const float* W, void* Wp, int Cin, int Cout, int groups, int taps, int stride, int bf16, void* stream);
+/* Data gradient of dx_disc_conv's layer: dZ (rows of (N + 2 pad - taps) / stride + 1 positions, Cout channels, strides szb, szr, szn)
+ * -> dX, R, G (rows of N positions, Cin channels, strides sxb, sxr, sxn): dX[n][ci] = sum over co of ci's group and taps t with
+ * (n + pad - t) % stride == 0 of dZ[(n + pad - t) / stride][co] W[co][ci][t], then the epilogue.  Every dX[n][ci], n < N, is written
+ * once.  stride <= taps <= 41, stride <= 4, pad <= 20; channels per group: in 8, 16, 32 or a multiple of 64, out 16, 32 or a multiple
+ * of 64; Cin % 16 == 0.  dZ 16-byte aligned with strides % 4 == 0; dX must not alias dZ. */
+int dx_disc_conv_dgrad(const float* dZ, long szb, long szr, long szn, const void* Wp, float* dX, const float* R, const float* G, long sxb,
+                       long sxr, long sxn, const float* gw_fm, float fm_scale, int rows, int rdiv, int N, int Cin, int Cout, int groups,
+                       int taps, int stride, int pad, int epilogue, int bf16, void* stream);
+/* The Cout = 1 last layer transposed, from the scores: dS[m] = s_scale (gw_gen (Sg[m] - 1) + gw_fm sign(Sg[m] - Sr[m])), s_scale =
+ * 2 / numel(Sg); dZ[n][c] = sum_t dS[n + (taps - 1) / 2 - t] W[c][t], then the epilogue with the last conv layer's map.  Sr / Sg are
+ * addressed with (ssb, ssr, ssn), dZ / R / G with (sxb, sxr, sxn) and C channels; W the folded (1, C, taps). */
+int dx_disc_post_bwd(const float* Sr, const float* Sg, long ssb, long ssr, long ssn, const float* W, float* dZ, const float* R, const float* G,
+                     long sxb, long sxr, long sxn, const float* gw_gen, const float* gw_fm, float s_scale, float fm_scale, int rows, int rdiv,
+                     int N, int C, int taps, int epilogue, void* stream);
+/* The Cin = 1 first layer transposed, through the period view: dZ [B][Hout][p][Cout] -> dy [B][sdb], T samples per row.  Sample i sums
+ * its own folded position and, where 2 (T - 1) - i lies in the reflect-padded tail [T, H p), that position too.  accumulate = 1 adds
+ * to dy. */
+int dx_disc_first_bwd(const float* dZ, const float* W, float* dy, long sdb, int T, int B, int p, int Cout, int taps, int stride, int pad,
+                      int accumulate, void* stream);
+/* AvgPool1d(4, 2, padding = 2) transposed: dy [R][T / 2 + 1] -> dx [R][T], dx[i] = (dy[i / 2] + dy[i / 2 + 1]) / 4 (terms past the end
+ * dropped); accumulate = 1 adds to dx. */
+int dx_disc_pool_bwd(const float* dy, float* dx, int R, int T, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,10 @@ profiling.price() from the launches themselves, and per-kernel times with TFLOP/
 Times are host clocks around work that ends in a device synchronise, after warm-up; the per-kernel figures bracket each launch with
 events (profiling.py), in a pass of their own.  Needs a GPU: there is no fallback.
 
-    python tools/bench_discriminators.py
+    python tools/bench_discriminators.py [--backward]
+
+``--backward`` measures the generator side instead: ``losses()``, ``generator_loss_grad()`` (the same pass + the backward to the
+generated waveform), the per-kernel split of the backward, and torch autograd of the restatement (forward + backward) on the same GPU.
 """
 import json
 import os
@@ -35,9 +38,41 @@ def timed(fn, n=10, warm=3):
     return (time.perf_counter() - t0) / n
 
 
+def backward_main():
+    from tests import disc_backward_torch as dbt
+    dev = 'cuda'
+    y, y_hat = (t.to(dev) for t in dh.make_inputs(T, 9, batch=B))
+    states = dh.state_dicts()
+    out = {'workload': f'B={B} segments of {T} samples, real + generated; gradient to the generated half'}
+    geom = profiling.Geometry([[1]])
+    for prec in ('f32', 'bf16'):
+        D = disc.HiFiGanDiscriminators(states, device=dev, precision=prec)
+        with torch.no_grad():
+            t_fwd = timed(lambda: D.losses(y, y_hat))
+        t_all = timed(lambda: D.generator_loss_grad(y, y_hat))
+        recs = []
+        old = _lib.set_timer(recs)
+        D.generator_loss_grad(y, y_hat)
+        _lib.set_timer(old)
+        torch.cuda.synchronize()
+        bwd = [r for r in recs if r[0] in ('dx_disc_conv_dgrad', 'dx_disc_post_bwd', 'dx_disc_first_bwd', 'dx_disc_pool_bwd')]
+        flops = sum(profiling.price(name, args, geom)[2] or 0.0 for name, args, _, _ in bwd)
+        out[f'hip_{prec}'] = {'losses_s': round(t_fwd, 6), 'generator_loss_grad_s': round(t_all, 6), 'backward_s': round(t_all - t_fwd, 6),
+                              'backward_launches': len(bwd), 'backward_tflop': round(flops / 1e12, 4)}
+        out[f'profile_backward_{prec}'] = profiling.summarize(bwd, geom, prec)
+        out[f'profile_forward_{prec}'] = profiling.summarize([r for r in recs if r not in bwd], geom, prec)
+    mpd_w = {k: (w.reshape(w.shape[0], w.shape[1], w.shape[2]).to(dev), b.to(dev)) for k, (w, b) in disc.fold_state_dict(states['mpd']).items()}
+    msd_w = {k: (w.to(dev), b.to(dev)) for k, (w, b) in disc.fold_state_dict(states['msd']).items()}
+    out['torch_fp32_autograd'] = {'s': round(timed(lambda: dbt.autograd_grad(y, y_hat, mpd_w, msd_w, (1, 1, 1, 1), torch.float32), n=5, warm=2), 6)}
+    out['hip_f32_over_torch_fp32'] = round(out['torch_fp32_autograd']['s'] / out['hip_f32']['generator_loss_grad_s'], 2)
+    print(json.dumps(out))
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit('bench_discriminators needs a GPU')
+    if '--backward' in sys.argv[1:]:
+        return backward_main()
     dev = 'cuda'
     y, y_hat = (t.to(dev) for t in dh.make_inputs(T, 9, batch=B))
     states = dh.state_dicts()

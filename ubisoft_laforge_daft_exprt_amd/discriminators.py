@@ -1,4 +1,5 @@
-"""HiFi-GAN discriminators on gfx950, forward only (reference src/daft_exprt/vocoder/discriminators.py).
+"""HiFi-GAN discriminators on gfx950 (reference src/daft_exprt/vocoder/discriminators.py): the forward, the GAN losses, and the
+backward of the generator-side losses to the generated waveform.
 
 ``MultiPeriodDiscriminator`` / ``DiscriminatorP`` and ``MultiScaleDiscriminator`` / ``DiscriminatorS`` own exactly the reference's
 state-dict keys and shapes (90 and 80 tensors), so ``load_state_dict(strict=True)`` takes the ``['mpd']`` / ``['msd']`` entries of a
@@ -12,8 +13,10 @@ Weight folding, once and lazily (``refresh_weights()`` drops the folded copies; 
     EVAL-mode semantics, ``W = weight_orig / (u . (W_mat v))`` with the stored ``u`` and ``v``.  The reference's train-mode power
     iteration is NOT done and ``.train()`` does not change the forward.
 
-There is no backward: with grad mode on, an input (or a parameter of the module) that requires grad raises instead of returning a
-silently detached result.  The parameters are created with ``requires_grad=False``.
+``forward``, ``losses`` and the three loss functions have no backward: with grad mode on, an input (or a parameter of the module) that
+requires grad raises instead of returning a silently detached result.  The parameters are created with ``requires_grad=False``.
+The one backward that exists is ``HiFiGanDiscriminators.generator_losses`` / ``generator_loss_grad`` (csrc/dx_disc_bwd.hip): the
+gradient of loss_gen and loss_fm of both discriminators with respect to ``y_hat`` only; ``y`` and the weights are constants.
 
 ``discriminator_loss``, ``generator_loss`` and ``feature_loss`` keep the reference signatures and run through ``dx_disc_losses``.
 The one deviation: the per-sub-discriminator entries are 0-d device tensors where the reference returns ``.item()`` floats (no host
@@ -37,6 +40,7 @@ MSD_LAYERS = ((1, 128, 15, 1, 1, 7), (128, 128, 41, 2, 4, 20), (128, 256, 41, 2,
               (512, 1024, 41, 4, 16, 20), (1024, 1024, 41, 1, 16, 20), (1024, 1024, 5, 1, 1, 2))
 POST = (1024, 1, 3, 1, 1, 1)
 LOSS_NAMES = ('loss_disc_f', 'loss_gen_f', 'loss_fm_f', 'loss_disc_s', 'loss_gen_s', 'loss_fm_s')
+GEN_LOSS_NAMES = ('loss_gen_f', 'loss_fm_f', 'loss_gen_s', 'loss_fm_s')     # the generator-side losses: the ones with a backward
 
 
 def conv_out(n, taps, stride, pad):
@@ -113,6 +117,16 @@ def _check_reflect(T, periods):
             raise ValueError(f'period {p}: the reflect padding ({p - T % p} samples) must be shorter than the signal ({T} samples)')
 
 
+def _check_differentiable(owner, y, y_hat):
+    """The guards of the entry points that have a backward: only ``y_hat`` may require grad."""
+    if y.requires_grad:
+        raise RuntimeError('the discriminators\' backward goes to y_hat only: y must not require grad')
+    if any(q.requires_grad for m in (owner.mpd, owner.msd) for q in m.parameters()):
+        raise RuntimeError('the discriminators\' backward goes to y_hat only: their parameters are constants and must not require grad')
+    if y.device.type != 'cuda':
+        raise RuntimeError('the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels); there is no CPU path')
+
+
 def _check_run(module, *xs):
     if torch.is_grad_enabled() and (any(t.requires_grad for t in xs) or any(q.requires_grad for q in module.parameters())):
         raise RuntimeError('the discriminators are forward only: their backward is not built, and an input or parameter requires grad '
@@ -154,10 +168,12 @@ class _SubDiscriminator(nn.Module):
         self.convs = nn.ModuleList([conv_cls((cout, cin // g, k) + tail) for cin, cout, k, _, g, _ in self.LAYERS])
         self.conv_post = conv_cls((POST[1], POST[0], POST[2]) + tail)
         self._packs = None
+        self._dgrad = None
 
     def refresh_weights(self):
         """Drop the folded, packed device weights: the next forward folds the current parameters again."""
         self._packs = None
+        self._dgrad = None
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
@@ -166,6 +182,7 @@ class _SubDiscriminator(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):
         self._packs = None                      # .to() / .cuda(): the packs follow the parameters
+        self._dgrad = None
         return super()._apply(fn, *args, **kwargs)
 
     def folded(self) -> dict:
@@ -188,6 +205,49 @@ class _SubDiscriminator(nn.Module):
                 P[f'convs.{i}'] = (buf, b)
             self._packs = P
         return self._packs
+
+    def _dgrad_weights(self):
+        """The transposed, per-stride-phase packs of dx_disc_conv_dgrad, built on the first backward only."""
+        if self._dgrad is None:
+            L, bf16 = lib(), PRECISIONS[self.precision]
+            F = self.folded()
+            dev = self.conv_post.bias.device
+            P = {}
+            for i, (cin, cout, k, s, g, _) in enumerate(self.LAYERS[1:], 1):
+                w = F[f'convs.{i}'][0]
+                nbytes = torch.zeros(1, dtype=torch.long)
+                L.dx_disc_dgrad_pack_size(cin, cout, g, k, s, bf16, nbytes.data_ptr())
+                buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=dev)
+                L.dx_disc_dgrad_pack(w.data_ptr(), buf.data_ptr(), cin, cout, g, k, s, bf16, _stream(dev))
+                P[i] = buf
+            self._dgrad = P
+        return self._dgrad
+
+    def _run_bwd(self, score, fmaps, B, T, p, gw, i_gen, i_fm, dz, dy, accumulate):
+        """The chain of one sub-discriminator from its scores down to the waveform: score (2B, N, p) and the channels-last maps of a
+        forward pass over real + generated rows; gw the four upstream gradients (device); dz two buffers for the pre-activation
+        gradients; dy (B, T) receives (accumulate: is added) the gradient of the generated rows.  One launch per layer."""
+        L, st, bf16 = lib(), _stream(score.device), PRECISIONS[self.precision]
+        P, D = self._device_weights(), self._dgrad_weights()
+        gen, fm = gw.data_ptr() + 4 * i_gen, gw.data_ptr() + 4 * i_fm
+        half = lambda t: (t.data_ptr(), t.data_ptr() + 4 * (t.numel() // 2))
+        N, C = score.shape[1], POST[0]
+        last = fmaps[-1]
+        (sr, sg), (r, g) = half(score), half(last)
+        cur, nxt = dz
+        L.dx_disc_post_bwd(sr, sg, N * p, 1, p, P['conv_post'][0].data_ptr(), cur.data_ptr(), r, g, N * p * C, C, p * C, gen, fm,
+                           2.0 / (score.numel() // 2), 2.0 / (last.numel() // 2), B * p, p, N, C, POST[2], 1, st)
+        for i in range(len(self.LAYERS) - 1, 0, -1):
+            cin, cout, k, s, grp, pad = self.LAYERS[i]
+            below = fmaps[i - 1]
+            n_in, n_out = below.shape[1], fmaps[i].shape[1]
+            r, g = half(below)
+            L.dx_disc_conv_dgrad(cur.data_ptr(), n_out * p * cout, cout, p * cout, D[i].data_ptr(), nxt.data_ptr(), r, g, n_in * p * cin, cin,
+                                 p * cin, fm, 2.0 / (below.numel() // 2), B * p, p, n_in, cin, cout, grp, k, s, pad, 1, bf16, st)
+            cur, nxt = nxt, cur
+        _, cout, k, s, _, pad = self.LAYERS[0]
+        L.dx_disc_first_bwd(cur.data_ptr(), P['convs.0'][0].data_ptr(), dy.data_ptr(), dy.shape[1], T, B, p, cout, k, s, pad,
+                            int(accumulate), st)
 
     def _run(self, x2, p, alloc):
         """x2 (R, T) fp32 contiguous on the device, period p (1: no folding) -> (scores (R, N, p), [channels-last feature maps
@@ -445,15 +505,19 @@ class HiFiGanDiscriminators:
         self.msd.to(self.device).eval()
         self._plans = {}
 
-    def _pass(self, y, y_hat):
+    def _pass(self, y, y_hat, differentiable=False):
         _check_inputs(y, y_hat)
         _check_reflect(y.shape[2], PERIODS)
-        _check_run(self.mpd, y, y_hat)
+        if differentiable:
+            _check_differentiable(self, y, y_hat)
+        else:
+            _check_run(self.mpd, y, y_hat)
         B, _, T = y.shape
         key = (B, T, y.device)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = {'f': _Arena(), 's': _Arena(), 'loss': None}
+            plan = self._plans[key] = {'f': _Arena(), 's': _Arena(), 'loss': None, 'pass': 0, 'bwd': None, 'gw': {}}
+        plan['pass'] += 1
         x2 = torch.cat([y.detach().reshape(B, -1), y_hat.detach().reshape(B, -1)], 0)
         plan['f'].reset()
         plan['s'].reset()
@@ -463,14 +527,90 @@ class HiFiGanDiscriminators:
 
     def losses(self, y, y_hat) -> dict:
         plan, B, mpd, msd = self._pass(y, y_hat)
+        return self._losses(plan, B, mpd, msd, y.device)
+
+    def _losses(self, plan, B, mpd, msd, device):
         if plan['loss'] is None:
             rows, keep = [], []
             for s, outs in enumerate((mpd, msd)):
                 rows += _loss_rows([(sc[:B], sc[B:]) for sc, _ in outs], 0, s, keep)
                 rows += _loss_rows([(f[:B], f[B:]) for sc, fm in outs for f in fm + [sc]], 1, s, keep)
-            plan['loss'] = _LossPlan(rows, 2, y.device)
+            plan['loss'] = _LossPlan(rows, 2, device)
         out = plan['loss'].run()
         return {name: out[i] for i, name in enumerate(LOSS_NAMES)}
+
+    # ---- backward to the generated waveform (csrc/dx_disc_bwd.hip) -------------------------------------------------------------------
+    def _forward_kept(self, y, y_hat):
+        """One pass whose feature maps stay in the plan for a backward -> (state, the four generator-side losses)."""
+        plan, B, mpd, msd = self._pass(y, y_hat, differentiable=True)
+        six = self._losses(plan, B, mpd, msd, y.device)
+        state = (plan, plan['pass'], B, y.shape[2], mpd, msd)
+        return state, {name: six[name] for name in GEN_LOSS_NAMES}
+
+    def _backward(self, state, gw):
+        """gw: fp32 device tensor of 4, the upstream gradients in GEN_LOSS_NAMES order -> dy_hat (B, 1, T)."""
+        plan, stamp, B, T, mpd, msd = state
+        if plan['pass'] != stamp:
+            raise RuntimeError('the discriminators\' feature maps of this pass were overwritten by a later pass at the same (B, T): '
+                               'call backward() before the next losses() / generator_losses() / generator_loss_grad() at that shape')
+        dev = gw.device
+        if plan['bwd'] is None:
+            biggest = max(f.numel() // 2 for _, fm in mpd + msd for f in fm)
+            plan['bwd'] = {'dz': (_fresh((biggest,), dev), _fresh((biggest,), dev)),
+                           'pooled': [_fresh((B, msd[i][1][0].shape[1]), dev) for i in (1, 2)]}
+        dz, pooled = plan['bwd']['dz'], plan['bwd']['pooled']
+        dy = _fresh((B, T), dev)
+        for i, (d, (score, fmaps)) in enumerate(zip(self.mpd.discriminators, mpd)):
+            d._run_bwd(score, fmaps, B, T, d.period, gw, 0, 1, dz, dy, i > 0)
+        subs = self.msd.discriminators
+        subs[0]._run_bwd(*msd[0], B, T, 1, gw, 2, 3, dz, dy, True)
+        T1, T2 = pooled[0].shape[1], pooled[1].shape[1]
+        subs[1]._run_bwd(*msd[1], B, T1, 1, gw, 2, 3, dz, pooled[0], False)
+        subs[2]._run_bwd(*msd[2], B, T2, 1, gw, 2, 3, dz, pooled[1], False)
+        L, st = lib(), _stream(dev)
+        L.dx_disc_pool_bwd(pooled[1].data_ptr(), pooled[0].data_ptr(), B, T1, 1, st)
+        L.dx_disc_pool_bwd(pooled[0].data_ptr(), dy.data_ptr(), B, T, 1, st)
+        return dy.view(B, 1, T)
+
+    def generator_losses(self, y, y_hat) -> dict:
+        """-> {loss_gen_f, loss_fm_f, loss_gen_s, loss_fm_s}: the bits of ``losses()``, differentiable with respect to ``y_hat`` (only).
+        The backward must run before the next pass at the same (B, T): the feature maps live in the per-shape plan."""
+        out = _GeneratorLosses.apply(y_hat, self, y)
+        return dict(zip(GEN_LOSS_NAMES, out))
+
+    def generator_loss_grad(self, y, y_hat, weights=(1.0, 1.0, 1.0, 1.0)):
+        """-> ({the four generator-side losses}, d sum_i weights[i] loss_i / d y_hat (B, 1, T)), without autograd.  ``weights``: four
+        floats or an fp32 device tensor of 4, in the order loss_gen_f, loss_fm_f, loss_gen_s, loss_fm_s."""
+        with torch.no_grad():
+            state, four = self._forward_kept(y, y_hat)
+            plan = state[0]
+            if torch.is_tensor(weights):
+                if weights.shape != (4,) or weights.dtype != torch.float32 or weights.device != y.device:
+                    raise ValueError('weights: four floats or an fp32 tensor of 4 on the inputs\' device')
+                gw = weights.detach().contiguous()
+            else:
+                key = tuple(float(w) for w in weights)
+                if len(key) != 4:
+                    raise ValueError('weights: four floats or an fp32 tensor of 4 on the inputs\' device')
+                gw = plan['gw'].get(key)
+                if gw is None:                       # uploaded once per plan: a captured graph must not copy from host memory
+                    gw = plan['gw'][key] = torch.tensor(key, dtype=torch.float32).to(y.device)
+            return four, self._backward(state, gw)
+
+
+class _GeneratorLosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y_hat, owner, y):
+        state, four = owner._forward_kept(y, y_hat)
+        ctx.owner, ctx.state = owner, state
+        return tuple(four[name].clone() for name in GEN_LOSS_NAMES)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        ref = next(g for g in grads if g is not None)
+        gw = torch.stack([torch.zeros_like(ref) if g is None else g for g in grads]).float().reshape(4).contiguous()
+        return ctx.owner._backward(ctx.state, gw), None, None
 
 
 __all__ = ['DiscriminatorP', 'DiscriminatorS', 'MultiPeriodDiscriminator', 'MultiScaleDiscriminator', 'HiFiGanDiscriminators',

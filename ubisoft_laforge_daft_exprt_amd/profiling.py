@@ -211,6 +211,23 @@ def price(name, a, geom: Geometry):
         return 'disc_losses', 'hbm', None, 2 * a['total_count'] * 4 + (3 * a['n_sets'] + 3 * a['n']) * 4
     if name == 'dx_disc_pack':
         return 'disc_pack', 'hbm', None, a['Cout'] * a['Cin_g'] * a['taps'] * (4 + (2 if a['bf16'] else 4))
+    if name == 'dx_disc_conv_dgrad':                     # the forward layer's FLOPs for the same rows; dZ read, dX written, R and G read by the epilogue
+        nout = (a['N'] + 2 * a['pad'] - a['taps']) // a['stride'] + 1
+        cin_g = a['Cin'] // a['groups']
+        op = 'bf16' if g('bf16') else 'f32'
+        byt = a['rows'] * (nout * a['Cout'] + a['N'] * a['Cin'] * (3 if g('epilogue') else 1)) * 4 + a['Cout'] * cin_g * a['taps'] * (2 if g('bf16') else 4)
+        kind = 'disc_dgrad_grouped' if a['groups'] > 1 else 'disc_dgrad'
+        return f'{kind}<{op}>', 'mfma', 2.0 * a['rows'] * nout * a['taps'] * cin_g * a['Cout'], byt
+    if name == 'dx_disc_post_bwd':                       # both score halves read, dZ written, R and G read
+        return 'disc_post_bwd', 'hbm', None, a['rows'] * a['N'] * (2 + a['C'] * (3 if g('epilogue') else 1)) * 4
+    if name == 'dx_disc_first_bwd':                      # dZ read once, the waveform gradient written (and read when accumulating)
+        h = -(-a['T'] // a['p'])
+        hout = (h + 2 * a['pad'] - a['taps']) // a['stride'] + 1
+        return 'disc_first_bwd', 'hbm', None, a['B'] * (hout * a['p'] * a['Cout'] + a['T'] * (2 if g('accumulate') else 1)) * 4
+    if name == 'dx_disc_pool_bwd':
+        return 'disc_pool_bwd', 'hbm', None, a['R'] * (a['T'] // 2 + 1 + a['T'] * (2 if g('accumulate') else 1)) * 4
+    if name == 'dx_disc_dgrad_pack':
+        return 'disc_dgrad_pack', 'hbm', None, a['Cout'] * (a['Cin'] // a['groups']) * a['taps'] * (4 + (2 if a['bf16'] else 4))
     if name == 'dx_mel':                                 # valid frames only: DFT GEMM (2 kmax outputs of 1024) + mel GEMM per frame
         frames = geom.rows(a['B'], a['T_max'])
         flops = 2.0 * frames * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])
