@@ -21,6 +21,28 @@ def test_library_exports_every_declared_symbol():
     assert lib.dx_version() == 1
 
 
+def test_every_header_in_csrc_is_a_dependency_of_every_object(monkeypatch):
+    """A header that is created and not registered would leave stale objects in the tree: the dependency list that ``_compile`` hands to
+    the staleness check holds the source and every ``*.h`` that csrc/ holds now (the directory is listed here, no name is spelled)."""
+    from ubisoft_laforge_daft_exprt_amd import build
+    headers = {os.path.join(build.CSRC, f) for f in os.listdir(build.CSRC) if f.endswith('.h')}
+    assert len(headers) >= 3
+    seen = []
+
+    def never_stale(target, deps):
+        seen.append((target, set(deps)))
+        return False                                                  # nothing is compiled
+
+    monkeypatch.setattr(build, '_stale', never_stale)
+    jobs = [(src, False) for src in build.SOURCES] + [(src, True) for src in build.F16_SOURCES]
+    for job in jobs:
+        build._compile(job)
+    assert len(seen) == len(jobs)
+    for (src, _), (target, deps) in zip(jobs, seen):
+        assert os.path.join(build.CSRC, src) in deps, target
+        assert headers <= deps, (target, sorted(headers - deps))
+
+
 def test_argument_validation_without_gpu():
     from ubisoft_laforge_daft_exprt_amd._lib import lib, DxError
     with pytest.raises(DxError, match='taps'):

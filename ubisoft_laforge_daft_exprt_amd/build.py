@@ -21,11 +21,15 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _deps(src):
+    """An object depends on its source and on every header in csrc/: listed, not kept by hand, so a new header cannot be forgotten."""
+    return [os.path.join(CSRC, src)] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h'))
+
+
 def _compile(job):
     src, f16 = job
     obj = os.path.join(CSRC, os.path.splitext(src)[0] + ('_f16.o' if f16 else '.o'))
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, 'dx_common.h'), os.path.join(CSRC, 'dx_f16_names.h'), os.path.join(CSRC, 'dx_rowvec.h')]
-    if _stale(obj, deps):
+    if _stale(obj, _deps(src)):
         subprocess.run(['hipcc', *FLAGS, *(['-DDX_F16'] if f16 else []), '-c', os.path.join(CSRC, src), '-o', obj], check=True)
     return obj
 

@@ -57,6 +57,7 @@ typedef dx_h16 bf16x4 __attribute__((ext_vector_type(4)));
 
 static inline int dx_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int dx_roundup(int a, int b) { return dx_cdiv(a, b) * b; }
+static inline bool dx_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 #ifdef __HIPCC__
 // ---- split-bf16 operands (C ABI operand mode 2, bf16 build) ---------------------------------------------------------------------
@@ -92,6 +93,36 @@ __device__ __forceinline__ f32x4 dx_mma_split3(const dx_bf16x8& ah, const dx_bf1
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
   return c;
 }
+
+// ---- exact-f32 / bf16 operand modes of the kernels whose storage is fp32 ---------------------------------------------------------
+// One 16-wide k step in exact f32: four chained v_mfma_f32_16x16x4_f32; a / b hold the lane's 4 consecutive k (k = 4 (lane / 16) + e)
+// of row / column (lane % 16).  A and B use the same k map, so any permutation inside a step cancels.
+__device__ __forceinline__ f32x4 dx_mma_f32_k16(f32x4 a, f32x4 b, f32x4 c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+  return c;
+}
+// T: the LDS / pack element; KS: k per step; VEC: k per lane and step (one 16-byte fragment); PAD: LDS row padding in elements.
+// Always bf16 (never dx_h16): these kernels have no fp16 twin.
+template <bool BF> struct DxMmaOp;
+template <> struct DxMmaOp<false> {
+  typedef float T;
+  static constexpr int KS = 16, VEC = 4, PAD = 4;
+  __device__ static __forceinline__ T cvt(float v) { return v; }
+  __device__ static __forceinline__ f32x4 mma(const uint4& a, const uint4& b, f32x4 c) {
+    return dx_mma_f32_k16(__builtin_bit_cast(f32x4, a), __builtin_bit_cast(f32x4, b), c);
+  }
+};
+template <> struct DxMmaOp<true> {
+  typedef __bf16 T;
+  static constexpr int KS = 32, VEC = 8, PAD = 8;
+  __device__ static __forceinline__ T cvt(float v) { return (__bf16)v; }
+  __device__ static __forceinline__ f32x4 mma(const uint4& a, const uint4& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dx_bf16x8, a), __builtin_bit_cast(dx_bf16x8, b), c, 0, 0, 0);
+  }
+};
 
 // ---- wave64 reductions -------------------------------------------------------------------------
 __device__ __forceinline__ float dx_wave_sum(float v) {

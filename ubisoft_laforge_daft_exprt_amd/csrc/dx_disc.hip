@@ -17,40 +17,14 @@
 // v_mfma_f32_16x16x32_bf16; fp32 accumulation, bias and leaky-ReLU in the epilogue, one store per output element.
 //
 // No atomics anywhere: every output element and every loss is summed in an order fixed by the shapes alone.
-#include "dx_common.h"
+#include "dx_disc_tile.h"
 
 namespace {
 
-constexpr float DISC_SLOPE = 0.1f;
-constexpr int DT = 64;              // output positions per tile (4 MFMA row blocks)
 constexpr int KC = 64;              // input channels of one group per LDS chunk, at most
-constexpr int THREADS = 256;
 constexpr int LOSS_CHUNK = 16384;   // elements per partial sum of dx_disc_losses
 
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * DISC_SLOPE; }
-
-template <bool BF> struct DiscOp;
-template <> struct DiscOp<false> {
-  typedef float T;
-  static constexpr int KS = 16, VEC = 4, PAD = 4, BLOCK = 4;
-  __device__ static __forceinline__ T cvt(float v) { return v; }
-  __device__ static __forceinline__ f32x4 mma(const uint4& a4, const uint4& b4, f32x4 c) {
-    const f32x4 a = __builtin_bit_cast(f32x4, a4), b = __builtin_bit_cast(f32x4, b4);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-  }
-};
-template <> struct DiscOp<true> {
-  typedef __bf16 T;
-  static constexpr int KS = 32, VEC = 8, PAD = 8, BLOCK = 16;
-  __device__ static __forceinline__ T cvt(float v) { return (__bf16)v; }
-  __device__ static __forceinline__ f32x4 mma(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dx_bf16x8, a), __builtin_bit_cast(dx_bf16x8, b), c, 0, 0, 0);
-  }
-};
 
 // chunk geometry shared by the pack and the kernel: cg channels of a group per chunk, nchunks chunks, KST k steps per chunk
 struct PackGeom { int cg, lg, nchunks, KST; };
@@ -75,67 +49,31 @@ struct ConvArgs {
 // NI: 16-wide column blocks per wave (the workgroup covers 64 * NI output channels, all of one group when NI > 1)
 template <bool BF, int NI>
 __global__ void __launch_bounds__(THREADS) disc_conv_kernel(ConvArgs p) {
-  typedef DiscOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char disc_smem[];
   T* A = reinterpret_cast<T*>(disc_smem);
   const int row = blockIdx.y, m0 = blockIdx.x * DT, co0 = blockIdx.z * (NI * 64);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-  const int rb = row / p.rdiv, rc = row - rb * p.rdiv;
-  const float* X = p.X + rb * p.sxb + rc * p.sxr;
-  float* Y = p.Y + rb * p.syb + rc * p.syr;
+  const float* X = p.X + disc_row_offset(row, p.rdiv, p.sxb, p.sxr);
+  float* Y = p.Y + disc_row_offset(row, p.rdiv, p.syb, p.syr);
   const int grp0 = co0 / p.Cout_g;
   const int ngrp = p.Cout_g >= NI * 64 ? 1 : (NI * 64) / p.Cout_g;
   const int cw = ngrp * p.cg, lda = cw + Op::PAD;
   const int rows = (DT - 1) * p.stride + p.taps, RP = (rows + p.stride - 1) / p.stride;
   const int coff = ((co0 + w * 16) / p.Cout_g - grp0) * p.cg;      // this wave's group inside the staged channels
-  const int K = p.taps * p.cg, q4 = cw >> 2, n0 = m0 * p.stride - p.pad;
-  // The K sum is blocked: Op::BLOCK k steps of one chunk (64 products in f32) run as one MFMA chain from zero in `part`, and the block
-  // sums are added into `acc` in order.  One chain over a 5120-product sum loses about four times as much to rounding.
-  f32x4 acc[NI][4], part[NI][4];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = part[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // LDS row of window position q (a tap, or a staged row): de-interleaved by stride phase, (q % stride) * RP + q / stride
+  const auto lrow = [&](int q) {
+    const int qd = (q * p.inv_stride) >> 16;
+    return (q - qd * p.stride) * RP + qd;
+  };
+  f32x4 acc[NI][4] = {}, part[NI][4] = {};
   for (int ch = 0; ch < p.nchunks; ++ch) {
-    const int cin0 = grp0 * p.Cin_g + ch * p.cg;
     __syncthreads();
-    for (int e = threadIdx.x; e < rows * q4; e += THREADS) {
-      const int rr = e / q4, cc = (e - rr * q4) * 4, n = n0 + rr;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n >= 0 && n < p.N) v = *reinterpret_cast<const float4*>(X + (long)n * p.sxn + cin0 + cc);
-      const int qd = (rr * p.inv_stride) >> 16, lrow = (rr - qd * p.stride) * RP + qd;
-      T* d = A + lrow * lda + cc;
-      d[0] = Op::cvt(v.x); d[1] = Op::cvt(v.y); d[2] = Op::cvt(v.z); d[3] = Op::cvt(v.w);
-    }
+    disc_stage<BF>(A, lda, X + (grp0 * p.Cin_g + ch * p.cg), p.sxn, m0 * p.stride - p.pad, p.N, rows, cw >> 2, lrow);
     __syncthreads();
-    for (int ks = 0; ks < p.KST; ++ks) {
-      if ((ks & (Op::BLOCK - 1)) == 0) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            acc[i][j] += part[i][j];
-            part[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-          }
-      }
-      const int k0 = ks * Op::KS + g * Op::VEC;
-      const bool valid = k0 < K;                                       // past K the pack holds zeros; A must not be read there
-      const int t = valid ? k0 >> p.lg : 0, c = k0 & (p.cg - 1);
-      const int td = (t * p.inv_stride) >> 16, lrow = (t - td * p.stride) * RP + td;
-      const T* ap = A + (lrow + r) * lda + coff + c;
-      uint4 b[NI];
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-        b[i] = p.Wp[(((long)(co0 / 16 + w + 4 * i) * p.nchunks + ch) * p.KST + ks) * 64 + lane];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint4 a = make_uint4(0u, 0u, 0u, 0u);
-        if (valid) a = *reinterpret_cast<const uint4*>(ap + j * 16 * lda);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) part[i][j] = Op::mma(a, b[i], part[i][j]);
-      }
-    }
+    disc_chunk_mma<BF>(A, lda, coff, p.Wp + ((long)(co0 / 16 + w) * p.nchunks + ch) * p.KST * 64, 4L * p.nchunks * p.KST * 64, p.KST,
+                       p.taps * p.cg, p.lg, p.cg - 1, lrow, acc, part);
   }
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
@@ -159,20 +97,15 @@ __global__ void __launch_bounds__(THREADS) disc_conv_kernel(ConvArgs p) {
 // channel nb * 16 + n, k = t * cg + c the tap and the channel inside the chunk; zero at k >= taps * cg.  W is (Cout, Cin_g, taps).
 template <bool BF>
 __global__ void disc_pack_kernel(const float* W, void* out, int Cin_g, int taps, PackGeom q, long total) {
-  typedef DiscOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
-  const int v = (int)(e % Op::VEC);
-  long f = e / Op::VEC;
-  const int lane = (int)(f % 64); f /= 64;
-  const int ks = (int)(f % q.KST); f /= q.KST;
-  const int ch = (int)(f % q.nchunks); f /= q.nchunks;
-  const int nb = (int)f;
-  const int k = ks * Op::KS + (lane >> 4) * Op::VEC + v, n = nb * 16 + (lane & 15);
+  DiscPackIdx x = disc_pack_lane<BF>(e);
+  disc_pack_step<BF>(x, q.KST, q.nchunks);
   float val = 0.f;
-  if (k < taps * q.cg) {
-    const int t = k >> q.lg, c = ch * q.cg + (k & (q.cg - 1));
-    val = W[((long)n * Cin_g + c) * taps + t];
+  if (x.k < taps * q.cg) {
+    const int t = x.k >> q.lg, c = x.ch * q.cg + (x.k & (q.cg - 1));
+    val = W[((long)x.n * Cin_g + c) * taps + t];
   }
   reinterpret_cast<typename Op::T*>(out)[e] = Op::cvt(val);
 }
@@ -181,7 +114,7 @@ long pack_elems(int Cout, const PackGeom& q, int bf16) { return (long)(Cout / 16
 
 template <bool BF, int NI>
 int launch_conv(const ConvArgs& a, int rows, int Cout, hipStream_t s) {
-  typedef DiscOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const int ngrp = a.Cout_g >= NI * 64 ? 1 : (NI * 64) / a.Cout_g;
   const int win = (DT - 1) * a.stride + a.taps, RP = dx_cdiv(win, a.stride);
   const size_t smem = (size_t)RP * a.stride * (ngrp * a.cg + Op::PAD) * sizeof(typename Op::T);
@@ -239,8 +172,8 @@ __global__ void __launch_bounds__(THREADS) disc_post_kernel(const float* X, long
   if (id >= total) return;
   const int lane = threadIdx.x & 63;
   const int row = (int)(id / N), m = (int)(id - (long)row * N);
-  const int rb = row / rdiv, rc = row - rb * rdiv, pad = (taps - 1) / 2;
-  const float* x = X + rb * sxb + rc * sxr;
+  const int pad = (taps - 1) / 2;
+  const float* x = X + disc_row_offset(row, rdiv, sxb, sxr);
   float acc = 0.f, comp = 0.f;
   for (int t = 0; t < taps; ++t) {
     const int n = m - pad + t;
@@ -255,7 +188,7 @@ __global__ void __launch_bounds__(THREADS) disc_post_kernel(const float* X, long
     }
   }
   acc = dx_wave_sum(acc + comp);
-  if (lane == 0) Y[rb * syb + rc * syr + (long)m * syn] = acc + bias[0];
+  if (lane == 0) Y[disc_row_offset(row, rdiv, syb, syr) + (long)m * syn] = acc + bias[0];
 }
 
 // AvgPool1d(4, 2, padding = 2), count_include_pad: y[j] = (x[2j-2] + x[2j-1] + x[2j] + x[2j+1]) / 4, zeros outside [0, T).
@@ -349,8 +282,6 @@ __global__ void __launch_bounds__(THREADS) disc_loss_final_kernel(const LossEntr
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -394,7 +325,7 @@ int dx_disc_conv(const float* X, long sxb, long sxr, long sxn, const void* Wp, c
   DX_REQUIRE(pack_geom(Cin_g, taps, bf16, &q), "dx_disc_conv: unsupported shape (input channels per group 8, 16, 32 or a multiple of 64)");
   DX_REQUIRE(Cout % 64 == 0 && (Cout_g % 64 == 0 || ((Cout_g == 16 || Cout_g == 32) && q.nchunks == 1)) && Cout / 64 <= 65535,
              "dx_disc_conv: unsupported shape (Cout %% 64 == 0; output channels per group 16, 32 or a multiple of 64)");
-  DX_REQUIRE(sxn % 4 == 0 && sxr % 4 == 0 && sxb % 4 == 0 && aligned16(X),
+  DX_REQUIRE(sxn % 4 == 0 && sxr % 4 == 0 && sxb % 4 == 0 && dx_aligned16(X),
              "dx_disc_conv: the input needs strides %% 4 == 0 and a 16-byte aligned X");
   ConvArgs a;
   a.X = X; a.sxb = sxb; a.sxr = sxr; a.sxn = sxn;
@@ -427,7 +358,7 @@ int dx_disc_post(const float* X, long sxb, long sxr, long sxn, const float* W, c
   DX_REQUIRE(X && W && bias && Y, "dx_disc_post: null pointer");
   DX_REQUIRE(rows > 0 && rdiv > 0 && N > 0 && C > 0 && C % 4 == 0 && taps > 0 && taps % 2 == 1,
              "dx_disc_post: bad shape (positive sizes, C %% 4 == 0, odd taps)");
-  DX_REQUIRE(sxn % 4 == 0 && sxr % 4 == 0 && sxb % 4 == 0 && aligned16(X), "dx_disc_post: the input needs strides %% 4 == 0 and a 16-byte aligned X");
+  DX_REQUIRE(sxn % 4 == 0 && sxr % 4 == 0 && sxb % 4 == 0 && dx_aligned16(X), "dx_disc_post: the input needs strides %% 4 == 0 and a 16-byte aligned X");
   const long total = (long)rows * N;
   hipLaunchKernelGGL(disc_post_kernel, dim3((unsigned)((total + 3) / 4)), dim3(THREADS), 0, (hipStream_t)stream,
                      X, sxb, sxr, sxn, W, bias, Y, syb, syr, syn, rdiv, N, C, taps, total);

@@ -12,37 +12,11 @@
 // slope (read from the stored maps), so what is written is that layer's pre-activation gradient, once.
 //
 // No atomics, no scratch: every sum runs in an order fixed by the shapes alone.
-#include "dx_common.h"
+#include "dx_disc_tile.h"
 
 namespace {
 
-constexpr float DISC_SLOPE = 0.1f;
-constexpr int DT = 64;              // positions of one phase per tile (4 MFMA row blocks)
-constexpr int THREADS = 256;
 constexpr int SUB = 8;              // lanes per waveform sample in dx_disc_first_bwd
-
-template <bool BF> struct DgOp;
-template <> struct DgOp<false> {
-  typedef float T;
-  static constexpr int KS = 16, VEC = 4, PAD = 4, BLOCK = 4;
-  __device__ static __forceinline__ T cvt(float v) { return v; }
-  __device__ static __forceinline__ f32x4 mma(const uint4& a4, const uint4& b4, f32x4 c) {
-    const f32x4 a = __builtin_bit_cast(f32x4, a4), b = __builtin_bit_cast(f32x4, b4);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-  }
-};
-template <> struct DgOp<true> {
-  typedef __bf16 T;
-  static constexpr int KS = 32, VEC = 8, PAD = 8, BLOCK = 16;
-  __device__ static __forceinline__ T cvt(float v) { return (__bf16)v; }
-  __device__ static __forceinline__ f32x4 mma(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dx_bf16x8, a), __builtin_bit_cast(dx_bf16x8, b), c, 0, 0, 0);
-  }
-};
 
 __host__ __device__ __forceinline__ int taps_of_phase(int taps, int stride, int phase) { return (taps - phase + stride - 1) / stride; }
 __host__ __device__ __forceinline__ int ksteps(int U, int cgk, int KS) { return (U * cgk + KS - 1) / KS; }
@@ -92,69 +66,32 @@ __device__ __forceinline__ float seeded(float v, float seed, float rv, float gv)
 // NI: 16-wide column blocks per wave (the workgroup covers 64 * NI input channels, all of one group when NI > 1)
 template <bool BF, int NI>
 __global__ void __launch_bounds__(THREADS) disc_dgrad_kernel(DgArgs p) {
-  typedef DgOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
   T* A = reinterpret_cast<T*>(dg_smem);
   const int row = blockIdx.y, phase = blockIdx.z % p.stride, ci0 = (blockIdx.z / p.stride) * (NI * 64);
   const int q0 = p.qlo + blockIdx.x * DT;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-  const int rb = row / p.rdiv, rc = row - rb * p.rdiv;
-  const float* Z = p.dZ + rb * p.szb + rc * p.szr;
-  const long xoff = rb * p.sxb + rc * p.sxr;
-  const int U = taps_of_phase(p.taps, p.stride, phase), KST = ksteps(U, p.cgk, Op::KS), K = U * p.cgk;
+  const float* Z = p.dZ + disc_row_offset(row, p.rdiv, p.szb, p.szr);
+  const long xoff = disc_row_offset(row, p.rdiv, p.sxb, p.sxr);
+  const int U = taps_of_phase(p.taps, p.stride, phase), KST = ksteps(U, p.cgk, Op::KS);
   long poff = 0;                                                         // this phase's part of the pack, in lanes' 16-byte fragments
   for (int f = 0; f < phase; ++f) poff += ksteps(taps_of_phase(p.taps, p.stride, f), p.cgk, Op::KS);
   poff *= (long)(p.Cin / 16) * p.nchunks * 64;
   const int grp0 = ci0 / p.Cin_g;
   const int cw = p.ng == 1 ? p.cgk : p.ng * p.Cout_g, lda = cw + Op::PAD;
-  const int rows = DT - 1 + U, q4 = cw >> 2, m0 = q0 - (U - 1);
   const int coff = p.ng == 1 ? 0 : ((ci0 + w * 16) / p.Cin_g - grp0) * p.Cout_g;   // this wave's groups inside the staged channels
   const bool active = ci0 + w * 16 < p.Cin;                              // a 16- or 32-channel dense layer leaves waves without columns
-  // The K sum is blocked as in dx_disc_conv: Op::BLOCK k steps run as one MFMA chain from zero, the block sums are added in order.
-  f32x4 acc[NI][4], part[NI][4];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = part[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int top = U - 1;             // window row of dZ position q - u: top - u (spelled U - 1 - u it costs the k loop an instruction)
+  f32x4 acc[NI][4] = {}, part[NI][4] = {};
   for (int ch = 0; ch < p.nchunks; ++ch) {
-    const int co0 = grp0 * p.Cout_g + ch * p.cgk;
     __syncthreads();
-    for (int e = threadIdx.x; e < rows * q4; e += THREADS) {
-      const int rr = e / q4, cc = (e - rr * q4) * 4, m = m0 + rr;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (m >= 0 && m < p.Nout) v = *reinterpret_cast<const float4*>(Z + (long)m * p.szn + co0 + cc);
-      T* d = A + rr * lda + cc;
-      d[0] = Op::cvt(v.x); d[1] = Op::cvt(v.y); d[2] = Op::cvt(v.z); d[3] = Op::cvt(v.w);
-    }
+    disc_stage<BF>(A, lda, Z + (grp0 * p.Cout_g + ch * p.cgk), p.szn, q0 - (U - 1), p.Nout, DT - 1 + U, cw >> 2, [](int rr) { return rr; });
     __syncthreads();
     if (!active) continue;
-    for (int ks = 0; ks < KST; ++ks) {
-      if ((ks & (Op::BLOCK - 1)) == 0) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            acc[i][j] += part[i][j];
-            part[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-          }
-      }
-      const int k0 = ks * Op::KS + g * Op::VEC;
-      const bool valid = k0 < K;                                         // past K the pack holds zeros; A must not be read there
-      const int u = valid ? k0 >> p.lg : 0, c = k0 & (p.cgk - 1);
-      const T* ap = A + (U - 1 - u + r) * lda + coff + c;                // window row of dZ position q - u
-      uint4 b[NI];
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-        b[i] = p.Wp[poff + (((long)(ci0 / 16 + w + 4 * i) * p.nchunks + ch) * KST + ks) * 64 + lane];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint4 a = make_uint4(0u, 0u, 0u, 0u);
-        if (valid) a = *reinterpret_cast<const uint4*>(ap + j * 16 * lda);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) part[i][j] = Op::mma(a, b[i], part[i][j]);
-      }
-    }
+    disc_chunk_mma<BF>(A, lda, coff, p.Wp + poff + ((long)(ci0 / 16 + w) * p.nchunks + ch) * KST * 64, 4L * p.nchunks * KST * 64, KST,
+                       U * p.cgk, p.lg, p.cgk - 1, [=](int u) { return top - u; }, acc, part);
   }
   if (!active) return;
   const float seed = p.epi ? p.gw[0] * p.fm_scale : 0.f;
@@ -181,26 +118,21 @@ __global__ void __launch_bounds__(THREADS) disc_dgrad_kernel(DgArgs p) {
 // chunk * cgk + c; zero past the phase's taps and where that output channel is not in ci's group.  W is (Cout, Cin_g, taps).
 template <bool BF>
 __global__ void disc_dgrad_pack_kernel(const float* W, void* out, int Cin, int Cin_g, int Cout_g, int taps, int stride, DgGeom q, long total) {
-  typedef DgOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
-  const int v = (int)(e % Op::VEC);
-  long f = e / Op::VEC;
-  const int lane = (int)(f % 64); f /= 64;
+  DiscPackIdx x = disc_pack_lane<BF>(e);
   int phase = 0, U = 0, KST = 0;
   for (; phase < stride; ++phase) {
     U = taps_of_phase(taps, stride, phase);
     KST = ksteps(U, q.cgk, Op::KS);
     const long per = (long)(Cin / 16) * q.nchunks * KST;
-    if (f < per) break;
-    f -= per;
+    if (x.f < per) break;
+    x.f -= per;
   }
-  const int ks = (int)(f % KST); f /= KST;
-  const int ch = (int)(f % q.nchunks); f /= q.nchunks;
-  const int nb = (int)f;
-  const int k = ks * Op::KS + (lane >> 4) * Op::VEC + v, ci = nb * 16 + (lane & 15);
-  const int u = k >> q.lg, c = k & (q.cgk - 1), t = phase + stride * u;
-  const int co = ((nb * 16) / Cin_g) * Cout_g + ch * q.cgk + c;
+  disc_pack_step<BF>(x, KST, q.nchunks);
+  const int ci = x.n, u = x.k >> q.lg, c = x.k & (q.cgk - 1), t = phase + stride * u;
+  const int co = ((x.nb * 16) / Cin_g) * Cout_g + x.ch * q.cgk + c;
   float val = 0.f;
   if (u < U && t < taps && co / Cout_g == ci / Cin_g) val = W[((long)co * Cin_g + ci % Cin_g) * taps + t];
   reinterpret_cast<typename Op::T*>(out)[e] = Op::cvt(val);
@@ -208,7 +140,7 @@ __global__ void disc_dgrad_pack_kernel(const float* W, void* out, int Cin, int C
 
 template <bool BF, int NI>
 int launch_dgrad(const DgArgs& a, int rows, hipStream_t s) {
-  typedef DgOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const int cw = a.ng == 1 ? a.cgk : a.ng * a.Cout_g;
   const int U0 = taps_of_phase(a.taps, a.stride, 0);
   const size_t smem = (size_t)(DT - 1 + U0) * (cw + Op::PAD) * sizeof(typename Op::T);
@@ -246,8 +178,8 @@ __global__ void __launch_bounds__(THREADS) disc_post_bwd_kernel(const float* Sr,
   long pos = e / c4;
   const int n = (int)(pos % N);
   const int row = (int)(pos / N);
-  const int rb = row / rdiv, rc = row - rb * rdiv, pad = (taps - 1) / 2;
-  const long so = rb * ssb + rc * ssr;
+  const int pad = (taps - 1) / 2;
+  const long so = disc_row_offset(row, rdiv, ssb, ssr);
   const float wgen = gw_gen[0] * s_scale, wfm = gw_fm[0] * s_scale;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   for (int t = 0; t < taps; ++t) {
@@ -259,7 +191,7 @@ __global__ void __launch_bounds__(THREADS) disc_post_bwd_kernel(const float* Sr,
     a2 = __builtin_fmaf(ds, W[(long)(c + 2) * taps + t], a2);
     a3 = __builtin_fmaf(ds, W[(long)(c + 3) * taps + t], a3);
   }
-  const long off = rb * sxb + rc * sxr + (long)n * sxn + c;
+  const long off = disc_row_offset(row, rdiv, sxb, sxr) + (long)n * sxn + c;
   if (epi) {
     const float seed = gw_fm[0] * fm_scale;
     const float4 rv = *reinterpret_cast<const float4*>(R + off), gv = *reinterpret_cast<const float4*>(G + off);
@@ -320,8 +252,6 @@ __global__ void __launch_bounds__(THREADS) disc_pool_bwd_kernel(const float* dy,
   dx[e] = accumulate ? dx[e] + s : s;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 bool dgrad_shape_ok(int Cin, int Cout, int groups, int taps, int stride, int bf16, DgGeom* q) {
   return (bf16 == 0 || bf16 == 1) && taps > 0 && taps <= 41 && stride >= 1 && stride <= 4 && taps >= stride && dgrad_geom(Cin, Cout, groups, q);
 }
@@ -372,7 +302,7 @@ int dx_disc_conv_dgrad(const float* dZ, long szb, long szr, long szn, const void
   DX_REQUIRE(dgrad_geom(Cin, Cout, groups, &q),
              "dx_disc_conv_dgrad: unsupported shape (Cin %% 16 == 0; input channels per group 8, 16, 32 or a multiple of 64; output channels "
              "per group 16, 32 or a multiple of 64)");
-  DX_REQUIRE(szn % 4 == 0 && szr % 4 == 0 && szb % 4 == 0 && aligned16(dZ),
+  DX_REQUIRE(szn % 4 == 0 && szr % 4 == 0 && szb % 4 == 0 && dx_aligned16(dZ),
              "dx_disc_conv_dgrad: dZ needs strides %% 4 == 0 and a 16-byte aligned pointer");
   DgArgs a;
   a.dZ = dZ; a.szb = szb; a.szr = szr; a.szn = szn;
@@ -393,7 +323,7 @@ int dx_disc_post_bwd(const float* Sr, const float* Sg, long ssb, long ssr, long 
   DX_REQUIRE(!epilogue || (R && G), "dx_disc_post_bwd: null pointer (the epilogue needs R and G)");
   DX_REQUIRE(rows > 0 && rdiv > 0 && N > 0 && C > 0 && C % 4 == 0 && taps > 0 && taps % 2 == 1,
              "dx_disc_post_bwd: bad shape (positive sizes, C %% 4 == 0, odd taps)");
-  DX_REQUIRE(sxn % 4 == 0 && sxr % 4 == 0 && sxb % 4 == 0 && aligned16(dZ) && (!epilogue || (aligned16(R) && aligned16(G))),
+  DX_REQUIRE(sxn % 4 == 0 && sxr % 4 == 0 && sxb % 4 == 0 && dx_aligned16(dZ) && (!epilogue || (dx_aligned16(R) && dx_aligned16(G))),
              "dx_disc_post_bwd: the maps need strides %% 4 == 0 and 16-byte aligned pointers");
   const long total = (long)rows * N * (C / 4);
   DX_REQUIRE((total + THREADS - 1) / THREADS <= 0x7fffffffL, "dx_disc_post_bwd: too many outputs for one launch");
@@ -410,7 +340,7 @@ int dx_disc_first_bwd(const float* dZ, const float* W, float* dy, long sdb, int 
              "dx_disc_first_bwd: non-positive size (Cout %% 4 == 0, sdb >= T)");
   DX_REQUIRE(accumulate == 0 || accumulate == 1, "dx_disc_first_bwd: bad accumulate flag");
   DX_REQUIRE(T % p == 0 || p - T % p < T, "dx_disc_first_bwd: the reflect padding (p - T %% p samples) must be shorter than the signal");
-  DX_REQUIRE(aligned16(dZ), "dx_disc_first_bwd: dZ must be 16-byte aligned");
+  DX_REQUIRE(dx_aligned16(dZ), "dx_disc_first_bwd: dZ must be 16-byte aligned");
   const int H = dx_cdiv(T, p);
   DX_REQUIRE(H + 2 * pad >= taps, "dx_disc_first_bwd: unsupported shape (H + 2 pad >= taps)");
   const int Hout = (H + 2 * pad - taps) / stride + 1;

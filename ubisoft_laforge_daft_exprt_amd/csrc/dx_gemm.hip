@@ -56,10 +56,7 @@ struct ConvGemmArgs {
 template <typename T> struct Mma;
 template <> struct Mma<float> {
   static __device__ __forceinline__ void run(const float4& a, const float4& b, f32x4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
+    c = dx_mma_f32_k16(f32x4{a.x, a.y, a.z, a.w}, f32x4{b.x, b.y, b.z, b.w}, c);
   }
 };
 template <> struct Mma<dx_h16> {

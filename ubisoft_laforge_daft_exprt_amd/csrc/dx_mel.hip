@@ -33,15 +33,6 @@ struct MelArgs {
   float clip;
 };
 
-__device__ __forceinline__ f32x4 mma4(const f32x4& a, const uint4& b4, f32x4 c) {
-  const f32x4 b = __builtin_bit_cast(f32x4, b4);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-  return c;
-}
-
 __host__ __device__ inline int mel_lds_floats(int kmaxp, int n_mels) {
   const int win = (MF + 3) * SEGW, mag = MF * (kmaxp + 4);
   return (win > mag ? win : mag) + MF * (n_mels + 1);
@@ -85,7 +76,7 @@ __device__ __forceinline__ void dft_gemm(const float* Wd, const uint4* Bp, int r
 #pragma unroll
       for (int c = 0; c < 2; ++c)
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb) acc[i][c][mb] += mma4(a[mb], bc[i][c], f32x4{0.f, 0.f, 0.f, 0.f});
+        for (int mb = 0; mb < 2; ++mb) acc[i][c][mb] += dx_mma_f32_k16(a[mb], __builtin_bit_cast(f32x4, bc[i][c]), f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
     for (int i = 0; i < NKB; ++i)
 #pragma unroll
@@ -141,7 +132,7 @@ __global__ void __launch_bounds__(THREADS) mel_kernel(MelArgs p) {
     f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f};
     const uint4* Fp = p.fb + (long)nb * KS2 * 64 + lane;
     const float* A = Mg + (mb * 16 + r) * ldm + 4 * g;
-    for (int ks = 0; ks < KS2; ++ks) c = mma4(*reinterpret_cast<const f32x4*>(A + ks * 16), Fp[ks * 64], c);
+    for (int ks = 0; ks < KS2; ++ks) c = dx_mma_f32_k16(*reinterpret_cast<const f32x4*>(A + ks * 16), __builtin_bit_cast(f32x4, Fp[ks * 64]), c);
     const int n = nb * 16 + r;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -245,7 +236,7 @@ __global__ void __launch_bounds__(THREADS) mel_bwd_kernel(MelBwdArgs p) {
     f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f};
     const uint4* Fp = p.fb + (long)nb * KS2 * 64 + lane;
     const float* A = Mg + (mb * 16 + r) * ldm + 4 * g;
-    for (int ks = 0; ks < KS2; ++ks) c = mma4(*reinterpret_cast<const f32x4*>(A + ks * 16), Fp[ks * 64], c);
+    for (int ks = 0; ks < KS2; ++ks) c = dx_mma_f32_k16(*reinterpret_cast<const f32x4*>(A + ks * 16), __builtin_bit_cast(f32x4, Fp[ks * 64]), c);
     const int n = nb * 16 + r;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -262,9 +253,9 @@ __global__ void __launch_bounds__(THREADS) mel_bwd_kernel(MelBwdArgs p) {
     f32x4 c[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     const uint4* Fp = p.fbT + (long)(w * NKB + i) * NB * 64 + lane;
     for (int ks = 0; ks < NB; ++ks) {
-      const uint4 f = Fp[ks * 64];
+      const f32x4 f = __builtin_bit_cast(f32x4, Fp[ks * 64]);
 #pragma unroll
-      for (int mb = 0; mb < 2; ++mb) c[mb] = mma4(*reinterpret_cast<const f32x4*>(Dl + (mb * 16 + r) * ldl + ks * 16 + 4 * g), f, c[mb]);
+      for (int mb = 0; mb < 2; ++mb) c[mb] = dx_mma_f32_k16(*reinterpret_cast<const f32x4*>(Dl + (mb * 16 + r) * ldl + ks * 16 + 4 * g), f, c[mb]);
     }
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
@@ -300,9 +291,9 @@ __global__ void __launch_bounds__(THREADS) mel_bwd_kernel(MelBwdArgs p) {
       for (int mb = 0; mb < 2; ++mb) a[mb] = *reinterpret_cast<const f32x4*>(D + (mb * 16 + r) * LDD + ks * 16 + 4 * g);
 #pragma unroll
       for (int cb = 0; cb < 16; ++cb) {
-        const uint4 t4 = Tp[((long)cb * NKB * (DCH / 16) + ks) * 64];
+        const f32x4 t4 = __builtin_bit_cast(f32x4, Tp[((long)cb * NKB * (DCH / 16) + ks) * 64]);
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb) out[cb][mb] += mma4(a[mb], t4, f32x4{0.f, 0.f, 0.f, 0.f});
+        for (int mb = 0; mb < 2; ++mb) out[cb][mb] += dx_mma_f32_k16(a[mb], t4, f32x4{0.f, 0.f, 0.f, 0.f});
       }
     }
   }

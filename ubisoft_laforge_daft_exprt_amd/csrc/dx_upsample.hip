@@ -220,11 +220,7 @@ struct UpBwdArgs {
 
 // four v_mfma_f32_16x16x4_f32 over 16 consecutive k: a / b = the lane's 4 consecutive k values (k = 4 (lane / 16) + e) of row (lane % 16)
 __device__ __forceinline__ f32x4 up_mma4(const float4& a, const float4& b, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
-  return c;
+  return dx_mma_f32_k16(f32x4{a.x, a.y, a.z, a.w}, f32x4{b.x, b.y, b.z, b.w}, c);
 }
 
 // grid (ceil(T/TT), B), 256 threads.  LDS: g[TT][D+4] (dx_up tile), dw[Lp][TT], w[Lp][TT+4], inner[256], and one region that holds the

@@ -27,35 +27,12 @@ constexpr int THREADS = 256;
 
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * VOC_SLOPE; }
 
-template <bool BF> struct VocOp;
-template <> struct VocOp<false> {
-  typedef float T;
-  static constexpr int KS = 16, VEC = 4, PAD = 4;
-  __device__ static __forceinline__ T cvt(float v) { return v; }
-  __device__ static __forceinline__ f32x4 mma(const uint4& a4, const uint4& b4, f32x4 c) {
-    const f32x4 a = __builtin_bit_cast(f32x4, a4), b = __builtin_bit_cast(f32x4, b4);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-    return c;
-  }
-};
-template <> struct VocOp<true> {
-  typedef __bf16 T;
-  static constexpr int KS = 32, VEC = 8, PAD = 8;
-  __device__ static __forceinline__ T cvt(float v) { return (__bf16)v; }
-  __device__ static __forceinline__ f32x4 mma(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dx_bf16x8, a), __builtin_bit_cast(dx_bf16x8, b), c, 0, 0, 0);
-  }
-};
-
 // A[rr][cc] = lrelu?(X[b][row0 + rr][c0 + cc]) for rr < R, cc < kcw; 0 outside [0, len) x [0, Cin).  Channels-last rows (sxc == 1,
 // sxn >= Cin) are read as float4; any other layout (the (B, 80, T) mel, whose channel stride is 1 too when T == 1) element-wise.
 template <bool BF>
-__device__ __forceinline__ void voc_stage(typename VocOp<BF>::T* A, int lda, int R, const float* X, long sxn, long sxc,
+__device__ __forceinline__ void voc_stage(typename DxMmaOp<BF>::T* A, int lda, int R, const float* X, long sxn, long sxc,
                                           int row0, int len, int c0, int kcw, int Cin, int pro) {
-  typedef VocOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   if (sxc == 1 && sxn >= Cin) {
     const int q = kcw >> 2;
     for (int e = threadIdx.x; e < R * q; e += THREADS) {
@@ -84,9 +61,9 @@ __device__ __forceinline__ void voc_stage(typename VocOp<BF>::T* A, int lda, int
 // acc[i][j] += sum_t sum_{k step s < nks} A[(16 mb_j + row + t*dil)][s*KS ...] * W[t][nb_i][ks0 + s]
 // wave (wn, wm) owns column blocks nb_i = wn + i*WN and row blocks mb_j = wm + j*WM (< MB).
 template <bool BF, int NI, int MI>
-__device__ __forceinline__ void voc_mma(const typename VocOp<BF>::T* A, int lda, int MB, int taps, int dil, const uint4* Wp,
+__device__ __forceinline__ void voc_mma(const typename DxMmaOp<BF>::T* A, int lda, int MB, int taps, int dil, const uint4* Wp,
                                         int NB, int KST, int ks0, int nks, int wn, int WN, int wm, int WM, f32x4 (&acc)[NI][MI]) {
-  typedef VocOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   for (int t = 0; t < taps; ++t) {
     for (int s = 0; s < nks; ++s) {
@@ -123,7 +100,7 @@ struct ConvArgs {
 // One conv (up == 1) or one phase of a transposed conv (up > 1, grid.z = phase) on a 64-sample tile of one batch row.
 template <bool BF, int NI, int MI>
 __global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p) {
-  typedef VocOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
   T* A = reinterpret_cast<T*>(voc_smem);
@@ -197,7 +174,7 @@ struct PairArgs {
 // Y = acc_mode( conv2(lrelu(conv1(lrelu(X)) + b1)) + b2 + X ): one ResBlock1 pair, intermediate (80 rows with halo) in LDS.
 template <bool BF, int MI1, int MI2>
 __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p) {
-  typedef VocOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
   const int b = blockIdx.y, s0 = blockIdx.x * VT, C = p.C;
@@ -299,7 +276,7 @@ __global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long 
 // up == 1: W (Cout, Cin, taps); up > 1: W (Cin, Cout, 2 up) of a ConvTranspose1d, tap t of phase r = kernel index j0(r) - t*up.
 template <bool BF>
 __global__ void voc_pack_kernel(const float* W, void* out, int Cout, int Cin, int taps, int up, int KST, long total) {
-  typedef VocOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
   const int NB = Cout / 16, v = (int)(e % Op::VEC);
@@ -329,7 +306,7 @@ long voc_pack_elems(int Cout, int Cin, int taps, int up, int bf16) {
 
 template <bool BF, int NI, int MI>
 int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
-  typedef VocOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const size_t smem = (size_t)(VT + (a.taps - 1) * a.dil) * (KC + Op::PAD) * sizeof(typename Op::T);
   hipLaunchKernelGGL((voc_conv_kernel<BF, NI, MI>), dim3(dx_cdiv(a.N, VT), B, a.up), dim3(THREADS), smem, s, a);
   DX_LAUNCH_CHECK("dx_voc_conv");
@@ -349,7 +326,7 @@ int dispatch_conv(const ConvArgs& a, int B, hipStream_t s) {
 
 template <bool BF, int MI1, int MI2>
 int launch_pair(const PairArgs& a, int B, hipStream_t s) {
-  typedef VocOp<BF> Op;
+  typedef DxMmaOp<BF> Op;
   const int h1 = a.dil * (a.taps - 1) / 2;
   const size_t smem = ((size_t)(MIDR + 2 * h1) * (KC + Op::PAD) + (size_t)MIDR * (a.C + Op::PAD)) * sizeof(typename Op::T);
   hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a);

@@ -51,6 +51,22 @@ def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _packed(kind, w, dims, device):
+    """``dx_<kind>_pack`` of the contiguous fp32 device tensor ``w`` -> its operand pack, a uint8 device buffer of the size that
+    ``dx_<kind>_pack_size`` reports; ``dims``: the arguments the two entry points share."""
+    L = lib()
+    nbytes = torch.zeros(1, dtype=torch.long)
+    getattr(L, f'dx_{kind}_pack_size')(*dims, nbytes.data_ptr())
+    buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=device)
+    getattr(L, f'dx_{kind}_pack')(w.data_ptr(), buf.data_ptr(), *dims, _stream(device))
+    return buf
+
+
+def _halves(t):
+    """-> the device addresses of the real and the generated half of a (2B, ...) fp32 buffer."""
+    return t.data_ptr(), t.data_ptr() + 4 * (t.numel() // 2)
+
+
 def _frozen(t):
     return nn.Parameter(t, requires_grad=False)
 
@@ -192,34 +208,25 @@ class _SubDiscriminator(nn.Module):
 
     def _device_weights(self):
         if self._packs is None:
-            L, bf16 = lib(), PRECISIONS[self.precision]
+            bf16 = PRECISIONS[self.precision]
             F = self.folded()
             dev = self.conv_post.bias.device
             P = {'convs.0': F['convs.0'], 'conv_post': F['conv_post']}
             for i, (cin, cout, k, _, g, _) in enumerate(self.LAYERS[1:], 1):
                 w, b = F[f'convs.{i}']
-                nbytes = torch.zeros(1, dtype=torch.long)
-                L.dx_disc_pack_size(cout, cin // g, k, bf16, nbytes.data_ptr())
-                buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=dev)
-                L.dx_disc_pack(w.data_ptr(), buf.data_ptr(), cout, cin // g, k, bf16, _stream(dev))
-                P[f'convs.{i}'] = (buf, b)
+                P[f'convs.{i}'] = (_packed('disc', w, (cout, cin // g, k, bf16), dev), b)
             self._packs = P
         return self._packs
 
     def _dgrad_weights(self):
         """The transposed, per-stride-phase packs of dx_disc_conv_dgrad, built on the first backward only."""
         if self._dgrad is None:
-            L, bf16 = lib(), PRECISIONS[self.precision]
+            bf16 = PRECISIONS[self.precision]
             F = self.folded()
             dev = self.conv_post.bias.device
             P = {}
             for i, (cin, cout, k, s, g, _) in enumerate(self.LAYERS[1:], 1):
-                w = F[f'convs.{i}'][0]
-                nbytes = torch.zeros(1, dtype=torch.long)
-                L.dx_disc_dgrad_pack_size(cin, cout, g, k, s, bf16, nbytes.data_ptr())
-                buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=dev)
-                L.dx_disc_dgrad_pack(w.data_ptr(), buf.data_ptr(), cin, cout, g, k, s, bf16, _stream(dev))
-                P[i] = buf
+                P[i] = _packed('disc_dgrad', F[f'convs.{i}'][0], (cin, cout, g, k, s, bf16), dev)
             self._dgrad = P
         return self._dgrad
 
@@ -230,10 +237,9 @@ class _SubDiscriminator(nn.Module):
         L, st, bf16 = lib(), _stream(score.device), PRECISIONS[self.precision]
         P, D = self._device_weights(), self._dgrad_weights()
         gen, fm = gw.data_ptr() + 4 * i_gen, gw.data_ptr() + 4 * i_fm
-        half = lambda t: (t.data_ptr(), t.data_ptr() + 4 * (t.numel() // 2))
         N, C = score.shape[1], POST[0]
         last = fmaps[-1]
-        (sr, sg), (r, g) = half(score), half(last)
+        (sr, sg), (r, g) = _halves(score), _halves(last)
         cur, nxt = dz
         L.dx_disc_post_bwd(sr, sg, N * p, 1, p, P['conv_post'][0].data_ptr(), cur.data_ptr(), r, g, N * p * C, C, p * C, gen, fm,
                            2.0 / (score.numel() // 2), 2.0 / (last.numel() // 2), B * p, p, N, C, POST[2], 1, st)
@@ -241,7 +247,7 @@ class _SubDiscriminator(nn.Module):
             cin, cout, k, s, grp, pad = self.LAYERS[i]
             below = fmaps[i - 1]
             n_in, n_out = below.shape[1], fmaps[i].shape[1]
-            r, g = half(below)
+            r, g = _halves(below)
             L.dx_disc_conv_dgrad(cur.data_ptr(), n_out * p * cout, cout, p * cout, D[i].data_ptr(), nxt.data_ptr(), r, g, n_in * p * cin, cin,
                                  p * cin, fm, 2.0 / (below.numel() // 2), B * p, p, n_in, cin, cout, grp, k, s, pad, 1, bf16, st)
             cur, nxt = nxt, cur

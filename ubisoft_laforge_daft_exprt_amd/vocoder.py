@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from ._lib import lib
+from .discriminators import _packed
 
 NEG_SLOPE = 0.1     # leaky-ReLU slope before every convolution (applied inside the kernels)
 HOP = 256           # waveform samples per mel frame: the product of the four upsampling factors
@@ -158,12 +159,7 @@ class HiFiGanVocoder:
             taps = 2
         else:
             cout, cin, taps = w.shape
-        nbytes = torch.zeros(1, dtype=torch.long)
-        lib().dx_voc_pack_size(cout, cin, taps, up, bf16, nbytes.data_ptr())
-        buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=self.device)
-        wd = w.to(self.device).contiguous()
-        lib().dx_voc_pack(wd.data_ptr(), buf.data_ptr(), cout, cin, taps, up, bf16, _stream(self.device))
-        return buf
+        return _packed('voc', w.to(self.device).contiguous(), (cout, cin, taps, up, bf16), self.device)
 
     def _device_weights(self):
         if self._packs is None:
