@@ -742,7 +742,8 @@ __device__ __forceinline__ void stage_tile_bf16(unsigned char* dst, const float*
 }
 
 // software pipeline: the NEXT tile's rows are fetched into registers (4 x 16 bytes per thread per tensor) before the current
-// tile's MFMA/softmax work, and converted + written to LDS after it
+// tile's MFMA/softmax work, and converted + written to LDS after it.  (Macros on purpose: as inline functions the loops of the
+// fp32-stored variants of both backward kernels come out 3 to 5 instructions longer.  They use the `tid` of the scope they expand in.)
 #define DX_TILE_LOAD(QT_, REG, BASE, LD, COL0, R0, NROWS)                                                         \
   if constexpr (sizeof(QT_) == 4) {                                                                               \
     _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                                           \
@@ -821,6 +822,11 @@ __device__ __forceinline__ void store4(dx_h16* p, float a, float b, float c, flo
   bf16x4 h; h[0] = (dx_h16)a; h[1] = (dx_h16)b; h[2] = (dx_h16)c; h[3] = (dx_h16)d;
   *reinterpret_cast<bf16x4*>(p) = h;
 }
+// a lane's 4 x 4 channels of a 64-wide row slice, zeroed: what the 16-bit kernels leave in a padding tile (first row >= len)
+template <typename T> __device__ __forceinline__ void zero_row64(T* out, int g) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) store4(out + dt * 16 + g * 4, 0.f, 0.f, 0.f, 0.f);
+}
 #define DX_MFMA_BF16(A, B, C) DX_MFMA_H16((A), (B), (C))
 __device__ __forceinline__ float dx_max2(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, INFINITY); }   // no NaNs here: scores are finite or -inf
 // (fmaxf() makes hipcc canonicalise every operand first - a v_max_f32 x, x, x each, 16 per key tile.  An inline-asm v_max3_f32 on the
@@ -828,28 +834,16 @@ __device__ __forceinline__ float dx_max2(float a, float b) { return __builtin_am
 // accumulators before the matrix pipe had written them - maxima of stale data, a 0.4 % output error that the eager-vs-graph
 // bitwise test caught.  Inline asm may only consume values that an ordinary VALU instruction produced.)
 
-template <typename QT, typename CT>
-__global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_) {
-  AttnArgs a = a_;
-  if (a.seed_offset) a.seed += *a.seed_offset;
-  __shared__ __attribute__((aligned(16))) unsigned char Ks[64 * 128];
-  __shared__ __attribute__((aligned(16))) unsigned char Vs[64 * 128];
-  const AttnBlock blk = attn_block(a.xcd_map);
-  const int b = a.order ? a.order[blk.z] : blk.z, h = blk.h, q0 = blk.tile * 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// The key loop of the 16-bit forward, from the Q fragments to the last P V MFMA: one wave = 16 query rows (lane: row qrow, 4 x 4 of its
+// 64 context channels in o) against every key tile of utterance b, head h, with the online softmax in base 2 (m_run, l_run; o is NOT yet
+// divided by l_run).  Ks / Vs = the K and V images of the 256 threads (tid) that walk this head.  attn_fwd_bf16_kernel and
+// attn_proj_ln_fwd_kernel both run it: same arithmetic, same dropout draws, same bits.
+struct AttnRowState { f32x4 o[4]; float m_run, l_run; };
+template <typename QT>
+__device__ __forceinline__ AttnRowState attn_key_loop(const AttnArgs& a, lds_bytes Ks3, lds_bytes Vs3, int tid, int qrow, int h, int b, int len, int lane) {
+  unsigned char* const Ks = (unsigned char*)Ks3; unsigned char* const Vs = (unsigned char*)Vs3;
   const int r = lane & 15, g = lane >> 4;
-  const int len = a.lens[b];
   const QT* base = reinterpret_cast<const QT*>(a.qkv) + (size_t)b * a.N * a.ld;
-  const int qrow = q0 + wave * 16 + r;
-  CT* out = reinterpret_cast<CT*>(a.ctx) + ((size_t)b * a.N + qrow) * a.ldc + h * HD;
-  if (q0 >= len) {
-    if (qrow < a.N) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store4(out + dt * 16 + g * 4, 0.f, 0.f, 0.f, 0.f);
-      if (g == 0) a.lse[((size_t)b * a.H + h) * a.N + qrow] = 0.f;
-    }
-    return;
-  }
   const int qload = min(qrow, a.N - 1);
   bf16x8 qf[2];
 #pragma unroll
@@ -935,6 +929,32 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_
       o[dt] = acc;
     }
   }
+  return AttnRowState{{o[0], o[1], o[2], o[3]}, m_run, l_run};
+}
+
+template <typename QT, typename CT>
+__global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_) {
+  AttnArgs a = a_;
+  if (a.seed_offset) a.seed += *a.seed_offset;
+  __shared__ __attribute__((aligned(16))) unsigned char Ks[64 * 128];
+  __shared__ __attribute__((aligned(16))) unsigned char Vs[64 * 128];
+  const AttnBlock blk = attn_block(a.xcd_map);
+  const int b = a.order ? a.order[blk.z] : blk.z, h = blk.h, q0 = blk.tile * 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int len = a.lens[b];
+  const int qrow = q0 + wave * 16 + r;
+  CT* out = reinterpret_cast<CT*>(a.ctx) + ((size_t)b * a.N + qrow) * a.ldc + h * HD;
+  if (q0 >= len) {
+    if (qrow < a.N) {
+      zero_row64(out, g);
+      if (g == 0) a.lse[((size_t)b * a.H + h) * a.N + qrow] = 0.f;
+    }
+    return;
+  }
+  const AttnRowState att = attn_key_loop<QT>(a, (lds_bytes)Ks, (lds_bytes)Vs, tid, qrow, h, b, len, lane);
+  const f32x4 (&o)[4] = att.o;
+  const float m_run = att.m_run, l_run = att.l_run;
   if (qrow < a.N) {
     const bool valid = qrow < len;
     const float inv = valid ? (a.thresh ? a.inv_keep : 1.f) / l_run : 0.f;
@@ -954,7 +974,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bf16_kernel(const AttnArgs a_
 // workgroups are still in their key loops (utterances differ in length, so the HBM-bound row pass hides under their VALU-bound loops).
 // Results are bit-identical to the two launches (same operands, same K order, same row arithmetic): the test compares bitwise.
 // ------------------------------------------------------------------------------------------------
-constexpr float APL_LN_EPS = 1e-5f;          // (= LN_EPS of dx_rows.hip)
 struct AttnProjLnArgs {
   AttnArgs at;
   const dx_h16* Wp; const float* proj_bias;                       // out-projection: forward pack of the (128, 128) weight, bias
@@ -976,7 +995,7 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
   const int tid512 = threadIdx.x, lane = tid512 & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid512 >> 6);
   const int h = wave >> 2, wq = wave & 3;
-  const int tid = tid512 & 255;                         // the staging macros walk 256 threads per (head) image
+  const int tid = tid512 & 255;                         // the key loop stages with 256 threads per (head) image
   unsigned char* const Ks = smem + h * (64 * 128);
   unsigned char* const Vs = smem + 2 * 64 * 128 + h * (64 * 128);
   unsigned char* const Cs = smem + 4 * 64 * 128;        // [64 rows][256 B]: 16 slots of 8 channels, slot ^ (row & 15)
@@ -988,15 +1007,13 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
   const int b = (j / ntx) * 8 + xcd, q0 = (j - (j / ntx) * ntx) * 64;
   if (b >= a.B) return;
   const int len = a.lens[b];
-  const QT* base = reinterpret_cast<const QT*>(a.qkv) + (size_t)b * a.N * a.ld;
   const int qrow = q0 + wq * 16 + r;
   CT* out = reinterpret_cast<CT*>(a.ctx) + ((size_t)b * a.N + qrow) * a.ldc + h * HD;
   constexpr int E = RowVec<C>::E, LPR = RowVec<C>::LPR;
   const int l = lane % LPR, sub = lane / LPR;
   if (q0 >= len) {                                      // a padding tile: what the two launches leave there
     if (qrow < a.N) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store4(out + dt * 16 + g * 4, 0.f, 0.f, 0.f, 0.f);
+      zero_row64(out, g);
       if (g == 0) a.lse[((size_t)b * a.H + h) * a.N + qrow] = 0.f;
     }
     float zero[E];
@@ -1015,85 +1032,9 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
     }
     return;
   }
-  const int qload = min(qrow, a.N - 1);
-  bf16x8 qf[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) qf[ks] = load_row8(base + (size_t)qload * a.ld + h * HD + ks * 32 + g * 8, QSCALE2);
-  f32x4 o[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m_run = -INFINITY, l_run = 0.f;
-  const int bh = b * a.H + h;
-  const int ntiles = (len + 63) / 64;
-  const uint64_t drow = (uint64_t)((size_t)bh * a.N + qrow) << 14;
-  const uint32_t thresh_v = a.thresh;
-  f32x4 kreg[4], vreg[4];
-  DX_TILE_LOAD(QT, kreg, base, a.ld, a.D + h * HD, 0, a.N)
-  DX_TILE_LOAD(QT, vreg, base, a.ld, 2 * a.D + h * HD, 0, a.N)
-  for (int kt0 = 0; kt0 < ntiles; ++kt0) {
-    const int kbase = kt0 * 64;
-    __syncthreads();
-    DX_TILE_STORE(QT, kreg, Ks)
-    DX_TILE_STORE(QT, vreg, Vs)
-    __syncthreads();
-    if (kt0 + 1 < ntiles) {
-      DX_TILE_LOAD(QT, kreg, base, a.ld, a.D + h * HD, kbase + 64, a.N)
-      DX_TILE_LOAD(QT, vreg, base, a.ld, 2 * a.D + h * HD, kbase + 64, a.N)
-    }
-    f32x4 st[4];
-    float mx = -INFINITY;
-    const bool tail_tile = kbase + 64 > len;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) acc = DX_MFMA_BF16(row_frag(Ks, kt * 16 + r, ks, g), qf[ks], acc);
-      if (tail_tile) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (kbase + kt * 16 + g * 4 + e >= len) acc[e] = -INFINITY;
-      }
-      mx = dx_max2(mx, dx_max2(dx_max2(acc[0], acc[1]), dx_max2(acc[2], acc[3])));
-      st[kt] = acc;
-    }
-    mx = dx_max2(mx, __shfl_xor(mx, 16, 64));
-    mx = dx_max2(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = dx_max2(m_run, mx);
-    const bool rescale = __builtin_amdgcn_ballot_w64(m_new > m_run) != 0;
-    float ls = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      float pk[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pk[e] = __builtin_amdgcn_exp2f(st[kt][e] - m_new);
-        ls += pk[e];
-      }
-      if (a.thresh) dx_keep4(dx_rand64(a.seed, drow | (uint64_t)((kbase + kt * 16 + g * 4) >> 2)), thresh_v, pk, 0.f);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) st[kt][e] = pk[e];
-    }
-    ls += __shfl_xor(ls, 16, 64);
-    ls += __shfl_xor(ls, 32, 64);
-    if (rescale) {
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[dt][e] *= alpha;
-    }
-    l_run += ls;
-    m_run = m_new;
-    const bf16x8 p01 = pack_pair(st[0], st[1]), p23 = pack_pair(st[2], st[3]);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      f32x4 acc = o[dt];
-      acc = DX_MFMA_BF16(tr_pair(Vs, 0 + g * 4, 16 + g * 4, dt * 16, lane), p01, acc);
-      acc = DX_MFMA_BF16(tr_pair(Vs, 32 + g * 4, 48 + g * 4, dt * 16, lane), p23, acc);
-      o[dt] = acc;
-    }
-  }
+  const AttnRowState att = attn_key_loop<QT>(a, (lds_bytes)Ks, (lds_bytes)Vs, tid, qrow, h, b, len, lane);
+  const f32x4 (&o)[4] = att.o;
+  const float m_run = att.m_run, l_run = att.l_run;
   // ---- context: to HBM as before, and (the very same 16-bit values) into the LDS image the projection reads ----------------------------
   {
     const bool valid = qrow < len;
@@ -1110,23 +1051,15 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
     if (qrow < a.N && g == 0) a.lse[((size_t)b * a.H + h) * a.N + qrow] = valid ? m_run + __log2f(l_run) : 0.f;
   }
   // the row pass's global reads go out before the projection (a workgroup is one dependent chain)
-  bool valid[2]; long rown[2];
-  float rv[2][E];
+  LnRowsAhead<C, 2> ah;
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
     const int n = q0 + wave * 8 + st * 4 + sub;
-    const bool inb = n < a.N;
-    valid[st] = inb && n < len;
-    rown[st] = inb ? (long)b * a.N + n : -1;
-#pragma unroll
-    for (int e = 0; e < E; ++e) rv[st][e] = 0.f;
-    if (valid[st] && p_.res) row_load<C>(p_.res + rown[st] * C, l, rv[st]);
+    ah.request(st, n < a.N, n < a.N && n < len, b, (long)b * a.N + n, p_.res, l);
   }
-  float wv[E], bv[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) { wv[e] = p_.w[row_col<C>(l, e)]; bv[e] = p_.bias[row_col<C>(l, e)]; }
+  row_affine<C>(p_.w, p_.bias, l, ah.wv, ah.bv);
   __syncthreads();                                      // the context image is complete; every K / V read has retired
-  // ---- out-projection: wave = column tile (16 tokens) wq x four of the eight 16-channel row blocks; K order 0..3 as proj_ln_fwd_kernel --------
+  // ---- out-projection: wave = column tile (16 tokens) wq x four of the eight 16-channel row blocks -----------------------------------------
   {
     const int tok = wq * 16 + r;
     const bool live = q0 + tok < len;
@@ -1134,71 +1067,12 @@ __global__ __launch_bounds__(512, 4) void attn_proj_ln_fwd_kernel(const AttnProj
       bf16x8 xb[4];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) xb[ks] = *reinterpret_cast<const bf16x8*>(Cs + tok * 256 + (((ks * 4 + g) ^ (tok & 15)) << 4));
-      f32x4 acc[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        acc[i] = p_.proj_bias ? *reinterpret_cast<const f32x4*>(p_.proj_bias + (h * 4 + i) * 16 + g * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        bf16x8 wa[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) wa[i] = *reinterpret_cast<const bf16x8*>(p_.Wp + (size_t)((h * 4 + i) * 4 + ks) * 512 + lane * 8);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = DX_MFMA_H16(wa[i], xb[ks], acc[i]);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<f32x4*>(tile + tok * C + ((((h * 4 + i) * 4 + g) ^ (tok & 15)) << 2)) = acc[i];
+      proj128_to_tile<4>(xb, p_.Wp, p_.proj_bias, h * 4, lane, tok, (lds_floats)tile);
     }
   }
   __syncthreads();
-  // ---- row pass: exactly phase 2 of proj_ln_fwd_kernel, eight rows per wave in two steps of four -------------------------------------------
-#pragma unroll
-  for (int st = 0; st < 2; ++st) {
-    const int lrow = wave * 8 + st * 4 + sub;
-    const long row = rown[st];
-    const bool inb = row >= 0, vld = valid[st];
-    float z[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) z[e] = 0.f;
-    if (vld) {
-#pragma unroll
-      for (int k = 0; k < RowVec<C>::K; ++k) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(tile + lrow * C + (((k * LPR + l) ^ (lrow & 15)) << 2));
-        z[k * 4 + 0] = t[0]; z[k * 4 + 1] = t[1]; z[k * 4 + 2] = t[2]; z[k * 4 + 3] = t[3];
-      }
-      if (p_.thresh_pre) {
-        float f[E];
-        row_dropout<C>(seed_pre, (uint64_t)row, l, p_.thresh_pre, p_.inv_keep_pre, f);
-#pragma unroll
-        for (int e = 0; e < E; ++e) z[e] *= f[e];
-      }
-#pragma unroll
-      for (int e = 0; e < E; ++e) z[e] += rv[st][e];
-    }
-    if (inb) row_store<C>(p_.z + row * C, l, z);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) s += z[e];
-    const float mu = row_sum<C>(s) * (1.0f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const float d = z[e] - mu; q += d * d; }
-    const float rs = 1.0f / sqrtf(row_sum<C>(q) * (1.0f / C) + APL_LN_EPS);
-    if (inb && l == 0) { p_.mean[row] = vld ? mu : 0.f; p_.rstd[row] = vld ? rs : 0.f; }
-    float y[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int c = row_col<C>(l, e);
-      float t = (z[e] - mu) * rs * wv[e] + bv[e];
-      if (p_.film) t = p_.film[(size_t)b * p_.ld_film + c] * t + p_.film[(size_t)b * p_.ld_film + C + c];
-      y[e] = vld ? t : 0.f;
-    }
-    if (inb) {
-      row_store<C>(p_.y + row * C, l, y);
-      if (p_.y_h) row_store<C>(p_.y_h + row * C, l, y);
-    }
-  }
+  // ---- row pass: eight rows per wave in two steps of four ----------------------------------------------------------------------------------
+  ln_tile_pass<C, 2>((lds_floats)tile, wave * 8, l, sub, ah, seed_pre, p_.thresh_pre, p_.inv_keep_pre, p_.film, p_.ld_film, p_.z, p_.mean, p_.rstd, p_.y, p_.y_h);
 }
 
 // 8 consecutive values of a row as fp32
@@ -1227,10 +1101,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const AttnBwdA
   const int qrow = q0 + wave * 16 + r;
   OT* out = reinterpret_cast<OT*>(a.dqkv) + ((size_t)b * a.N + qrow) * a.ldg + h * HD;
   if (q0 >= len) {
-    if (qrow < a.N) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store4(out + dt * 16 + g * 4, 0.f, 0.f, 0.f, 0.f);
-    }
+    if (qrow < a.N) zero_row64(out, g);
     return;
   }
   const int qload = min(qrow, a.N - 1);
@@ -1344,13 +1215,7 @@ __global__ __launch_bounds__(256, (sizeof(QT) == 2 && sizeof(CT) == 2) ? 3 : 2) 
   OT* outk = reinterpret_cast<OT*>(a.dqkv) + ((size_t)b * a.N + krow) * a.ldg + a.D + h * HD;
   OT* outv = reinterpret_cast<OT*>(a.dqkv) + ((size_t)b * a.N + krow) * a.ldg + 2 * a.D + h * HD;
   if (k0 >= len) {
-    if (krow < a.N) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        store4(outk + dt * 16 + g * 4, 0.f, 0.f, 0.f, 0.f);
-        store4(outv + dt * 16 + g * 4, 0.f, 0.f, 0.f, 0.f);
-      }
-    }
+    if (krow < a.N) { zero_row64(outk, g); zero_row64(outv, g); }
     return;
   }
   const int kload = min(krow, a.N - 1);

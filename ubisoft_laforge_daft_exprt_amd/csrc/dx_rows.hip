@@ -12,8 +12,6 @@
 
 namespace {
 
-constexpr float LN_EPS = 1e-5f;
-
 // ------------------------------------------------------------------------------------------------
 // LayerNorm family.  z = drop_pre(a) + res  (written back over `a`), y = mask(film(drop_post(LN(z))))
 // ------------------------------------------------------------------------------------------------
@@ -46,8 +44,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnArgs a_) {
   const int lane = threadIdx.x & 63, l = lane % LPR, sub = lane / LPR;
   const long rows = (long)a.B * a.N;
   float wv[E], bv[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) { wv[e] = a.w[row_col<C>(l, e)]; bv[e] = a.bias[row_col<C>(l, e)]; }
+  row_affine<C>(a.w, a.bias, l, wv, bv);
+  RowPostDrop<C> post{a.seed_post, a.thresh_post, a.inv_keep_post};
   // the loop bound is wave-uniform; lanes whose row is out of range or padded run the arithmetic on zeros
   for (long base = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW; base < rows; base += (long)gridDim.x * 4 * RPW) {
     const long row = base + sub;
@@ -72,31 +70,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnArgs a_) {
         for (int e = 0; e < E; ++e) z[e] += rv[e];
       }
     }
-    // padded rows: the output is zero by definition and nothing reads z / mean / rstd of them (the backward skips them too)
     if (inb && (a.thresh_pre || a.res)) row_store<C>(A + row * C, l, z);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) s += z[e];
-    const float mu = row_sum<C>(s) * (1.0f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const float d = z[e] - mu; q += d * d; }
-    const float rs = 1.0f / sqrtf(row_sum<C>(q) * (1.0f / C) + LN_EPS);
-    if (inb && l == 0) { a.mean[row] = valid ? mu : 0.f; a.rstd[row] = valid ? rs : 0.f; }
-    float y[E], fpost[E];
-    if (a.thresh_post) row_dropout<C>(a.seed_post, (uint64_t)row, l, a.thresh_post, a.inv_keep_post, fpost);
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int c = row_col<C>(l, e);
-      float t = (z[e] - mu) * rs * wv[e] + bv[e];
-      if (a.thresh_post) t *= fpost[e];
-      if (a.film) t = a.film[(size_t)b * a.ld_film + c] * t + a.film[(size_t)b * a.ld_film + C + c];
-      y[e] = valid ? t : 0.f;
-    }
-    if (inb) {
-      row_store<C>(Y + row * C, l, y);
-      if constexpr (sizeof(IO) == 4 && C < 256) { if (a.y_h) row_store<C>(a.y_h + row * C, l, y); }
-    }
+    ln_row_finish<C, IO>(z, inb, valid, row, b, l, wv, bv, a.film, a.ld_film, post, a.mean, a.rstd, Y, a.y_h);
   }
 }
 
@@ -118,34 +93,23 @@ __global__ __launch_bounds__(256, 3) void proj_ln_fwd_kernel(const ProjLnArgs p_
   constexpr int C = 128;
   LnArgs a = p_.ln;
   if (a.seed_offset) { const uint64_t o = *a.seed_offset; a.seed_pre += o; a.seed_post += o; }
-  constexpr int E = RowVec<C>::E, LPR = RowVec<C>::LPR;
+  constexpr int LPR = RowVec<C>::LPR;
   __shared__ __attribute__((aligned(16))) float tile[64 * C];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int l = lane % LPR, sub = lane / LPR;
   const long rows = (long)a.B * a.N;
   const long row0 = (long)blockIdx.x * 64;
-  // Everything the row pass needs from global memory is requested BEFORE the matrix phase (the residual rows of the lane's four steps,
-  // the LayerNorm affine): a workgroup is one short dependent chain, and with these loads behind the barrier the 5.8 k-row
-  // symbol-level launch took 24 us for 3 MB.
-  bool valid[4]; int bidx[4]; long rown[4];
-  float rv[4][E];
+  LnRowsAhead<C, 4> ah;
 #pragma unroll
   for (int st = 0; st < 4; ++st) {
     const long row = row0 + wave * 16 + st * 4 + sub;
     const bool inb = row < rows;
     const int b = inb ? (int)(row / a.N) : 0, n = inb ? (int)(row - (long)b * a.N) : 0;
-    valid[st] = inb && (!a.lens || n < a.lens[b] + a.halo);
-    bidx[st] = b;
-    rown[st] = inb ? row : -1;
-#pragma unroll
-    for (int e = 0; e < E; ++e) rv[st][e] = 0.f;
-    if (valid[st] && a.res) row_load<C>(a.res + row * C, l, rv[st]);
+    ah.request(st, inb, inb && (!a.lens || n < a.lens[b] + a.halo), b, row, a.res, l);
   }
-  float wv[E], bv[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) { wv[e] = a.w[row_col<C>(l, e)]; bv[e] = a.bias[row_col<C>(l, e)]; }
-  // ---- phase 1: the wave's 16 tokens x 128 output channels (W = A operand, X^T = B operand: a lane owns 4 channels of one token)
+  row_affine<C>(a.w, a.bias, l, ah.wv, ah.bv);
+  // ---- phase 1: the wave's 16 tokens x 128 output channels
   {
     const long trow = row0 + wave * 16 + r;
     const long xrow = trow < rows ? trow : rows - 1;
@@ -158,73 +122,12 @@ __global__ __launch_bounds__(256, 3) void proj_ln_fwd_kernel(const ProjLnArgs p_
       bf16x8 xb[4];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) xb[ks] = *reinterpret_cast<const bf16x8*>(p_.X + xrow * p_.ldx + ks * 32 + g * 8);
-      f32x4 acc[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        acc[i] = p_.proj_bias ? *reinterpret_cast<const f32x4*>(p_.proj_bias + i * 16 + g * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        bf16x8 wa[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wa[i] = *reinterpret_cast<const bf16x8*>(p_.Wp + (size_t)(i * 4 + ks) * 512 + lane * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] = DX_MFMA_H16(wa[i], xb[ks], acc[i]);
-      }
-      const int tok = wave * 16 + r;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        *reinterpret_cast<f32x4*>(tile + tok * C + (((i * 4 + g) ^ (tok & 15)) << 2)) = acc[i];
+      proj128_to_tile<8>(xb, p_.Wp, p_.proj_bias, 0, lane, wave * 16 + r, (lds_floats)tile);
     }
   }
   __syncthreads();
-  // ---- phase 2: ln_fwd_kernel<128> on the tile (4 rows per wave-instruction, 16 lanes x 2 float4 per row), the four steps unrolled
-#pragma unroll
-  for (int st = 0; st < 4; ++st) {
-    const int lrow = wave * 16 + st * 4 + sub;
-    const long row = rown[st];
-    const bool inb = row >= 0, vld = valid[st];
-    const int b = bidx[st];
-    float z[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) z[e] = 0.f;
-    if (vld) {
-#pragma unroll
-      for (int k = 0; k < RowVec<C>::K; ++k) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(tile + lrow * C + (((k * LPR + l) ^ (lrow & 15)) << 2));
-        z[k * 4 + 0] = t[0]; z[k * 4 + 1] = t[1]; z[k * 4 + 2] = t[2]; z[k * 4 + 3] = t[3];
-      }
-      if (a.thresh_pre) {
-        float f[E];
-        row_dropout<C>(a.seed_pre, (uint64_t)row, l, a.thresh_pre, a.inv_keep_pre, f);
-#pragma unroll
-        for (int e = 0; e < E; ++e) z[e] *= f[e];
-      }
-#pragma unroll
-      for (int e = 0; e < E; ++e) z[e] += rv[st][e];
-    }
-    if (inb) row_store<C>(a.a + row * C, l, z);            // z, kept for the backward (zeros on padded rows)
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) s += z[e];
-    const float mu = row_sum<C>(s) * (1.0f / C);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const float d = z[e] - mu; q += d * d; }
-    const float rs = 1.0f / sqrtf(row_sum<C>(q) * (1.0f / C) + LN_EPS);
-    if (inb && l == 0) { a.mean[row] = vld ? mu : 0.f; a.rstd[row] = vld ? rs : 0.f; }
-    float y[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int c = row_col<C>(l, e);
-      float t = (z[e] - mu) * rs * wv[e] + bv[e];
-      if (a.film) t = a.film[(size_t)b * a.ld_film + c] * t + a.film[(size_t)b * a.ld_film + C + c];
-      y[e] = vld ? t : 0.f;
-    }
-    if (inb) {
-      row_store<C>(a.y + row * C, l, y);
-      if (a.y_h) row_store<C>(a.y_h + row * C, l, y);
-    }
-  }
+  // ---- phase 2: the row pass on the tile
+  ln_tile_pass<C, 4>((lds_floats)tile, wave * 16, l, sub, ah, a.seed_pre, a.thresh_pre, a.inv_keep_pre, a.film, a.ld_film, a.a, a.mean, a.rstd, a.y, a.y_h);
 }
 
 struct LnBwdArgs {
