@@ -366,6 +366,25 @@ int dx_voc_pair(const float* X, long sxb, const void* W1, const float* b1, const
  * X channels-last [B][N][32] (batch stride sxb), W the folded (1, 32, 7) fp32 weight. */
 int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
                 int B, int N, int ncols, void* stream);
+/* The windowed forms: the streaming generator (vocoder.stream_plan).  A launch reads the chunk index c from the device int32 `cursor`
+ * and computes rows [c == 0 ? 0 : c step + lag, (c + 1) step + lag) of its tile-row axis (the rows of X for the conv and the transposed
+ * conv, whose output rows are those times up; the samples for the pair and conv_post), clipped by the row's valid length; its grid
+ * covers step + lag rows.  N is the LOGICAL row count (frames axis length times scale).  Tensors are rings: logical row n lives at slot
+ * n & mask, mask = ring size - 1 (a power of two minus 1), or 0 for plain indexing (the mel read by conv_pre, a whole-length tensor).
+ * Nothing outside the window is stored, no zeros either: those slots hold older rows.  Zero padding at the two ends of an utterance is
+ * unchanged (logical rows outside [0, length) read as 0).  Each element is bit for bit what the unwindowed entry point writes at the
+ * same logical row, given the same rows in its receptive field.  R has its own batch stride srb; the pair's Y its own syb.
+ * dx_voc_post_win writes sample s to column s - c step of Y (B, ncols >= step + lag), 0 at and past the row's end (my must be 0). */
+int dx_voc_conv_win(const float* X, long sxb, long sxn, long sxc, const void* Wp, const float* bias, float* Y, long syb, const float* R,
+                    long srb, const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in,
+                    int acc_mode, int bf16, const int* cursor, int step, int lag, int mx, int my, int mr, void* stream);
+int dx_voc_pair_win(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y, long syb,
+                    const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, const int* cursor,
+                    int step, int lag, int mx, int my, void* stream);
+int dx_voc_post_win(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                    int B, int N, int ncols, const int* cursor, int step, int lag, int mx, int my, void* stream);
+/* *cursor += 1 by one thread: the last launch of a chunk, so that replaying the same launches computes the next window. */
+int dx_voc_stream_advance(int* cursor, void* stream);
 
 /* ---- mel front end (reference extract_features.py mel_spectrogram_HiFi, vocoder/dataset.py mel_spectrogram, center = False;
  * csrc/dx_mel.hip) ------------------------------------------------------------------------------------------------------------

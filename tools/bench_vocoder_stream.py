@@ -1,0 +1,96 @@
+"""Streaming HiFi-GAN vocoder against the whole call, on tools/bench_vocoder.py's batch (B = 16 utterances of 425 .. 850 frames,
+synthetic weights) and on its longest row alone (B = 1), for chunks of 8, 32 and 128 mel frames in both operand modes.  One JSON line;
+per case:
+
+    first_chunk_ms       from the call of ``stream`` (rings allocated and zeroed there) to a synchronise after chunk 0; median of 3
+    chunk_replayed_ms    mean over the chunks a captured graph replays (chunk 2 onwards), one synchronise at the end
+    capture_chunk_ms     chunk 1: the capture and its first replay
+    chunk_eager_ms       mean over chunks 1 onwards of a stream with use_graph=False
+    streamed_total_s     the whole stream, construction included, use_graph=True; ``audio_s_per_chunk`` is what one chunk plays for
+    infer_batch_s        ``infer_batch`` on the same mel (mean of 3 after 1 warm-up)
+    workspace            bytes of the stream (independent of the length) and of infer_batch (160 KB per frame of the longest row)
+
+All times are host clocks around work that ends in a device synchronise; every shape is warmed by one untimed stream first.
+
+    python tools/bench_vocoder_stream.py [--quick]      # --quick: B = 1 and F = 32 only
+"""
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import torch  # noqa: E402
+
+from tests import vocoder_helpers as vh  # noqa: E402
+from tools.bench_vocoder import B, T_MAX, timed  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd import vocoder as voc  # noqa: E402
+
+
+def clock():
+    torch.cuda.synchronize()
+    return time.perf_counter()
+
+
+def first_chunk(v, mels, lens, F):
+    t0 = clock()
+    s = v.stream(mels, lens, chunk_frames=F, clone=False)
+    next(s)
+    return clock() - t0
+
+
+def whole_stream(v, mels, lens, F, use_graph):
+    """-> (total s, chunk 1 s, mean s of the chunks after it)"""
+    t0 = clock()
+    s = v.stream(mels, lens, chunk_frames=F, use_graph=use_graph, clone=False)
+    next(s)
+    t1 = clock()
+    second = None
+    if len(s) > 1:
+        next(s)
+        second = clock() - t1
+    t2 = clock()
+    rest = 0
+    for _ in s:
+        rest += 1
+    t3 = clock()
+    return t3 - t0, second, ((t3 - t2) / rest if rest else None), s
+
+
+def main():
+    quick = '--quick' in sys.argv
+    dev = 'cuda'
+    g = torch.Generator().manual_seed(3)
+    lengths = torch.randint(T_MAX // 2, T_MAX + 1, (B,), generator=g)
+    lengths[0] = T_MAX
+    mels = ((torch.randn(B, 80, T_MAX, generator=g) * 1.5 - 5.0).clamp(-11.5, 2.0)).to(dev)
+    for b, n in enumerate(lengths.tolist()):
+        mels[b, :, n:] = 0
+    sd = vh.state_dict()
+    ms = lambda t: None if t is None else round(t * 1e3, 3)
+    out = {'workload': f'B = {B}: {int(lengths.sum())} mel frames (max {T_MAX}); B = 1: its first row, {T_MAX} frames'}
+    with torch.no_grad():
+        for prec in ('f32', 'bf16'):
+            v = voc.HiFiGanVocoder(sd, device=dev, precision=prec)
+            for nb in ((1,) if quick else (1, B)):
+                m, lens = mels[:nb].contiguous(), lengths[:nb].tolist()
+                whole = timed(lambda: v.infer_batch(m, lens), n=3, warm=1)
+                for F in ((32,) if quick else (8, 32, 128)):
+                    whole_stream(v, m, lens, F, True)                       # warm-up of every shape of this case
+                    first = statistics.median(first_chunk(v, m, lens, F) for _ in range(3))
+                    total, capture, replayed, s = whole_stream(v, m, lens, F, True)
+                    _, eager1, eager, _ = whole_stream(v, m, lens, F, False)
+                    n = len(s)
+                    eager_mean = None if eager1 is None else (eager1 + (eager or 0.0) * (n - 2)) / (n - 1)
+                    out[f'{prec}_B{nb}_F{F}'] = {
+                        'chunks': n, 'audio_s_per_chunk': round(F * 256 / 22050, 4), 'first_chunk_ms': ms(first),
+                        'chunk_replayed_ms': ms(replayed), 'capture_chunk_ms': ms(capture), 'chunk_eager_ms': ms(eager_mean),
+                        'streamed_total_s': round(total, 5), 'infer_batch_s': round(whole, 5), 'streamed_over_whole': round(total / whole, 3),
+                        'workspace': {'stream': s.workspace_bytes, 'infer_batch': nb * max(lens) * voc.WORKSPACE_BYTES_PER_FRAME}}
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

@@ -9,7 +9,7 @@ from .model import DaftExprt  # noqa: F401
 from .loss import DaftExprtLoss  # noqa: F401
 from .functional import manual_seed  # noqa: F401
 from .ops import set_precision, get_precision, Runtime  # noqa: F401
-from .vocoder import HiFiGANGenerator, HiFiGanVocoder, load_hifigan_vocoder  # noqa: F401
+from .vocoder import HiFiGANGenerator, HiFiGanVocoder, VocoderStream, load_hifigan_vocoder, stream_plan  # noqa: F401
 from .mel import MelSpectrogram, mel_filter_bank, mel_spectrogram, mel_spectrogram_HiFi  # noqa: F401
 from .speech import SpeechSynthesizer, condition_external_prosody, symbol_prosody, to_pcm16  # noqa: F401
 from .discriminators import (DiscriminatorP, DiscriminatorS, HiFiGanDiscriminators, MultiPeriodDiscriminator,  # noqa: F401

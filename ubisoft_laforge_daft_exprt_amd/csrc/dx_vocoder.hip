@@ -15,6 +15,13 @@
 // input samples s + base_r, s + base_r + 1 (base_r = -1 if r + u/2 < u else 0) with the phase's own 2 x Cin x Cout slice of W;
 // grid.z = phase.  ResBlock1 pairs (conv dil d -> conv dil 1) of the 64- and 32-channel stages run fused (dx_voc_pair): the
 // intermediate stays in LDS with its halo.
+//
+// Windowed form (template <bool WIN>, the dx_voc_*_win entry points): the streaming generator.  A launch reads the chunk index c from
+// device memory and computes rows [lo, hi) = [c == 0 ? 0 : c step + lag, (c + 1) step + lag), clipped by the row's length, of its
+// output; tiles start at lo.  Tensors live in rings: row n at slot n & mask (mask -1: plain indexing).  Every store and every
+// read-modify-write is masked to [lo, hi), because a slot outside the window holds an older row that a later launch still reads; for
+// the same reason nothing is zero-filled.  The zero padding at an utterance's two ends stays the 0 <= n < len test on LOGICAL rows.
+// An output element is summed in an order that does not depend on where its tile starts, so a window writes the bits the whole call does.
 #include "dx_common.h"
 
 namespace {
@@ -27,11 +34,30 @@ constexpr int THREADS = 256;
 
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * VOC_SLOPE; }
 
+struct WinArgs {
+  const int* cursor;      // device int32: the chunk index
+  int step, lag;          // in tile rows
+  int mx, my, mr;         // ring masks of X, Y, R (-1: plain indexing)
+};
+
+// rows [lo, hi) of the tile-row axis this launch computes, hi clipped by the valid length
+template <bool WIN>
+__device__ __forceinline__ void voc_window(const WinArgs& w, int len, int& lo, int& hi) {
+  lo = 0;
+  hi = len;
+  if (WIN) {
+    const int c = *w.cursor;
+    lo = c == 0 ? 0 : c * w.step + w.lag;
+    hi = min((c + 1) * w.step + w.lag, len);
+  }
+}
+
 // A[rr][cc] = lrelu?(X[b][row0 + rr][c0 + cc]) for rr < R, cc < kcw; 0 outside [0, len) x [0, Cin).  Channels-last rows (sxc == 1,
 // sxn >= Cin) are read as float4; any other layout (the (B, 80, T) mel, whose channel stride is 1 too when T == 1) element-wise.
-template <bool BF>
+// WIN: row n is read from ring slot n & mask.
+template <bool BF, bool WIN>
 __device__ __forceinline__ void voc_stage(typename DxMmaOp<BF>::T* A, int lda, int R, const float* X, long sxn, long sxc,
-                                          int row0, int len, int c0, int kcw, int Cin, int pro) {
+                                          int row0, int len, int c0, int kcw, int Cin, int pro, int mask) {
   typedef DxMmaOp<BF> Op;
   if (sxc == 1 && sxn >= Cin) {
     const int q = kcw >> 2;
@@ -39,7 +65,7 @@ __device__ __forceinline__ void voc_stage(typename DxMmaOp<BF>::T* A, int lda, i
       const int rr = e / q, cc = (e - rr * q) * 4, n = row0 + rr, c = c0 + cc;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (n >= 0 && n < len && c < Cin) {
-        v = *reinterpret_cast<const float4*>(X + (long)n * sxn + c);
+        v = *reinterpret_cast<const float4*>(X + (long)(WIN ? n & mask : n) * sxn + c);
         if (pro) { v.x = lrelu(v.x); v.y = lrelu(v.y); v.z = lrelu(v.z); v.w = lrelu(v.w); }
       }
       typename Op::T* d = A + rr * lda + cc;
@@ -50,7 +76,7 @@ __device__ __forceinline__ void voc_stage(typename DxMmaOp<BF>::T* A, int lda, i
       const int cc = e / R, rr = e - cc * R, n = row0 + rr, c = c0 + cc;
       float v = 0.f;
       if (n >= 0 && n < len && c < Cin) {
-        v = X[(long)n * sxn + (long)c * sxc];
+        v = X[(long)(WIN ? n & mask : n) * sxn + (long)c * sxc];
         if (pro) v = lrelu(v);
       }
       A[rr * lda + cc] = Op::cvt(v);
@@ -92,26 +118,31 @@ __device__ __forceinline__ float voc_finish(float v, const float* y, int acc_mod
 struct ConvArgs {
   const float* X; long sxb, sxn, sxc;
   const uint4* Wp; const float* bias;
-  float* Y; long syb; const float* R;
+  float* Y; long syb; const float* R; long srb;
   const int* frames; int in_scale;
   int N, Cin, Cout, taps, dil, pad, up, KST, pro, acc_mode;
 };
 
 // One conv (up == 1) or one phase of a transposed conv (up > 1, grid.z = phase) on a 64-sample tile of one batch row.
-template <bool BF, int NI, int MI>
-__global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p) {
+template <bool BF, int NI, int MI, bool WIN>
+__global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p, WinArgs win) {
   typedef DxMmaOp<BF> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
   T* A = reinterpret_cast<T*>(voc_smem);
-  const int b = blockIdx.y, ph = blockIdx.z, m0 = blockIdx.x * VT;
+  const int b = blockIdx.y, ph = blockIdx.z;
   const int in_len = min(p.frames[b] * p.in_scale, p.N);
   const int out_len = in_len * p.up;
+  int lo, hi;
+  voc_window<WIN>(win, in_len, lo, hi);
+  const int m0 = lo + blockIdx.x * VT;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
   float* Y = p.Y + b * p.syb;
   const int NB = p.Cout / 16;
   const int WN = NB < 4 ? NB : 4, WM = 4 / WN, wn = w % WN, wm = w / WN;
-  if (m0 * p.up + ph >= out_len) {                   // no valid output row in this tile: zeros only
+  if (WIN) {
+    if (m0 >= hi) return;                            // a tile wholly outside the window stores nothing
+  } else if (m0 * p.up + ph >= out_len) {            // no valid output row in this tile: zeros only
     for (int e = threadIdx.x; e < VT * p.Cout; e += THREADS) {
       const int m = m0 + e / p.Cout, n = e % p.Cout;
       if (m < p.N) Y[(long)(m * p.up + ph) * p.Cout + n] = 0.f;
@@ -135,11 +166,11 @@ __global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p) {
   for (int c0 = 0; c0 < KP; c0 += KC) {
     const int kcw = min(KC, KP - c0);
     __syncthreads();
-    voc_stage<BF>(A, lda, rows, X, p.sxn, p.sxc, m0 - pad, in_len, c0, kcw, p.Cin, p.pro);
+    voc_stage<BF, WIN>(A, lda, rows, X, p.sxn, p.sxc, m0 - pad, in_len, c0, kcw, p.Cin, p.pro, win.mx);
     __syncthreads();
     voc_mma<BF, NI, MI>(A, lda, 4, p.taps, p.dil, Wp, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc);
   }
-  const float* R = p.R ? p.R + b * p.syb : nullptr;
+  const float* R = p.R ? p.R + b * p.srb : nullptr;
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int n = (wn + i * WN) * 16 + r;
@@ -149,6 +180,15 @@ __global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int m = m0 + (wm + j * WM) * 16 + 4 * g + e;
+        if (WIN) {                                   // only rows of the window, at their ring slots
+          if (m >= hi) continue;
+          const int row = m * p.up + ph;
+          const long o = (long)(row & win.my) * p.Cout + n;
+          float v = acc[i][j][e] + bn;
+          if (R) v += R[(long)(row & win.mr) * p.Cout + n];
+          Y[o] = voc_finish(v, Y + o, p.acc_mode);
+          continue;
+        }
         if (m >= p.N) continue;
         const long o = (long)(m * p.up + ph) * p.Cout + n;
         float v = 0.f;
@@ -166,22 +206,27 @@ __global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p) {
 struct PairArgs {
   const float* X; long sxb;
   const uint4* W1; const float* b1; const uint4* W2; const float* b2;
-  float* Y;
+  float* Y; long syb;
   const int* frames; int scale;
   int N, C, taps, dil, KST, acc_mode;
 };
 
 // Y = acc_mode( conv2(lrelu(conv1(lrelu(X)) + b1)) + b2 + X ): one ResBlock1 pair, intermediate (80 rows with halo) in LDS.
-template <bool BF, int MI1, int MI2>
-__global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p) {
+template <bool BF, int MI1, int MI2, bool WIN>
+__global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs win) {
   typedef DxMmaOp<BF> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
-  const int b = blockIdx.y, s0 = blockIdx.x * VT, C = p.C;
+  const int b = blockIdx.y, C = p.C;
   const int len = min(p.frames[b] * p.scale, p.N);
+  int lo, hi;
+  voc_window<WIN>(win, len, lo, hi);
+  const int s0 = lo + blockIdx.x * VT;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-  float* Y = p.Y + b * p.sxb;
-  if (s0 >= len) {
+  float* Y = p.Y + b * p.syb;
+  if (WIN) {
+    if (s0 >= hi) return;
+  } else if (s0 >= len) {
     for (int e = threadIdx.x; e < VT * C; e += THREADS) {
       const int m = s0 + e / C;
       if (m < p.N) Y[(long)m * C + e % C] = 0.f;
@@ -200,7 +245,7 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p) {
   for (int c0 = 0; c0 < C; c0 += KC) {
     const int kcw = min(KC, C - c0);
     __syncthreads();
-    voc_stage<BF>(A, lda, rows, X, C, 1, s0 - h2 - h1, len, c0, kcw, C, 1);
+    voc_stage<BF, WIN>(A, lda, rows, X, C, 1, s0 - h2 - h1, len, c0, kcw, C, 1, win.mx);
     __syncthreads();
     voc_mma<BF, 1, MI1>(A, lda, MIDR / 16, p.taps, p.dil, p.W1, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc1);
   }
@@ -231,6 +276,12 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int m = s0 + (wm + j * WM) * 16 + 4 * g + e;
+      if (WIN) {
+        if (m >= hi) continue;
+        const long o = (long)(m & win.my) * C + n;
+        Y[o] = voc_finish(acc2[0][j][e] + bn + X[(long)(m & win.mx) * C + n], Y + o, p.acc_mode);
+        continue;
+      }
       if (m >= p.N) continue;
       const long o = (long)m * C + n;
       float v = 0.f;
@@ -241,15 +292,24 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p) {
 }
 
 // conv_post (32 -> 1, k = 7, padding 3) on lrelu(X), then tanh and the clip to [-1, 1]; one output sample per thread.
-// Y row b holds ncols samples: those at or past the row's valid length are written as 0.
+// Y row b holds ncols samples: those at or past the row's valid length are written as 0.  WIN: sample s of the window goes to column
+// s - c step of the chunk buffer.
+template <bool WIN>
 __global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy,
-                                                           const int* frames, int scale, int N, int ncols) {
+                                                           const int* frames, int scale, int N, int ncols, WinArgs win) {
   __shared__ float ws[32 * 7];
   for (int e = threadIdx.x; e < 32 * 7; e += THREADS) ws[e] = W[e];
   __syncthreads();
-  const int b = blockIdx.y, s = blockIdx.x * THREADS + threadIdx.x;
-  if (s >= ncols) return;
+  const int b = blockIdx.y;
   const int len = min(frames[b] * scale, N);
+  int s = blockIdx.x * THREADS + threadIdx.x, col = s;
+  if (WIN) {
+    const int c = *win.cursor;
+    s += c == 0 ? 0 : c * win.step + win.lag;
+    col = s - c * win.step;
+    if (s >= (c + 1) * win.step + win.lag) return;
+  }
+  if (col >= ncols) return;
   float v = 0.f;
   if (s < len) {
     const float* x = X + b * sxb;
@@ -257,7 +317,7 @@ __global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long 
     for (int t = 0; t < 7; ++t) {
       const int n = s - 3 + t;
       if (n < 0 || n >= len) continue;
-      const float4* xr = reinterpret_cast<const float4*>(x + (long)n * 32);
+      const float4* xr = reinterpret_cast<const float4*>(x + (long)(WIN ? n & win.mx : n) * 32);
 #pragma unroll
       for (int c4 = 0; c4 < 8; ++c4) {
         const float4 q = xr[c4];
@@ -269,8 +329,11 @@ __global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long 
     }
     v = fminf(fmaxf(tanhf(acc + bias[0]), -1.f), 1.f);
   }
-  Y[(long)b * ldy + s] = v;
+  Y[(long)b * ldy + col] = v;
 }
+
+// The chunk's last launch: the next replay of the same launches computes the next window.
+__global__ void voc_advance_kernel(int* cursor) { *cursor += 1; }
 
 // Pack: [phase][t][nb][ks][lane][VEC]; lane (n = l & 15, g = l >> 4) element v holds k = ks*KS + g*VEC + v of column nb*16 + n.
 // up == 1: W (Cout, Cin, taps); up > 1: W (Cin, Cout, 2 up) of a ConvTranspose1d, tap t of phase r = kernel index j0(r) - t*up.
@@ -304,37 +367,98 @@ long voc_pack_elems(int Cout, int Cin, int taps, int up, int bf16) {
   return (long)(up > 1 ? up : 1) * taps * (Cout / 16) * dx_cdiv(Cin, KS) * 64 * (bf16 ? 8 : 4);
 }
 
+// win == nullptr: the whole tensor (tiles over N rows); else the window kernels, with a grid for chunk 0's window of step + lag rows.
 template <bool BF, int NI, int MI>
-int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
+int launch_conv(const ConvArgs& a, const WinArgs* win, int B, hipStream_t s) {
   typedef DxMmaOp<BF> Op;
   const size_t smem = (size_t)(VT + (a.taps - 1) * a.dil) * (KC + Op::PAD) * sizeof(typename Op::T);
-  hipLaunchKernelGGL((voc_conv_kernel<BF, NI, MI>), dim3(dx_cdiv(a.N, VT), B, a.up), dim3(THREADS), smem, s, a);
+  if (win)
+    hipLaunchKernelGGL((voc_conv_kernel<BF, NI, MI, true>), dim3(dx_cdiv(win->step + win->lag, VT), B, a.up), dim3(THREADS), smem, s, a, *win);
+  else
+    hipLaunchKernelGGL((voc_conv_kernel<BF, NI, MI, false>), dim3(dx_cdiv(a.N, VT), B, a.up), dim3(THREADS), smem, s, a, WinArgs{});
   DX_LAUNCH_CHECK("dx_voc_conv");
   return DX_OK;
 }
 
 template <bool BF>
-int dispatch_conv(const ConvArgs& a, int B, hipStream_t s) {
+int dispatch_conv(const ConvArgs& a, const WinArgs* win, int B, hipStream_t s) {
   switch (a.Cout / 16) {
-    case 32: return launch_conv<BF, 8, 4>(a, B, s);
-    case 16: return launch_conv<BF, 4, 4>(a, B, s);
-    case 8: return launch_conv<BF, 2, 4>(a, B, s);
-    case 4: return launch_conv<BF, 1, 4>(a, B, s);
-    default: return launch_conv<BF, 1, 2>(a, B, s);
+    case 32: return launch_conv<BF, 8, 4>(a, win, B, s);
+    case 16: return launch_conv<BF, 4, 4>(a, win, B, s);
+    case 8: return launch_conv<BF, 2, 4>(a, win, B, s);
+    case 4: return launch_conv<BF, 1, 4>(a, win, B, s);
+    default: return launch_conv<BF, 1, 2>(a, win, B, s);
   }
 }
 
 template <bool BF, int MI1, int MI2>
-int launch_pair(const PairArgs& a, int B, hipStream_t s) {
+int launch_pair(const PairArgs& a, const WinArgs* win, int B, hipStream_t s) {
   typedef DxMmaOp<BF> Op;
   const int h1 = a.dil * (a.taps - 1) / 2;
   const size_t smem = ((size_t)(MIDR + 2 * h1) * (KC + Op::PAD) + (size_t)MIDR * (a.C + Op::PAD)) * sizeof(typename Op::T);
-  hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a);
+  if (win)
+    hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2, true>), dim3(dx_cdiv(win->step + win->lag, VT), B), dim3(THREADS), smem, s, a, *win);
+  else
+    hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2, false>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a, WinArgs{});
   DX_LAUNCH_CHECK("dx_voc_pair");
   return DX_OK;
 }
 
+// A ring mask is 0 (plain indexing, passed to the kernels as -1) or 2^k - 1; the window is [c step + lag, (c + 1) step + lag).
+bool voc_mask_ok(int m) { return m >= 0 && (m & (m + 1)) == 0; }
+bool voc_win_ok(const void* cursor, int step, int lag, int mx, int my, int mr) {
+  return cursor && step > 0 && lag >= 0 && voc_mask_ok(mx) && voc_mask_ok(my) && voc_mask_ok(mr);
+}
+WinArgs voc_win(const int* cursor, int step, int lag, int mx, int my, int mr) {
+  WinArgs w;
+  w.cursor = cursor; w.step = step; w.lag = lag;
+  w.mx = mx ? mx : -1; w.my = my ? my : -1; w.mr = mr ? mr : -1;
+  return w;
+}
+
 bool voc_taps_ok(int taps, int dil) { return (taps == 3 || taps == 7 || taps == 11) && (dil == 1 || dil == 3 || dil == 5); }
+
+// dx_voc_conv (win == nullptr; srb = syb) and dx_voc_conv_win
+int voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const float* bias, float* Y, long syb, const float* R, long srb,
+             const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in, int acc_mode,
+             int bf16, const WinArgs* win, void* stream) {
+  DX_REQUIRE(X && Wp && Y && frames, "dx_voc_conv: null pointer");
+  DX_REQUIRE(B > 0 && N > 0 && in_scale > 0 && Cin > 0 && (Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512),
+             "dx_voc_conv: bad shape (Cout in {32, 64, 128, 256, 512})");
+  DX_REQUIRE(up == 1 ? (taps % 2 == 1 && taps <= 11 && dil >= 1 && dil <= 5) : (taps == 2 && dil == 1 && up % 2 == 0 && up <= 8),
+             "dx_voc_conv: bad taps / dilation / upsampling (odd taps <= 11 with dilation <= 5, or a polyphase transposed conv: taps 2, even up <= 8)");
+  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_conv: bad acc_mode / bf16");
+  DX_REQUIRE((const void*)X != (const void*)Y, "dx_voc_conv: Y must not alias X (tiles read their neighbours' rows); R may alias Y");
+  DX_REQUIRE(sxc != 1 || sxn < Cin || (Cin % 4 == 0 && sxn % 4 == 0 && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0),
+             "dx_voc_conv: channels-last input needs Cin and strides %% 4 == 0 and a 16-byte aligned X");
+  ConvArgs a;
+  a.X = X; a.sxb = sxb; a.sxn = sxn; a.sxc = sxc;
+  a.Wp = reinterpret_cast<const uint4*>(Wp); a.bias = bias;
+  a.Y = Y; a.syb = syb; a.R = R; a.srb = srb;
+  a.frames = frames; a.in_scale = in_scale;
+  a.N = N; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.dil = dil; a.pad = dil * (taps - 1) / 2; a.up = up;
+  a.KST = dx_cdiv(Cin, bf16 ? 32 : 16); a.pro = lrelu_in; a.acc_mode = acc_mode;
+  return bf16 ? dispatch_conv<true>(a, win, B, (hipStream_t)stream) : dispatch_conv<false>(a, win, B, (hipStream_t)stream);
+}
+
+// dx_voc_pair (win == nullptr; syb = sxb) and dx_voc_pair_win
+int voc_pair(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y, long syb,
+             const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, const WinArgs* win, void* stream) {
+  DX_REQUIRE(X && W1 && b1 && W2 && b2 && Y && frames, "dx_voc_pair: null pointer");
+  DX_REQUIRE(X != Y, "dx_voc_pair: Y must not alias X (tiles read their neighbours' rows)");
+  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && (C == 32 || C == 64) && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
+             "dx_voc_pair: bad shape (C in {32, 64}; sxb %% 4 == 0 and a 16-byte aligned X)");
+  DX_REQUIRE(voc_taps_ok(taps, dil), "dx_voc_pair: bad taps / dilation (taps 3, 7 or 11; dilation 1, 3 or 5)");
+  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_pair: bad acc_mode / bf16");
+  PairArgs a;
+  a.X = X; a.sxb = sxb;
+  a.W1 = reinterpret_cast<const uint4*>(W1); a.b1 = b1; a.W2 = reinterpret_cast<const uint4*>(W2); a.b2 = b2;
+  a.Y = Y; a.syb = syb; a.frames = frames; a.scale = scale;
+  a.N = N; a.C = C; a.taps = taps; a.dil = dil; a.KST = C / (bf16 ? 32 : 16); a.acc_mode = acc_mode;
+  hipStream_t s = (hipStream_t)stream;
+  if (C == 64) return bf16 ? launch_pair<true, 5, 4>(a, win, B, s) : launch_pair<false, 5, 4>(a, win, B, s);
+  return bf16 ? launch_pair<true, 3, 2>(a, win, B, s) : launch_pair<false, 3, 2>(a, win, B, s);
+}
 
 }  // namespace
 
@@ -366,41 +490,36 @@ int dx_voc_pack(const float* W, void* Wp, int Cout, int Cin, int taps, int up, i
 int dx_voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const float* bias, float* Y, long syb, const float* R,
                 const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in, int acc_mode,
                 int bf16, void* stream) {
-  DX_REQUIRE(X && Wp && Y && frames, "dx_voc_conv: null pointer");
-  DX_REQUIRE(B > 0 && N > 0 && in_scale > 0 && Cin > 0 && (Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512),
-             "dx_voc_conv: bad shape (Cout in {32, 64, 128, 256, 512})");
-  DX_REQUIRE(up == 1 ? (taps % 2 == 1 && taps <= 11 && dil >= 1 && dil <= 5) : (taps == 2 && dil == 1 && up % 2 == 0 && up <= 8),
-             "dx_voc_conv: bad taps / dilation / upsampling (odd taps <= 11 with dilation <= 5, or a polyphase transposed conv: taps 2, even up <= 8)");
-  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_conv: bad acc_mode / bf16");
-  DX_REQUIRE((const void*)X != (const void*)Y, "dx_voc_conv: Y must not alias X (tiles read their neighbours' rows); R may alias Y");
-  DX_REQUIRE(sxc != 1 || sxn < Cin || (Cin % 4 == 0 && sxn % 4 == 0 && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0),
-             "dx_voc_conv: channels-last input needs Cin and strides %% 4 == 0 and a 16-byte aligned X");
-  ConvArgs a;
-  a.X = X; a.sxb = sxb; a.sxn = sxn; a.sxc = sxc;
-  a.Wp = reinterpret_cast<const uint4*>(Wp); a.bias = bias;
-  a.Y = Y; a.syb = syb; a.R = R;
-  a.frames = frames; a.in_scale = in_scale;
-  a.N = N; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.dil = dil; a.pad = dil * (taps - 1) / 2; a.up = up;
-  a.KST = dx_cdiv(Cin, bf16 ? 32 : 16); a.pro = lrelu_in; a.acc_mode = acc_mode;
-  return bf16 ? dispatch_conv<true>(a, B, (hipStream_t)stream) : dispatch_conv<false>(a, B, (hipStream_t)stream);
+  return voc_conv(X, sxb, sxn, sxc, Wp, bias, Y, syb, R, syb, frames, in_scale, B, N, Cin, Cout, taps, dil, up, lrelu_in, acc_mode, bf16,
+                  nullptr, stream);
+}
+
+int dx_voc_conv_win(const float* X, long sxb, long sxn, long sxc, const void* Wp, const float* bias, float* Y, long syb, const float* R,
+                    long srb, const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in,
+                    int acc_mode, int bf16, const int* cursor, int step, int lag, int mx, int my, int mr, void* stream) {
+  DX_REQUIRE(voc_win_ok(cursor, step, lag, mx, my, mr), "dx_voc_conv_win: bad window (cursor, step > 0, lag >= 0, masks 0 or 2^k - 1)");
+  DX_REQUIRE(my == 0 || (long)(my + 1) * Cout <= syb, "dx_voc_conv_win: Y's ring does not fit its batch stride");
+  DX_REQUIRE(!R || (mr ? (long)(mr + 1) : (long)N * (up > 1 ? up : 1)) * Cout <= srb, "dx_voc_conv_win: R's ring (or its N rows) does not fit its batch stride");
+  DX_REQUIRE(mx == 0 || (long)mx * sxn + (long)(Cin - 1) * sxc < sxb, "dx_voc_conv_win: X's ring does not fit its batch stride");
+  DX_REQUIRE(my != 0 || (long)N * (up > 1 ? up : 1) * Cout <= syb, "dx_voc_conv_win: an unringed Y holds all N rows");
+  const WinArgs w = voc_win(cursor, step, lag, mx, my, mr);
+  return voc_conv(X, sxb, sxn, sxc, Wp, bias, Y, syb, R, srb, frames, in_scale, B, N, Cin, Cout, taps, dil, up, lrelu_in, acc_mode, bf16,
+                  &w, stream);
 }
 
 int dx_voc_pair(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y,
                 const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, void* stream) {
-  DX_REQUIRE(X && W1 && b1 && W2 && b2 && Y && frames, "dx_voc_pair: null pointer");
-  DX_REQUIRE(X != Y, "dx_voc_pair: Y must not alias X (tiles read their neighbours' rows)");
-  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && (C == 32 || C == 64) && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
-             "dx_voc_pair: bad shape (C in {32, 64}; sxb %% 4 == 0 and a 16-byte aligned X)");
-  DX_REQUIRE(voc_taps_ok(taps, dil), "dx_voc_pair: bad taps / dilation (taps 3, 7 or 11; dilation 1, 3 or 5)");
-  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_pair: bad acc_mode / bf16");
-  PairArgs a;
-  a.X = X; a.sxb = sxb;
-  a.W1 = reinterpret_cast<const uint4*>(W1); a.b1 = b1; a.W2 = reinterpret_cast<const uint4*>(W2); a.b2 = b2;
-  a.Y = Y; a.frames = frames; a.scale = scale;
-  a.N = N; a.C = C; a.taps = taps; a.dil = dil; a.KST = C / (bf16 ? 32 : 16); a.acc_mode = acc_mode;
-  hipStream_t s = (hipStream_t)stream;
-  if (C == 64) return bf16 ? launch_pair<true, 5, 4>(a, B, s) : launch_pair<false, 5, 4>(a, B, s);
-  return bf16 ? launch_pair<true, 3, 2>(a, B, s) : launch_pair<false, 3, 2>(a, B, s);
+  return voc_pair(X, sxb, W1, b1, W2, b2, Y, sxb, frames, scale, B, N, C, taps, dil, acc_mode, bf16, nullptr, stream);
+}
+
+int dx_voc_pair_win(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y, long syb,
+                    const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, const int* cursor,
+                    int step, int lag, int mx, int my, void* stream) {
+  DX_REQUIRE(voc_win_ok(cursor, step, lag, mx, my, 0), "dx_voc_pair_win: bad window (cursor, step > 0, lag >= 0, masks 0 or 2^k - 1)");
+  DX_REQUIRE((mx ? (long)(mx + 1) : (long)N) * C <= sxb && (my ? (long)(my + 1) : (long)N) * C <= syb,
+             "dx_voc_pair_win: a ring (or the N rows of an unringed tensor) does not fit its batch stride");
+  const WinArgs w = voc_win(cursor, step, lag, mx, my, 0);
+  return voc_pair(X, sxb, W1, b1, W2, b2, Y, syb, frames, scale, B, N, C, taps, dil, acc_mode, bf16, &w, stream);
 }
 
 int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
@@ -408,9 +527,30 @@ int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, flo
   DX_REQUIRE(X && W && bias && Y && frames, "dx_voc_post: null pointer");
   DX_REQUIRE(B > 0 && N > 0 && scale > 0 && ncols >= N && ldy >= ncols && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
              "dx_voc_post: bad shape (ncols >= N, ldy >= ncols, sxb %% 4 == 0, a 16-byte aligned X)");
-  hipLaunchKernelGGL(voc_post_kernel, dim3(dx_cdiv(ncols, THREADS), B), dim3(THREADS), 0, (hipStream_t)stream,
-                     X, sxb, W, bias, Y, ldy, frames, scale, N, ncols);
+  hipLaunchKernelGGL(voc_post_kernel<false>, dim3(dx_cdiv(ncols, THREADS), B), dim3(THREADS), 0, (hipStream_t)stream,
+                     X, sxb, W, bias, Y, ldy, frames, scale, N, ncols, WinArgs{});
   DX_LAUNCH_CHECK("dx_voc_post");
+  return DX_OK;
+}
+
+int dx_voc_post_win(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                    int B, int N, int ncols, const int* cursor, int step, int lag, int mx, int my, void* stream) {
+  DX_REQUIRE(X && W && bias && Y && frames, "dx_voc_post_win: null pointer");
+  DX_REQUIRE(voc_win_ok(cursor, step, lag, mx, my, 0) && my == 0, "dx_voc_post_win: bad window (cursor, step > 0, lag >= 0, mx 0 or 2^k - 1, my 0: the chunk buffer is not a ring)");
+  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && ncols >= step + lag && ldy >= ncols && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0 &&
+                 (mx ? (long)(mx + 1) : (long)N) * 32 <= sxb,
+             "dx_voc_post_win: bad shape (ncols >= step + lag, ldy >= ncols, sxb %% 4 == 0 and holding X's ring, a 16-byte aligned X)");
+  const WinArgs w = voc_win(cursor, step, lag, mx, 0, 0);
+  hipLaunchKernelGGL(voc_post_kernel<true>, dim3(dx_cdiv(step + lag, THREADS), B), dim3(THREADS), 0, (hipStream_t)stream,
+                     X, sxb, W, bias, Y, ldy, frames, scale, N, ncols, w);
+  DX_LAUNCH_CHECK("dx_voc_post_win");
+  return DX_OK;
+}
+
+int dx_voc_stream_advance(int* cursor, void* stream) {
+  DX_REQUIRE(cursor, "dx_voc_stream_advance: null pointer");
+  hipLaunchKernelGGL(voc_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, cursor);
+  DX_LAUNCH_CHECK("dx_voc_stream_advance");
   return DX_OK;
 }
 

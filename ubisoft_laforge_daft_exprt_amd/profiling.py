@@ -178,9 +178,13 @@ def price(name, a, geom: Geometry):
         return 'relu_bwd', 'hbm', None, 3 * a['n'] * 4
     if name == 'dx_colsum':
         return 'colsum', 'hbm', None, a['rows'] * a['C'] * (2 if a['x_bf16'] else 4)
+    if name in ('dx_voc_conv_win', 'dx_voc_pair_win', 'dx_voc_post_win'):       # the streaming forms: the rows of ONE interior window
+        return price(name[:-4], dict(a, window_rows=a['B'] * a['step']), geom)  # (B x step; chunk 0 computes lag more, the last chunks fewer)
+    if name == 'dx_voc_stream_advance':
+        return 'voc_stream_advance', 'hbm', None, 8
     if name in ('dx_voc_conv', 'dx_voc_pair', 'dx_voc_post'):   # HiFi-GAN vocoder: N rows of samples, frames * scale of them valid
         s = max(1, a['in_scale'] if name == 'dx_voc_conv' else a['scale'])
-        rows = geom.rows(a['B'], a['N'] // s) * s
+        rows = g('window_rows') or geom.rows(a['B'], a['N'] // s) * s
         op = 'bf16' if g('bf16') else 'f32'
         if name == 'dx_voc_conv':                        # conv (up = 1) or polyphase transposed conv: rows in, rows * up out
             out_rows = rows * a['up']

@@ -17,7 +17,7 @@ import torch
 from ._lib import lib
 from .durations import get_int_durations
 from .inference import GraphedSynthesizer
-from .vocoder import HOP
+from .vocoder import HOP, VocoderStream
 
 PITCH_MODES = {None: 0, 'add': 1, 'multiply': 2}
 PROSODY_KEYS = ('duration_preds', 'energy_preds', 'pitch_preds')      # model.inference's external_prosody (already normalised)
@@ -199,6 +199,33 @@ def to_pcm16(audio, sample_lengths):
     return out
 
 
+class _PcmChunks:
+    """``SpeechSynthesizer.stream``'s 'chunks': a ``VocoderStream`` whose steps also carry the chunk as 16-bit PCM."""
+
+    def __init__(self, vocoder, mel, lengths, chunk_frames, pcm16, use_graph):
+        self.pcm = None
+        tail = None
+        if pcm16 and use_graph:                                   # dx_pcm16 as the captured chunk's last launch but one, into a buffer of its own
+            B, S = mel.shape[0], int(chunk_frames) * HOP
+            self.pcm = torch.zeros(B, max(S, 1), dtype=torch.int16, device=mel.device)
+            full = torch.full((B,), S, dtype=torch.int32, device=mel.device)       # the chunk is already 0 past each row's end
+            tail = lambda audio: lib().dx_pcm16(audio.data_ptr(), full.data_ptr(), self.pcm.data_ptr(), B, S, _stream(audio.device))
+        self.pcm16 = pcm16
+        self.voc = VocoderStream(vocoder, mel, lengths, chunk_frames, use_graph, clone=True, tail=tail)
+
+    def __len__(self):
+        return len(self.voc)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        audio, valid = next(self.voc)
+        if not self.pcm16:
+            return None, audio, valid
+        return (self.pcm.clone() if self.pcm is not None else to_pcm16(audio, valid)), audio, valid
+
+
 # ---- the whole call ------------------------------------------------------------------------------------------------------------------
 class SpeechSynthesizer:
     """``generate_batch_mel_specs`` from the collated batch to PCM, device-resident: ``model`` a ``DaftExprt``, ``vocoder`` a
@@ -256,6 +283,19 @@ class SpeechSynthesizer:
             sample_lengths = out_lens * HOP
             pcm = to_pcm16(audio, sample_lengths) if pcm16 else None
         return dict(pcm=pcm, audio=audio, sample_lengths=sample_lengths, mel=mel, output_lengths=out_lens, encoder_preds=encoder_preds,
+                    weights=weights)
+
+    def stream(self, inputs, pitch_transform, external_prosody, external_embeddings, external_accent_emb, source_stats=None,
+               alpha_dur=1.0, alpha_pitch=1.0, alpha_energy=1.0, pcm16=True, use_graph=True, chunk_frames=32):
+        """``__call__`` with the audio delivered in chunks of ``chunk_frames`` mel frames: the same dict, with 'pcm' and 'audio' replaced by
+        'chunks', an iterator (with a length) of (pcm (B, 256 chunk_frames) int16 or None, audio fp32, valid (B,) samples of the chunk that
+        belong to each row).  The acoustic model runs whole, as in ``__call__`` (it is not autoregressive); the vocoder is
+        ``HiFiGanVocoder.stream``, so the chunks concatenated are bitwise ``__call__``'s 'audio' and 'pcm'.  With ``use_graph`` the PCM
+        conversion is one more launch of the captured chunk (samples past a row's end are already 0 there)."""
+        prep = self.prepare(inputs, pitch_transform, external_prosody, source_stats, alpha_dur, alpha_pitch, alpha_energy)
+        encoder_preds, (mel, out_lens), weights = self.synth.run(prep, external_embeddings, external_accent_emb, use_graph)
+        chunks = _PcmChunks(self.vocoder, mel, prep['out_host'], chunk_frames, pcm16, use_graph)
+        return dict(chunks=chunks, sample_lengths=out_lens * HOP, mel=mel, output_lengths=out_lens, encoder_preds=encoder_preds,
                     weights=weights)
 
     def from_reference_audio(self, wavs, wav_lengths, frames_pitch, durations_int, inputs, pitch_transform, external_embeddings,

@@ -3,7 +3,8 @@
 ``HiFiGANGenerator`` owns the reference generator's weight-normed state-dict layout (234 tensors); ``HiFiGanVocoder`` /
 ``load_hifigan_vocoder`` are drop-ins for the reference helpers (``.infer``: one utterance, numpy in or out) and add
 ``.infer_batch``: a padded (B, 80, T_max) mel batch on the device -- what ``DaftExprt.inference`` and ``GraphedSynthesizer`` return --
-to (B, 256 T_max) audio on the device, row b bitwise equal to ``mel[b, :, :lengths[b]]`` vocoded alone.
+to (B, 256 T_max) audio on the device, row b bitwise equal to ``mel[b, :, :lengths[b]]`` vocoded alone -- and ``.stream``: the same
+samples, bit for bit, in chunks of a few mel frames from ring buffers of fixed size (``stream_plan``, ``VocoderStream``).
 
 Weight norm is folded once, at load time (``torch._weight_norm`` over dim 0, what ``remove_weight_norm`` computes: per OUTPUT channel
 for the Conv1d layers, per INPUT channel for the ConvTranspose1d ones, whose weight is (Cin, Cout, k)).  Every convolution runs in
@@ -56,6 +57,95 @@ def check_config(config) -> dict:
     if got != want:
         raise NotImplementedError(f'the gfx950 HiFi-GAN kernels implement V1 only ({v1_config()}); got {dict(config)}')
     return dict(config)
+
+
+# ---- the streaming plan (host only) ----------------------------------------------------------------------------------------------
+class StreamPlan:
+    """What ``stream_plan`` returns.  ``tensors``: {name: {'scale' samples per mel frame, 'channels', 'lag', 'left', 'ring'}} for every
+    tensor between two layers; ``launches``: the chunk's launches in order, each a dict (kind 'conv' / 'pair' / 'post', layer names, the
+    names of its tensors 'x', 'y', 'r', the shape, 'scale' = tile rows per frame, 'step' = chunk_frames * scale, 'lag', and its 'left' /
+    'right' reach in rows of x); ``lookahead``: mel frames past a chunk's own that the chunk reads."""
+
+    def __init__(self, chunk_frames, tensors, launches, lookahead):
+        self.chunk_frames, self.tensors, self.launches, self.lookahead = chunk_frames, tensors, launches, lookahead
+
+    def ring_bytes(self, batch=1):
+        return sum(batch * t['ring'] * t['channels'] * 4 for t in self.tensors.values())
+
+
+def stream_plan(config=None, chunk_frames=32) -> StreamPlan:
+    """The schedule of the chunked generator.  After chunk c, rows [0, min(len, (c + 1) F scale + lag)) of a tensor exist; chunk c
+    computes rows [c F scale + lag (0 for c = 0), (c + 1) F scale + lag) of it, F = chunk_frames.
+
+    Lags come from walking the generator backwards from conv_post's output (lag 0): a tensor's lag is the largest, over the launches that
+    read it, of that launch's own lag (in the tensor's rows) plus its right reach -- dil (k - 1) / 2 for a dilated conv, that plus
+    (k - 1) / 2 for a fused pair, 3 for conv_post, 1 for a polyphase transposed conv (output row s up + r reads input rows s + base_r and
+    s + base_r + 1, base_r in {-1, 0}), whose output lag is rounded up to a multiple of up so that its window is whole input rows.  A
+    residual and an accumulated output are read at the launch's own rows.  Row n of a tensor lives at slot n & (ring - 1); the ring is
+    the power of two that holds the chunk-0 window (F scale + lag) and, for every reader, F scale + (lag - reader's lag) + the reader's
+    left reach: what is resident between the oldest row a reader of chunk c still needs and the newest row chunk c has written."""
+    cfg = check_config(config)
+    F = int(chunk_frames)
+    if F < 1:
+        raise ValueError(f'stream_plan: chunk_frames must be >= 1, got {chunk_frames}')
+    c = cfg['upsample_initial_channel']
+    T, L = {}, []
+
+    def tensor(name, scale, channels):
+        T[name] = dict(scale=scale, channels=channels, lag=0, left=0, ring=0)
+        return name
+
+    def conv(layer, x, y, cin, cout, taps, dil, up, lrelu, acc, scale, reach, r=None):
+        L.append(dict(kind='conv', layer=layer, x=x, y=y, r=r, cin=cin, cout=cout, taps=taps, dil=dil, up=up, lrelu=lrelu, acc=acc,
+                      scale=scale, left=reach, right=reach))
+
+    x, scale = tensor('conv_pre', 1, c), 1
+    conv('conv_pre', 'mel', x, cfg['model_in_dim'], c, 7, 1, 1, 0, 0, 1, 3)
+    ks, ds = cfg['resblock_kernel_sizes'], cfg['resblock_dilation_sizes']
+    for i, u in enumerate(cfg['upsample_rates']):
+        up_out = tensor(f'ups.{i}', scale * u, c // 2)
+        conv(f'ups.{i}', x, up_out, c, c // 2, 2, 1, u, 1, 0, scale, 1)
+        scale, c = scale * u, c // 2
+        total = tensor(f'sum.{i}', scale, c)
+        for j, k in enumerate(ks):
+            name, src, h = f'resblocks.{i * len(ks) + j}', up_out, (k - 1) // 2
+            for p, d in enumerate(ds[j]):
+                dst = total if p == 2 else tensor(f'{name}.x{p}', scale, c)
+                acc = min(j, 2) if p == 2 else 0
+                if c <= 64:
+                    L.append(dict(kind='pair', layer=f'{name}.convs1.{p}', layer2=f'{name}.convs2.{p}', x=src, y=dst, r=None, cin=c, cout=c,
+                                  taps=k, dil=d, up=1, lrelu=1, acc=acc, scale=scale, left=d * h + h, right=d * h + h))
+                else:
+                    mid = tensor(f'{name}.mid{p}', scale, c)
+                    conv(f'{name}.convs1.{p}', src, mid, c, c, k, d, 1, 1, 0, scale, d * h)
+                    conv(f'{name}.convs2.{p}', mid, dst, c, c, k, 1, 1, 1, acc, scale, h, r=src)
+                src = dst
+        x = total
+    L.append(dict(kind='post', layer='conv_post', x=x, y='audio', r=None, cin=c, cout=1, taps=7, dil=1, up=1, lrelu=1, acc=0, scale=scale,
+                  left=3, right=3))
+    lookahead = 0
+    for ln in reversed(L):                                  # every reader of a tensor comes after its writer: lags settle backwards
+        up = ln['up']
+        if ln['y'] != 'audio':
+            T[ln['y']]['lag'] = -(-T[ln['y']]['lag'] // up) * up
+        ln['lag'] = 0 if ln['y'] == 'audio' else T[ln['y']]['lag'] // up
+        ln['step'] = F * ln['scale']
+        if ln['x'] == 'mel':
+            lookahead = ln['lag'] + ln['right']
+        else:
+            tx = T[ln['x']]
+            tx['lag'], tx['left'] = max(tx['lag'], ln['lag'] + ln['right']), max(tx['left'], ln['left'])
+        if ln['r'] is not None:
+            T[ln['r']]['lag'] = max(T[ln['r']]['lag'], ln['lag'])
+    for name, t in T.items():
+        need = F * t['scale'] + t['lag']
+        for ln in L:
+            if ln['x'] == name:
+                need = max(need, F * t['scale'] + t['lag'] - ln['lag'] + ln['left'])
+            if ln['r'] == name or (ln['y'] == name and ln['acc']):
+                need = max(need, F * t['scale'] + t['lag'] - ln['lag'] * ln['up'])
+        t['ring'] = 1 << (need - 1).bit_length()
+    return StreamPlan(F, T, L, lookahead)
 
 
 class _WNConv(nn.Module):
@@ -198,19 +288,14 @@ class HiFiGanVocoder:
         return np.clip(audio, -1.0, 1.0)
 
     # -- batched form ----------------------------------------------------------------------------------------------------------
-    def infer_batch(self, mels, lengths, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
-        """mels (B, 80, T_max) fp32 on the device; lengths: B frame counts (host ints, or a device tensor such as GraphedSynthesizer's
-        out_lens: one small device-to-host copy sizes the work).  -> (audio (B, 256 T_max) fp32 on the device, sample_lengths).
-        Row b is bitwise ``mel[b, :, :lengths[b]]`` vocoded alone; samples at or past 256 lengths[b] are 0.  max_workspace_bytes
-        bounds the activation workspace: the batch then runs in chunks of consecutive utterances (bitwise the same result).  A chunk
-        of b utterances whose longest has n frames takes b * n * WORKSPACE_BYTES_PER_FRAME (160 KB per frame, sized by the LONGEST row:
-        2.2 GB for 16 rows of 850 frames); one utterance longer than the bound still runs, alone.  None: no bound, one chunk."""
+    def _check_batch(self, who, mels, lengths):
+        """-> (mels fp32 contiguous, host frame counts clamped to [0, T], the same on the device as int32, sample lengths)."""
         if mels.dim() != 3 or mels.shape[1] != self.config['model_in_dim']:
-            raise ValueError(f'infer_batch: mels must be (B, {self.config["model_in_dim"]}, T_max), got {tuple(mels.shape)}')
+            raise ValueError(f'{who}: mels must be (B, {self.config["model_in_dim"]}, T_max), got {tuple(mels.shape)}')
         if mels.device != self.device and not (self.device.index is None and mels.device.type == self.device.type):
-            raise ValueError(f'infer_batch: mels are on {mels.device}, the vocoder on {self.device}')
+            raise ValueError(f'{who}: mels are on {mels.device}, the vocoder on {self.device}')
         mels = mels.float().contiguous()
-        B, n_mel, T = mels.shape
+        B, _, T = mels.shape
         dev = mels.device
         if torch.is_tensor(lengths):
             host = lengths.tolist()                                       # the one device-to-host copy (sizing only)
@@ -221,8 +306,31 @@ class HiFiGanVocoder:
             frames = torch.tensor(host, dtype=torch.int32).clamp(0, T).to(dev)
             sample_lengths = [min(max(v, 0), T) * HOP for v in host]
         if len(host) != B:
-            raise ValueError(f'infer_batch: {len(host)} lengths for a batch of {B}')
-        host = [min(max(int(v), 0), T) for v in host]
+            raise ValueError(f'{who}: {len(host)} lengths for a batch of {B}')
+        return mels, [min(max(int(v), 0), T) for v in host], frames, sample_lengths
+
+    def stream(self, mels, lengths, chunk_frames=32, use_graph=True, clone=True):
+        """``infer_batch``'s mels and lengths -> a ``VocoderStream``: an iterator of ``len(stream)`` = max(1, ceil(max(lengths) /
+        chunk_frames)) steps, each yielding (audio (B, 256 chunk_frames) fp32 on the device, valid (B,) int64 on the device).  Step c
+        holds samples [256 c chunk_frames, 256 (c + 1) chunk_frames) of every row, bit for bit what ``infer_batch`` writes there;
+        ``valid`` counts those that belong to the row (0 once the row has ended; the rest of its chunk is 0).  Every step runs the same
+        61 launches (the generator's 60 and the cursor's advance) on ring buffers whose size depends on chunk_frames and B alone (``stream.workspace_bytes``); with ``use_graph``
+        they are captured once, while the second chunk is due, and replayed from then on.  ``clone=False`` yields the stream's own
+        buffer, overwritten by the next step.  The mel is read in place until the last step: leave it unchanged meanwhile."""
+        return VocoderStream(self, mels, lengths, chunk_frames, use_graph, clone)
+
+    def infer_batch(self, mels, lengths, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+        """mels (B, 80, T_max) fp32 on the device; lengths: B frame counts (host ints, or a device tensor such as GraphedSynthesizer's
+        out_lens: one small device-to-host copy sizes the work).  -> (audio (B, 256 T_max) fp32 on the device, sample_lengths).
+        Row b is bitwise ``mel[b, :, :lengths[b]]`` vocoded alone; samples at or past 256 lengths[b] are 0.  max_workspace_bytes
+        bounds the activation workspace: the batch then runs in chunks of consecutive utterances (bitwise the same result).  A chunk
+        of b utterances whose longest has n frames takes b * n * WORKSPACE_BYTES_PER_FRAME (160 KB per frame, sized by the LONGEST row:
+        2.2 GB for 16 rows of 850 frames); one utterance longer than the bound still runs, alone.  None: no bound, one chunk.
+        Nothing is returned before the last sample exists: ``stream`` yields the same samples chunk by chunk, in a workspace that does
+        not grow with the length."""
+        mels, host, frames, sample_lengths = self._check_batch('infer_batch', mels, lengths)
+        B, n_mel, T = mels.shape
+        dev = mels.device
         P = self._device_weights()
         audio = torch.empty(B, T * HOP, dtype=torch.float32, device=dev)
         b0 = 0
@@ -276,6 +384,91 @@ class HiFiGanVocoder:
         w, b = P['conv_post']
         L.dx_voc_post(S, rows * c, w.data_ptr(), b.data_ptr(), audio.data_ptr() + 4 * b0 * T * HOP, T * HOP,
                       fr, scale, B, rows, T * HOP, st)
+
+
+class VocoderStream:
+    """One utterance batch being vocoded chunk by chunk (``HiFiGanVocoder.stream``).  It owns everything it touches -- the ring buffer
+    of every tensor of ``stream_plan``, the device cursor the window kernels read the chunk index from, the chunk buffer and the
+    captured graph -- so streams of one vocoder may be interleaved, and one that is dropped leaves nothing behind.
+    ``workspace_bytes``: rings + chunk buffer + cursor; ``captures``: graphs captured so far (at most 1).  ``tail``: a callable given the
+    chunk buffer inside every chunk, after conv_post and before the cursor advances (``SpeechSynthesizer.stream``'s PCM launch); it is
+    captured with the chunk, so it may launch but not allocate."""
+
+    def __init__(self, vocoder, mels, lengths, chunk_frames=32, use_graph=True, clone=True, tail=None):
+        if int(chunk_frames) < 1:
+            raise ValueError(f'stream: chunk_frames must be >= 1, got {chunk_frames}')
+        self.mels, host, self.frames, _ = vocoder._check_batch('stream', mels, lengths)
+        self.packs = vocoder._device_weights()
+        self.plan = stream_plan(vocoder.config, int(chunk_frames))
+        self.bf16 = PRECISIONS[vocoder.precision]
+        self.use_graph, self.clone, self.tail = bool(use_graph), bool(clone), tail
+        B, dev = self.mels.shape[0], self.mels.device
+        self.chunk_samples = self.plan.chunk_frames * HOP
+        self.n_chunks = max(1, -(-max(host) // self.plan.chunk_frames))
+        self.rings = {name: torch.zeros(B, t['ring'], t['channels'], dtype=torch.float32, device=dev) for name, t in self.plan.tensors.items()}
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.audio = torch.zeros(B, self.chunk_samples, dtype=torch.float32, device=dev)
+        self.workspace_bytes = self.plan.ring_bytes(B) + self.audio.numel() * 4 + 4
+        start = torch.arange(self.n_chunks, device=dev)[:, None] * self.chunk_samples
+        self.valid = (self.frames.to(torch.long)[None, :] * HOP - start).clamp(0, self.chunk_samples)       # (chunks, B)
+        self.graph, self.captures, self.done = None, 0, 0
+
+    def __len__(self):
+        return self.n_chunks
+
+    def __iter__(self):
+        return self
+
+    def _launch(self):
+        """The launches of one chunk, the same for every chunk: the window comes from the device cursor, which the last one advances."""
+        L, st = lib(), _stream(self.mels.device)
+        B, n_mel, T = self.mels.shape
+        fr, cur = self.frames.data_ptr(), self.cursor.data_ptr()
+        ring = lambda name: (self.rings[name].data_ptr(), self.plan.tensors[name]['ring'])
+        for ln in self.plan.launches:
+            w, b = self.packs[ln['layer']]
+            N, cin, cout = T * ln['scale'], ln['cin'], ln['cout']
+            if ln['kind'] == 'post':
+                X, nx = ring(ln['x'])
+                L.dx_voc_post_win(X, nx * cin, w.data_ptr(), b.data_ptr(), self.audio.data_ptr(), self.chunk_samples, fr, ln['scale'], B, N,
+                                  self.chunk_samples, cur, ln['step'], ln['lag'], nx - 1, 0, st)
+                continue
+            Y, ny = ring(ln['y'])
+            if ln['x'] == 'mel':
+                X, sxb, sxn, sxc, mx = self.mels.data_ptr(), n_mel * T, 1, T, 0
+            else:
+                X, nx = ring(ln['x'])
+                sxb, sxn, sxc, mx = nx * cin, cin, 1, nx - 1
+            if ln['kind'] == 'pair':
+                w2, b2 = self.packs[ln['layer2']]
+                L.dx_voc_pair_win(X, sxb, w.data_ptr(), b.data_ptr(), w2.data_ptr(), b2.data_ptr(), Y, ny * cout, fr, ln['scale'], B, N, cin,
+                                  ln['taps'], ln['dil'], ln['acc'], self.bf16, cur, ln['step'], ln['lag'], mx, ny - 1, st)
+                continue
+            R, nr = ring(ln['r']) if ln['r'] is not None else (None, 1)
+            L.dx_voc_conv_win(X, sxb, sxn, sxc, w.data_ptr(), b.data_ptr(), Y, ny * cout, R, nr * cout, fr, ln['scale'], B, N, cin, cout,
+                              ln['taps'], ln['dil'], ln['up'], ln['lrelu'], ln['acc'], self.bf16, cur, ln['step'], ln['lag'], mx, ny - 1,
+                              nr - 1, st)
+        if self.tail is not None:
+            self.tail(self.audio)
+        L.dx_voc_stream_advance(cur, st)
+
+    def __next__(self):
+        if self.done >= self.n_chunks:
+            raise StopIteration
+        with torch.no_grad():
+            if self.graph is not None:
+                self.graph.replay()
+            elif self.use_graph and self.done == 1:       # chunk 0 ran eagerly (first audio as early as possible, and the warm-up)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                    self._launch()
+                self.graph, self.captures = graph, self.captures + 1
+                graph.replay()
+            else:
+                self._launch()
+        valid = self.valid[self.done]
+        self.done += 1
+        return (self.audio.clone() if self.clone else self.audio), valid
 
 
 def load_hifigan_vocoder(checkpoint_path=None, device=None, precision='f32'):
