@@ -442,6 +442,37 @@ int dx_prosody_condition(const float* energy, const float* pitch, const long* du
  * audio [B][S] fp32 -> pcm [B][S] int16, 0 at or past sample_lengths[b] (device int32 [B]); both 16-byte aligned, B <= 65535. */
 int dx_pcm16(const float* audio, const int* sample_lengths, short* pcm, int B, long S, void* stream);
 
+/* ---- Griffin-Lim vocoding without a checkpoint (reference griffin_lim.py:100-198; csrc/dx_griffin_lim.hip) -------------------------
+ * fp32 only, n_fft = win = 1024 and hop = 256 only.  No atomics and no workspace; every sum in a fixed order that depends on the row
+ * alone, so two runs, and a batch row and that utterance alone, are bitwise equal. */
+/* griffin_lim.py:150-167, one pass of the while loop of reconstruct_signal_griffin_lim for a padded batch in one launch.
+ * x_in, x_out [B][sxb] (sxb >= 256 T_max + 1024, a multiple of 4; both 16-byte aligned; they must not alias: the caller ping-pongs).
+ * Row b has frames[b] frames (device int32, clamped to [0, T_max]) starting at samples 256 i under the SYMMETRIC Hann window
+ * np.hanning(1024): S_i = rfft(w x[256 i : 256 i + 1024]), P_i = M_i S_i / |S_i| ((M_i, 0) where S_i == 0, as np.angle(0) = 0),
+ * y_i = w irfft(P_i) (DC and Nyquist taken as real), x_out = overlap_add(y) / 2.  mag [B][T_max][513] frame-major (batch stride smb):
+ * the reference's (513, T) magnitudes transposed, repacked once outside the loop.  Samples at or past 256 frames[b] + 768 are written
+ * as 0 (the last 256 samples of the reference's signal are touched by no frame); x_in and mag are never read past a row's own frames.
+ * tab: 3072 floats computed in double on the host and rounded once: the window, then the cos and -sin twiddles of the radix-4 passes
+ * Ns = 4, 16, 64, 256 at offset Ns - 4 as [r - 1][q] = 2 pi q r / (4 Ns), r = 1..3, q < Ns. */
+int dx_gl_iter(const float* x_in, float* x_out, long sxb, const float* mag, long smb, const int* frames, const float* tab, int B,
+               int T_max, int n_fft, int hop, void* stream);
+/* griffin_lim.py:196 (waveform / np.max(abs(waveform))) per row: y[b] = x[b] / max|x[b]| over the row's S samples; an all-zero row
+ * stays zero (the reference divides by zero there).  y may alias x. */
+int dx_gl_peak_normalize(const float* x, float* y, long sxb, int B, long S, void* stream);
+/* HOST pointers: the hop blocks of 256 samples one workgroup of dx_gl_iter owns (its tile; tests place row lengths around it) and the
+ * 32-bit words of the packed filter bank dx_nnls_mel takes */
+int dx_gl_layout(int* tile_blocks, int* pack_words);
+/* griffin_lim.py:100-114 (mel_to_linear -> nnls): mel [B][n_mels][T] LINEAR-scale mel (batch stride smb), lengths device int32 [B] ->
+ * X [B][T][513] frame-major (batch stride sxb), X >= 0, approximately minimising |A X - mel|^2 per frame: x0 = max(pinv(A) mel, 0),
+ * then `iters` FISTA steps of size `step` (1 / |A|_2^2).  The problem is underdetermined (80 equations, 513 unknowns): the reference's
+ * L-BFGS-B answer is one minimiser among many and is not reproduced; the residual is.  Frames at or past lengths[b] are written as 0.
+ * pinvT [n_mels][576] fp32 = pinv(A) transposed, zero past bin 512.  pack (dx_gl_layout's pack_words words, built and validated by the
+ * host: every bin weighs at most two channels, every channel's non-zeros are one run of bins): [0, 576) per bin i0 | i1 << 16,
+ * [576, 1152) and [1152, 1728) its two weights, then 128 words each of every channel's first bin, bin count and weight offset, then
+ * 1536 words of channel-major weights. */
+int dx_nnls_mel(const float* mel, long smb, const int* lengths, const float* pinvT, const void* pack, float step, int iters, float* X,
+                long sxb, int B, int T, int n_mels, int n_freq, void* stream);
+
 /* ---- HiFi-GAN discriminators, forward (reference vocoder/discriminators.py; csrc/dx_disc.hip) -------------------------------------
  * Activations are fp32, channels-last.  A "row" is one independent 1-D signal: a batch row of the Multi-Scale Discriminator
  * ([B][T][C]: rdiv = 1) or one column of the Multi-Period Discriminator's period-folded tensor ([B][H][p][C]: rdiv = p, row = b p + w).

@@ -248,6 +248,14 @@ def price(name, a, geom: Geometry):
         return 'prosody_condition', 'hbm', None, a['B'] * a['L'] * (6 * 4 + 8)
     if name == 'dx_pcm16':
         return 'pcm16', 'hbm', None, a['B'] * a['S'] * (4 + 2)
+    if name == 'dx_gl_iter':                             # per valid frame: 513 magnitudes in, one hop of signal in and out
+        frames = geom.rows(a['B'], a['T_max'])
+        return 'gl_iter', 'hbm', None, frames * (513 * 4 + 2 * 256 * 4)
+    if name == 'dx_gl_peak_normalize':
+        return 'gl_peak_normalize', 'hbm', None, a['B'] * a['S'] * 3 * 4
+    if name == 'dx_nnls_mel':
+        frames = geom.rows(a['B'], a['T'])
+        return 'nnls_mel', 'hbm', None, frames * (a['n_mels'] + 513) * 4
     return name[3:], 'hbm', None, None
 
 

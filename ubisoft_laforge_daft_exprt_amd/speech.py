@@ -17,7 +17,8 @@ import torch
 from ._lib import lib
 from .durations import get_int_durations
 from .inference import GraphedSynthesizer
-from .vocoder import HOP, VocoderStream
+from .griffin_lim import GriffinLimVocoder
+from .vocoder import HOP, HiFiGanVocoder, VocoderStream
 
 PITCH_MODES = {None: 0, 'add': 1, 'multiply': 2}
 PROSODY_KEYS = ('duration_preds', 'energy_preds', 'pitch_preds')      # model.inference's external_prosody (already normalised)
@@ -229,7 +230,8 @@ class _PcmChunks:
 # ---- the whole call ------------------------------------------------------------------------------------------------------------------
 class SpeechSynthesizer:
     """``generate_batch_mel_specs`` from the collated batch to PCM, device-resident: ``model`` a ``DaftExprt``, ``vocoder`` a
-    ``HiFiGanVocoder``.  The acoustic model runs through a ``GraphedSynthesizer`` (``self.synth``: one captured graph per
+    ``HiFiGanVocoder``, or a ``GriffinLimVocoder`` where no checkpoint is at hand (its audio has 256 T + 512 samples per row, and it cannot
+    ``stream``).  The acoustic model runs through a ``GraphedSynthesizer`` (``self.synth``: one captured graph per
     (B, L up to 16, T up to 64) bucket)."""
 
     def __init__(self, model, hparams, vocoder, max_graphs=32):
@@ -279,8 +281,11 @@ class SpeechSynthesizer:
         prep = self.prepare(inputs, pitch_transform, external_prosody, source_stats, alpha_dur, alpha_pitch, alpha_energy)
         encoder_preds, (mel, out_lens), weights = self.synth.run(prep, external_embeddings, external_accent_emb, use_graph)
         with torch.no_grad():
-            audio, _ = self.vocoder.infer_batch(mel, prep['out_host'])
-            sample_lengths = out_lens * HOP
+            audio, voc_lengths = self.vocoder.infer_batch(mel, prep['out_host'])
+            if isinstance(self.vocoder, HiFiGanVocoder):
+                sample_lengths = out_lens * HOP
+            else:                                                 # any other vocoder states its own lengths (Griffin-Lim: 256 T + 512)
+                sample_lengths = torch.as_tensor(voc_lengths).to(device=audio.device, dtype=torch.long)
             pcm = to_pcm16(audio, sample_lengths) if pcm16 else None
         return dict(pcm=pcm, audio=audio, sample_lengths=sample_lengths, mel=mel, output_lengths=out_lens, encoder_preds=encoder_preds,
                     weights=weights)
@@ -291,7 +296,10 @@ class SpeechSynthesizer:
         'chunks', an iterator (with a length) of (pcm (B, 256 chunk_frames) int16 or None, audio fp32, valid (B,) samples of the chunk that
         belong to each row).  The acoustic model runs whole, as in ``__call__`` (it is not autoregressive); the vocoder is
         ``HiFiGanVocoder.stream``, so the chunks concatenated are bitwise ``__call__``'s 'audio' and 'pcm'.  With ``use_graph`` the PCM
-        conversion is one more launch of the captured chunk (samples past a row's end are already 0 there)."""
+        conversion is one more launch of the captured chunk (samples past a row's end are already 0 there).  A ``GriffinLimVocoder``
+        cannot stream (every iteration reads the whole row: the algorithm is not causal) and raises NotImplementedError."""
+        if isinstance(self.vocoder, GriffinLimVocoder):
+            raise NotImplementedError('SpeechSynthesizer.stream: Griffin-Lim is not causal (every iteration reads the whole utterance); use __call__')
         prep = self.prepare(inputs, pitch_transform, external_prosody, source_stats, alpha_dur, alpha_pitch, alpha_energy)
         encoder_preds, (mel, out_lens), weights = self.synth.run(prep, external_embeddings, external_accent_emb, use_graph)
         chunks = _PcmChunks(self.vocoder, mel, prep['out_host'], chunk_frames, pcm16, use_graph)
