@@ -1,0 +1,427 @@
+"""The GEMM family (csrc/dx_gemm.hip, csrc/dx_ffpair.hip) element by element against float64 on the operands the device multiplies,
+on every launch path the host functions choose between (tests/gemm_exact_helpers.py states the reference, the bound and the launch
+plan; tests/test_gemm_exact_cpu.py tests that statement).  Every case asserts, through the restated host-side predicate, the path it
+lands on: no switch forces one.
+
+Not covered: the ``B * N * ldx >= 2^31`` fallback of the deep-K kernel onto the tiled one (too large for a quick test), and the
+bf16x3 mode (tests/test_bf16x3_gpu.py has its own bars).
+"""
+import math
+
+import pytest
+import torch
+
+from tests import gemm_exact_helpers as gx
+
+pytestmark = pytest.mark.gpu
+
+DEV = 'cuda'
+
+
+@pytest.fixture(scope='module')
+def ops():
+    from ubisoft_laforge_daft_exprt_amd import ops as _ops
+    _ops.set_precision('f32')
+    return _ops
+
+
+def randn(*shape, seed=0, scale=1.0):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    return scale * torch.randn(*shape, generator=g, device=DEV)
+
+
+def i32(vals):
+    return torch.tensor(vals, dtype=torch.int32, device=DEV)
+
+
+def report(path, mode, ratio):
+    print(f'GEMM_EXACT path={path} mode={mode} ratio={ratio:.2f}')
+
+
+# Measured max |err| / (S g) per launch path, in units of 2^-24, over every case below (MI355X).  The bar is Q = 16 on every path: none
+# had to be raised towards the cap of 64.  (The wgrad figures move by a few tenths from run to run: split-K atomics.)
+#   path                                   f32    bf16   fp16
+#   conv tiled, 64-token                   4.8    1.8    1.9
+#   conv tiled, 128-token                  7.7    2.5    2.4
+#   conv weight-stationary                  -     2.8    2.9
+#   conv deep-K                             -     1.5    1.5
+#   wgrad f32 kernel (and 16-bit fallback) 1.9    1.5    1.5
+#   wgrad 16-bit narrow                     -     1.8    2.3
+#   wgrad 16-bit wide                       -     2.4    2.8
+#   wgrad batched launch                    -     2.2    2.4
+#   ff pair, 62-token tiles                 -     2.4    2.1
+#   ff pair, 126-token tiles                -     2.4    3.2
+BAR = {path: gx.Q0 for path in ('f32_64', 'f32_128', 'h16_64', 'h16_128', 'ws', 'dk', 'wgrad_f32', 'wgrad_narrow', 'wgrad_wide',
+                                'wgrad_batched', 'ffpair_62', 'ffpair_126')}
+
+# (path, B, N, Cin, Cout, taps): the smallest shapes that select each path of dx_conv_gemm / launch_conv
+CONV_F32 = [('f32_64', 3, 129, 80, 136, 3), ('f32_64', 5, 1, 192, 128, 1),
+            ('f32_128', 64, 200, 64, 1024, 3), ('f32_128', 64, 200, 64, 1024, 1)]            # >= 1024 tiles
+CONV_H16 = ([('h16_64', 4, 37, 192, 384, 1), ('h16_64', 3, 150, 128, 384, 1),               # taps = 1, < 1024 tiles, neither ws nor dk
+             ('h16_128', 3, 150, 128, 1024, 3), ('h16_128', 2, 130, 80, 136, 3),
+             ('h16_128', 4, 130, 288, 128, 3),                                                # CinP = 320 but Cin % 64 != 0: not deep-K
+             ('h16_128', 64, 200, 192, 1024, 1)]                                              # taps = 1 with >= 1024 tiles
+            + [('ws', 13, 640, ci, co, t) for ci in (128, 80) for co in (136, 384) for t in (1, 3)]       # CinP = 128, 65 token tiles
+            + [('dk', 4, 300, ci, co, t) for ci in (256, 320, 1024) for co in (128, 80) for t in (1, 3)]  # even and odd stage counts
+            + [('ws', 70, 250, 128, 1024, 3)]       # 140 token tiles for 32 workgroups per channel tile: strided order, row limits in LDS
+            + [('dk', 1100, 130, 256, 128, 3), ('ws', 1100, 130, 128, 256, 1)])              # > 1024 batch rows: plain tile order
+
+
+def conv_case(ops, mode, path, B, N, Cin, Cout, taps, transpose):
+    """One shape on one path, forward or as the input-gradient convolution (``transpose``: the parameter is (Cin, Cout[, 3]) so that
+    the launch has the table's channels and reads the ``bwd`` image): each activation storage, the whole epilogue set."""
+    h16 = gx.H16.get(mode)
+    tile = 64 if path.endswith('_64') else 128
+    q = BAR[path]
+    worst = 0.0
+    ops.set_precision(mode)
+    try:
+        pshape = ((Cin, Cout) if transpose else (Cout, Cin)) + ((3,) if taps == 3 else ())
+        w = randn(*pshape, seed=1, scale=1.0 / math.sqrt(Cin * taps))
+        pack = ops.PackedWeight(w)
+        w64 = gx.effective_weight(gx.operand64(w, mode), transpose)
+        bias = randn(Cout, seed=2, scale=0.1)
+        x32 = randn(B, N, Cin, seed=3)
+        wide32 = randn(B, N, Cin + 64, seed=4)
+        n_ax = torch.arange(N, device=DEV)[None, :, None]
+        for x16 in ([False, True] if h16 else [False]):
+            xin = x32.to(h16) if x16 else x32
+            tag = f'{path} {mode} x16={x16} T={transpose}'
+            assert gx.conv_path(mode, B, N, Cin, Cout, taps) == path and gx.plain_tile_order(B) == (B == 1100)
+            acc, S = gx.conv64(gx.operand64(xin, mode), w64, bias)
+            kw = dict(transpose=transpose)
+
+            # bias only
+            y = ops.conv_gemm(xin, pack, bias, **kw)
+            worst = max(worst, gx.check(y, acc, S, q=q, what=f'{tag} bias').assert_ok())
+
+            # relu + post_scale / post_shift + relu_aux + out_scale + lens + mask_rows; |post_scale| in [0.5, 1.5) with both signs so that
+            # the float32 rounding of the shifted value (2^-24 |y|, |shift| ~ 0.1) stays a small part of Q S |post_scale out_scale|
+            lens = i32(gx.pick_lens(B, N, tile, 0))
+            valid = n_ax < lens[:, None, None]
+            sc = (0.5 + torch.rand(Cout, device=DEV, generator=torch.Generator(device=DEV).manual_seed(5))) * torch.sign(randn(Cout, seed=6))
+            sh = randn(Cout, seed=7, scale=0.1)
+            aux32 = randn(B, N, Cout, seed=8)
+            for aux in ([aux32, aux32.to(h16)] if h16 else [aux32]):
+                y = ops.conv_gemm(xin, pack, bias, relu=True, post_scale=sc, post_shift=sh, relu_aux=aux, lens=lens, mask_rows=True,
+                                  out_scale=-0.5, **kw)
+                y64, g = gx.epilogue64(acc, S, relu=True, post_scale=sc, post_shift=sh, aux=aux, out_scale=-0.5)
+                worst = max(worst, gx.check(y, y64 * valid, S, g, q=q, exact=~valid, what=f'{tag} full epilogue aux={aux.dtype}').assert_ok())
+
+            # 16-bit-stored output (f32 mode: fp32) with tile skipping at len + 1
+            lens = i32(gx.pick_lens(B, N, tile, 1, open_halo=1))
+            y = ops.conv_gemm(xin, pack, bias, relu=True, lens=lens, halo=1, out_dtype=h16 or torch.float32, **kw)
+            must, beyond, between = gx.row_regions(N, lens, 1, DEV, tile)
+            y64, g = gx.epilogue64(acc, S, relu=True)
+            worst = max(worst, gx.check(y, y64, S, g, q=q, out16=mode if h16 else None, must=must, exact=beyond, between=between,
+                                        what=f'{tag} stored output, halo 1').assert_ok())
+
+            # accumulate onto a random tensor, tile skipping at len
+            lens = i32(gx.pick_lens(B, N, tile, 2, open_halo=0))
+            base = randn(B, N, Cout, seed=9)
+            y = ops.conv_gemm(xin, pack, bias, out=base.clone(), accumulate=True, lens=lens, halo=0, **kw)
+            must, beyond, between = gx.row_regions(N, lens, 0, DEV, tile)
+            worst = max(worst, gx.check(y, base.double() + acc, S + base.double().abs(), q=q, must=must, exact=beyond, exact_value=base,
+                                        between=between, what=f'{tag} accumulate, halo 0').assert_ok())
+
+            # out = one third of a (B, N, 3 Cout) buffer: ldy > Cout, the other thirds untouched
+            buf0 = randn(B, N, 3 * Cout, seed=10)
+            buf = buf0.clone()
+            y = ops.conv_gemm(xin, pack, bias, out=buf[:, :, Cout:2 * Cout], **kw)
+            worst = max(worst, gx.check(y, acc, S, q=q, what=f'{tag} strided out').assert_ok())
+            assert torch.equal(gx._bits(buf[:, :, :Cout]), gx._bits(buf0[:, :, :Cout])), f'{tag}: bytes before the written columns changed'
+            assert torch.equal(gx._bits(buf[:, :, 2 * Cout:]), gx._bits(buf0[:, :, 2 * Cout:])), f'{tag}: bytes after the written columns changed'
+
+            # x = a column slice of a wider tensor: ldx > Cin
+            wide = wide32.to(h16) if x16 else wide32
+            xs = wide[:, :, 32:32 + Cin]
+            assert gx.conv_path(mode, B, N, Cin, Cout, taps, ldx=Cin + 64) == path
+            acc_s, S_s = gx.conv64(gx.operand64(xs, mode), w64, bias)
+            y = ops.conv_gemm(xs, pack, bias, **kw)
+            worst = max(worst, gx.check(y, acc_s, S_s, q=q, what=f'{tag} strided x').assert_ok())
+
+            # rows_exist below and above lens: input rows at or beyond it read as zero, output rows there are zero
+            ll = gx.pick_lens(B, N, tile, 3)
+            re = i32([max(1, n - 3) if b % 2 == 0 else min(N, n + 5) for b, n in enumerate(ll)])
+            lens = i32(ll)
+            acc_r, S_r = gx.conv64(gx.operand64(xin, mode), w64, bias, rows_exist=re)
+            live = n_ax < torch.minimum(lens, re)[:, None, None]
+            y = ops.conv_gemm(xin, pack, bias, lens=lens, mask_rows=True, rows_exist=re, **kw)
+            worst = max(worst, gx.check(y, acc_r * live, S_r, q=q, exact=~live, what=f'{tag} rows_exist').assert_ok())
+    finally:
+        ops.set_precision('f32')
+    report(path, mode, worst)
+
+
+@pytest.mark.parametrize('transpose', [False, True])
+@pytest.mark.parametrize('path,B,N,Cin,Cout,taps', CONV_F32)
+def test_conv_f32_paths(ops, path, B, N, Cin, Cout, taps, transpose):
+    conv_case(ops, 'f32', path, B, N, Cin, Cout, taps, transpose)
+
+
+@pytest.mark.parametrize('transpose', [False, True])
+@pytest.mark.parametrize('mode', ['bf16', 'fp16'])
+@pytest.mark.parametrize('path,B,N,Cin,Cout,taps', CONV_H16)
+def test_conv_16bit_paths(ops, path, B, N, Cin, Cout, taps, mode, transpose):
+    conv_case(ops, mode, path, B, N, Cin, Cout, taps, transpose)
+
+
+@pytest.mark.parametrize('mode', ['f32', 'bf16', 'fp16'])
+def test_one_changed_operand_is_seen_in_the_device_result(ops, mode):
+    """The control: ONE input element of a K = 3072 convolution differs between the device's input and the reference's.  The check must
+    fail, only in the three rows times Cout outputs that element reaches, and in at least half of them (the signal is 2 |x| |w| per output
+    against a bar of 16 * 2^-24 * S: it hides only where the weight it meets is tiny)."""
+    B, N, Cin, Cout = 2, 130, 1024, 128
+    ops.set_precision(mode)
+    try:
+        assert gx.conv_path(mode, B, N, Cin, Cout, 3) == ('f32_64' if mode == 'f32' else 'dk')
+        w = randn(Cout, Cin, 3, seed=1, scale=1.0 / math.sqrt(3 * Cin))
+        pack = ops.PackedWeight(w)
+        x = randn(B, N, Cin, seed=3)
+        x[1, 70, 1023] = 0.75                                      # (representable in every mode)
+        acc, S = gx.conv64(gx.operand64(x, mode), gx.effective_weight(gx.operand64(w, mode)))
+        assert gx.check(ops.conv_gemm(x, pack), acc, S, what='unchanged').ok
+        xd = x.clone()
+        xd[1, 70, 1023] = -0.75
+        v = gx.check(ops.conv_gemm(xd, pack), acc, S, what='one operand negated')
+        reached = torch.zeros(B, N, Cout, dtype=torch.bool, device=DEV)
+        reached[1, 69:72] = True
+        assert not bool((v.fail & ~reached).any()) and float(v.fail[reached].float().mean()) >= 0.5, v.describe()
+    finally:
+        ops.set_precision('f32')
+
+
+# ---- weight gradients ---------------------------------------------------------------------------------------------------------
+# (path, B, N, Cin, Cout, taps); the N sweep puts ragged ends on both sides of the 64- and 128-token chunks (wb_bk) and of the 32-token
+# chunks of the f32 kernel
+WGRAD_F32 = [('wgrad_f32', 3, 65, 80, 136, 1), ('wgrad_f32', 3, 65, 80, 136, 3)]
+WGRAD_H16 = ([('wgrad_narrow', 3, 130, 128, 384, 1), ('wgrad_narrow', 3, 130, 128, 384, 3), ('wgrad_narrow', 2, 90, 256, 136, 3),
+              ('wgrad_wide', 2, 130, 1024, 512, 1), ('wgrad_wide', 2, 130, 1024, 512, 3),
+              ('wgrad_f32', 5, 17, 192, 4, 1)]                                              # Cout % 8 != 0: the f32 kernel in a 16-bit mode
+             + [('wgrad_narrow', 2, n, 128, 136, t) for t in (3, 1) for n in (63, 64, 65, 127, 128, 129)]
+             + [('wgrad_wide', 2, n, 1024, 512, 3) for n in (65, 127)]
+             + [('wgrad_narrow', 520, 20, 128, 136, 1)])                                     # > 512 batch rows: row limits read from memory
+
+
+def wgrad_case(ops, mode, path, B, N, Cin, Cout, taps):
+    h16 = gx.H16.get(mode)
+    q = BAR[path]
+    worst = 0.0
+    ops.set_precision(mode)
+    try:
+        assert 'wgrad_' + gx.wgrad_path(mode, Cin, Cout) == path
+        on16 = h16 is not None and path != 'wgrad_f32'          # the fallback takes fp32-stored operands only ...
+        opmode = mode if on16 else 'f32'                        # ... and multiplies them unrounded
+        w = randn(*((Cout, Cin) + ((3,) if taps == 3 else ())), seed=1, scale=0.05)
+        pack = ops.PackedWeight(w)
+        x32, dy32 = randn(B, N, Cin, seed=2), randn(B, N, Cout, seed=3)
+        g0 = randn(*w.shape, seed=4)
+        n_ax = torch.arange(N, device=DEV)[None, :, None]
+        for dy16, x16 in ([(a, b) for a in (False, True) for b in (False, True)] if on16 else [(False, False)]):
+            chunk = gx.wgrad_chunk(taps, dy16, x16) if path != 'wgrad_f32' else 32
+            ll = gx.pick_lens(B, N, chunk, int(dy16) + 2 * int(x16))
+            lens = i32(ll)
+            re = i32([max(1, n - 3) if b % 2 == 0 else min(N, n + 5) for b, n in enumerate(ll)])
+            for halo, rows_exist in ((-1, None), (0, None), (1, None), (-1, re)):
+                dy = dy32 * (n_ax < lens[:, None, None] + halo) if halo >= 0 else dy32     # the contract: dY is zero beyond len + halo
+                dyin, xin = (dy.to(h16) if dy16 else dy), (x32.to(h16) if x16 else x32)
+                G64, SG, db64, Sb = gx.wgrad64(gx.operand64(dyin, opmode), gx.operand64(xin, opmode), taps, rows_exist)
+                if w.dim() == 2:
+                    G64, SG = G64[:, :, 0], SG[:, :, 0]
+                for start in (torch.zeros_like(g0), g0):
+                    gw, gb = start.clone(), torch.zeros(Cout, device=DEV)
+                    ops.conv_wgrad(dyin, xin, pack, lens if halo >= 0 else None, halo, w_sink=gw, b_sink=gb, rows_exist=rows_exist)
+                    tag = f'{path} {mode} dy16={dy16} x16={x16} halo={halo} rows_exist={rows_exist is not None} onto_random={start is g0}'
+                    worst = max(worst, gx.check(gw, start.double() + G64, SG + start.double().abs(), q=q, what=tag + ' G').assert_ok())
+                    worst = max(worst, gx.check(gb, db64, Sb, q=q, what=tag + ' dbias').assert_ok())
+    finally:
+        ops.set_precision('f32')
+    report(path, mode, worst)
+
+
+@pytest.mark.parametrize('path,B,N,Cin,Cout,taps', WGRAD_F32)
+def test_wgrad_f32_path(ops, path, B, N, Cin, Cout, taps):
+    wgrad_case(ops, 'f32', path, B, N, Cin, Cout, taps)
+
+
+@pytest.mark.parametrize('mode', ['bf16', 'fp16'])
+@pytest.mark.parametrize('path,B,N,Cin,Cout,taps', WGRAD_H16)
+def test_wgrad_16bit_paths(ops, path, B, N, Cin, Cout, taps, mode):
+    wgrad_case(ops, mode, path, B, N, Cin, Cout, taps)
+
+
+@pytest.mark.parametrize('mode', ['bf16', 'fp16'])
+@pytest.mark.parametrize('taps', [1, 3])
+@pytest.mark.parametrize('dy16,x16', [(False, False), (True, False), (False, True), (True, True)])
+def test_wgrad_batched_launch(ops, mode, taps, dy16, x16):
+    """34 queued layers of four shapes with their own lengths and halo rules: more than one launch takes (32), more than one round of
+    workgroups, every job element-wise, onto zeros and onto a running gradient in turn."""
+    h16 = gx.H16[mode]
+    rt = ops.DEFAULT
+    ops.set_precision(mode)
+    try:
+        geo = [(2, 100, 128, 128), (3, 77, 128, 384), (2, 130, 256, 128), (1, 65, 128, 1024)]
+        chunk = gx.wgrad_chunk(taps, dy16, x16)
+        jobs = []
+        rt.defer_wgrad = True
+        for i in range(34):
+            B, N, Cin, Cout = geo[i % 4]
+            halo = (-1, 0, 1)[i % 3]
+            w = randn(*((Cout, Cin) + ((3,) if taps == 3 else ())), seed=100 + i, scale=0.05)
+            pack = ops.PackedWeight(w)
+            lens = i32(gx.pick_lens(B, N, chunk, i))
+            dy = randn(B, N, Cout, seed=300 + i)
+            if halo >= 0:
+                dy = dy * (torch.arange(N, device=DEV)[None, :, None] < lens[:, None, None] + halo)
+            dyin = dy.to(h16) if dy16 else dy
+            x = randn(B, N, Cin, seed=200 + i)
+            xin = x.to(h16) if x16 else x
+            start = randn(*w.shape, seed=400 + i) if i % 2 else torch.zeros_like(w)
+            gw, gb = start.clone(), torch.zeros(Cout, device=DEV)
+            re = i32([N - 5 - b for b in range(B)]) if i % 5 == 4 else None      # some jobs: rows at or beyond rows_exist read as zero
+            assert ops.conv_wgrad(dyin, xin, pack, lens if halo >= 0 else None, halo, w_sink=gw, b_sink=gb, defer=True, rows_exist=re) == (None, None)
+            jobs.append((B * N, Cin, Cout, dyin, xin, start, gw, gb, pack, re))
+        per_launch = ops.WGRAD_BATCH[taps]
+        order = sorted(jobs, key=lambda j: -j[0])                            # flush_wgrads launches the largest B * N first
+        if taps == 1:                                                        # (the k = 3 launches take 8 layers: one round)
+            assert gx.wgrad_batch_rounds([(j[1], j[2]) for j in order[:per_launch]]) > 1
+        assert ops.flush_wgrads(rt) == -(-34 // per_launch) and not rt.wgrad_queue
+        worst = 0.0
+        for i, (_, Cin, Cout, dyin, xin, start, gw, gb, pack, re) in enumerate(jobs):
+            G64, SG, db64, Sb = gx.wgrad64(gx.operand64(dyin, mode), gx.operand64(xin, mode), taps, re)
+            if taps == 1:
+                G64, SG = G64[:, :, 0], SG[:, :, 0]
+            tag = f'wgrad_batched {mode} taps={taps} dy16={dy16} x16={x16} job {i} ({Cin} -> {Cout})'
+            worst = max(worst, gx.check(gw, start.double() + G64, SG + start.double().abs(), q=BAR['wgrad_batched'], what=tag + ' G').assert_ok())
+            worst = max(worst, gx.check(gb, db64, Sb, q=BAR['wgrad_batched'], what=tag + ' dbias').assert_ok())
+    finally:
+        rt.defer_wgrad = False
+        rt.wgrad_queue.clear()
+        ops.set_precision('f32')
+    report('wgrad_batched', mode, worst)
+
+
+# ---- fused feed-forward pair --------------------------------------------------------------------------------------------------
+FF_SHAPES = [(62, 4, 127, [127, 63, 61, 1]), (62, 4, 127, [125, 124, 62, 127]),
+             (126, 32, 379, ([379, 378, 377, 253, 252, 251, 127, 126, 125, 1] * 4)[:32])]
+
+
+@pytest.mark.parametrize('mode', ['bf16', 'fp16'])
+@pytest.mark.parametrize('Fc', [256, 1024])
+@pytest.mark.parametrize('tok,B,N,lens_l', FF_SHAPES)
+def test_ff_pair_forward_and_backward(ops, tok, B, N, lens_l, Fc, mode):
+    """h (and dh) as a 16-bit-stored conv output over the rows the kernel defines (0 .. len, the halo row included); z (and dx) against
+    float64 on the device's OWN hidden tensor, so the second GEMM is operand-exact and carries the fp32-output bar.  The hidden rows a
+    live tile keeps in LDS for its neighbour's stencil are the ones a launch with every tile live stores: that launch provides them (and
+    must agree bit for bit wherever both launches compute)."""
+    h16 = gx.H16[mode]
+    path = f'ffpair_{tok}'
+    q = BAR[path]
+    ops.set_precision(mode)
+    try:
+        assert gx.ff_pair_tile(B, N) == tok
+        lens = i32(lens_l)
+        full = i32([N] * B)
+        w1, b1 = randn(Fc, 128, 3, seed=1, scale=1 / math.sqrt(384)), randn(Fc, seed=2, scale=0.1)
+        w2, b2 = randn(128, Fc, 3, seed=3, scale=1 / math.sqrt(3 * Fc)), randn(128, seed=4, scale=0.1)
+        p1, p2 = ops.PackedWeight(w1), ops.PackedWeight(w2)
+        w1_64, w2_64 = gx.operand64(w1, mode), gx.operand64(w2, mode)
+        x = randn(B, N, 128, seed=5).to(h16)
+        n_ax = torch.arange(N, device=DEV)[None, :, None]
+        must_h, beyond, between_h = gx.row_regions(N, lens, 1, DEV, tok)
+        must_z = n_ax < lens[:, None, None]
+        between_z = ~must_z & ~beyond
+        computed = ~beyond.expand(B, N, Fc)
+
+        # forward
+        z, h = ops.ff_pair(x, p1, p2, b1, b2, lens)
+        _, h_all = ops.ff_pair(x, p1, p2, b1, b2, full)
+        a1, S1 = gx.conv64(x.double(), w1_64, b1)
+        h64, g = gx.epilogue64(a1, S1, relu=True)
+        worst = gx.check(h, h64, S1, g, q=q, out16=mode, must=must_h, exact=beyond, between=between_h, what=f'{path} {mode} h').assert_ok()
+        same = (gx._bits(h) == gx._bits(h_all)) | ((h == 0) & between_h)
+        assert bool(same[computed].all()), 'tile skipping changed a hidden row it computes'
+        z64, S2 = gx.conv64(h_all.double(), w2_64, b2)
+        worst = max(worst, gx.check(z, z64, S2, q=q, must=must_z, exact=beyond, between=between_z, what=f'{path} {mode} z').assert_ok())
+
+        # backward: dh = [h > 0] conv2^T(dz) (16-bit), dx = base + conv1^T(dh)
+        dz = randn(B, N, 128, seed=6).to(h16)
+        base = randn(B, N, 128, seed=7)
+        dx, dh = ops.ff_pair(dz, p1, p2, None, None, lens, backward=True, aux=h_all, out=base.clone(), accumulate=True)
+        _, dh_all = ops.ff_pair(dz, p1, p2, None, None, full, backward=True, aux=h_all, out=base.clone(), accumulate=True)
+        a2, S3 = gx.conv64(dz.double(), gx.effective_weight(w2_64, True))
+        dh64, g = gx.epilogue64(a2, S3, aux=h_all)
+        worst = max(worst, gx.check(dh, dh64, S3, g, q=q, out16=mode, must=must_h, exact=beyond, between=between_h, what=f'{path} {mode} dh').assert_ok())
+        same = (gx._bits(dh) == gx._bits(dh_all)) | ((dh == 0) & between_h)
+        assert bool(same[computed].all()), 'tile skipping changed a hidden-gradient row it computes'
+        a3, S4 = gx.conv64(dh_all.double(), gx.effective_weight(w1_64, True))
+        worst = max(worst, gx.check(dx, base.double() + a3, S4 + base.double().abs(), q=q, must=must_z, exact=beyond, exact_value=base,
+                                    between=between_z, what=f'{path} {mode} dx').assert_ok())
+    finally:
+        ops.set_precision('f32')
+    report(path, mode, worst)
+
+
+# ---- the three routes that write the packed weight images ---------------------------------------------------------------------
+def pack_shapes():
+    """72 parameters of mixed shapes (two launches of dx_pack_weights_host), padded ones included"""
+    special = [(3, 80, 1), (3, 80, 3), (3, 192, 1), (3, 192, 3), (136, 80, 3), (384, 128, 1), (128, 1024, 3), (1024, 128, 3), (80, 256, 1)]
+    cycle = [(128, 128, 1), (136, 192, 3), (4, 192, 1), (256, 80, 3), (384, 320, 1), (80, 288, 3), (128, 64, 1)]
+    return special + [cycle[i % len(cycle)] for i in range(72 - len(special))]
+
+
+@pytest.mark.parametrize('mode', ['f32', 'bf16', 'fp16'])
+def test_pack_routes_write_the_images_of_a_fresh_pack(ops, mode):
+    """After an in-place weight update, ops.repack_all (dx_pack_weights_host) and dx_pack_weights_batched (device descriptor table) write
+    fwd / bwd images bitwise those of a fresh per-weight dx_pack_weights; padding is zero (the images are poisoned first)."""
+    from ubisoft_laforge_daft_exprt_amd._lib import lib
+    rt = ops.Runtime(mode)
+    half = int(mode != 'f32')
+    dt = gx.H16.get(mode, torch.float32)
+    shapes = pack_shapes()
+    assert len(shapes) > gx.PACK_MAX
+    weights = [randn(*((co, ci) + ((3,) if t == 3 else ())), seed=50 + i) for i, (co, ci, t) in enumerate(shapes)]
+    packs = [ops.PackedWeight(w, rt) for w in weights]
+    for pk in packs:
+        pk.image(mode)
+    for i, w in enumerate(weights):
+        w.add_(randn(*w.shape, seed=500 + i, scale=0.1))                      # what an optimiser step does
+    poison = lambda t: t.view(torch.int16).fill_(0x7FC1)                       # NaN patterns in every type
+    fresh = []
+    for pk in packs:
+        img = pk._image(mode)
+        assert img.dims == gx.pack_dims(pk.cout, pk.cin, half)
+        f, b = torch.empty_like(img.fwd), torch.empty_like(img.bwd)
+        poison(f), poison(b)
+        ops._fn('dx_pack_weights', mode)(pk.weight.data_ptr(), f.data_ptr(), b.data_ptr(), pk.cout, pk.cin, pk.taps, half, ops._stream())
+        fresh.append((f, b))
+        poison(img.fwd), poison(img.bwd)
+    assert ops.repack_all(rt, packs) == len(packs)
+    for pk, (f, b) in zip(packs, fresh):
+        img = pk._image(mode)
+        assert torch.equal(gx._bits(img.fwd), gx._bits(f)) and torch.equal(gx._bits(img.bwd), gx._bits(b)), (pk.cout, pk.cin, pk.taps)
+        # the image holds the rounded parameter and zeros, nothing else
+        vals = pk.weight.to(dt).flatten().float()
+        for image in (f, b):
+            assert image.dtype == dt and not bool(torch.isnan(image.float()).any())
+            nz = image.float()[image.float() != 0]
+            assert torch.equal(nz.sort().values, vals[vals != 0].sort().values), (pk.cout, pk.cin, pk.taps)
+        if not half:                                                           # f32 images are plain [taps][CoutP][CinP] / [taps][CinP][CoutP]
+            w3 = gx.effective_weight(pk.weight)
+            fi = f.view(pk.taps, img.dims[0], img.dims[1])
+            assert torch.equal(fi[:, :pk.cout, :pk.cin], w3.permute(2, 0, 1))
+            bi = b.view(pk.taps, img.dims[2], img.dims[3])
+            assert torch.equal(bi[:, :pk.cin, :pk.cout], gx.effective_weight(pk.weight, True).permute(2, 0, 1))
+    # the device-table route
+    recs = b''
+    for pk in packs:
+        img = pk._image(mode)
+        poison(img.fwd), poison(img.bwd)
+        recs += gx.pack_descriptor(pk.weight.data_ptr(), img.fwd.data_ptr(), img.bwd.data_ptr(), pk.cout, pk.cin, pk.taps, img.dims)
+    assert len(recs) == 56 * len(packs)
+    table = torch.frombuffer(bytearray(recs), dtype=torch.uint8).to(DEV)
+    ops._fn('dx_pack_weights_batched', mode)(table.data_ptr(), len(packs), half, ops._stream())
+    torch.cuda.synchronize()
+    for pk, (f, b) in zip(packs, fresh):
+        img = pk._image(mode)
+        assert torch.equal(gx._bits(img.fwd), gx._bits(f)) and torch.equal(gx._bits(img.bwd), gx._bits(b)), (pk.cout, pk.cin, pk.taps)

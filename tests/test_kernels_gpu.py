@@ -1,4 +1,4 @@
-"""Kernel-level parity: every C-ABI entry point against plain PyTorch fp32 math on the same inputs (GPU box only)."""
+"""Kernel-level parity: the training step's C-ABI entry points against plain PyTorch fp32 math on the same inputs, at whole-tensor tolerances (GPU box only); not every entry point or launch path is reached here: test_gemm_exact_gpu.py checks the GEMM family element-wise, path by path, and the pack routes bitwise."""
 import math
 
 import pytest
