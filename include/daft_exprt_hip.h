@@ -339,7 +339,7 @@ int dx_adam_step_dyn(float* p, const float* g, float* m, float* v, long n, float
                      float weight_decay, const float* normsq, float max_norm, const void* scaler, float* norm_out, float* zero_after,
                      void* stream);
 
-/* ---- HiFi-GAN V1 vocoder, inference (reference vocoder/hifigan.py HiFiGANGenerator.forward; csrc/dx_vocoder.hip) ----------------
+/* ---- HiFi-GAN V1 / V2 / V3 vocoder, inference (reference vocoder/hifigan.py HiFiGANGenerator.forward; csrc/dx_vocoder.hip) ----------------
  * Activations are fp32, channels-last [B][samples][C] (conv_pre reads the (B, 80, T) mel through its strides).  frames (device int32
  * [B]) with a samples-per-frame scale gives each batch row's valid length: input rows at or past it read as the conv's zero padding,
  * output rows there are written as 0, so batch row b equals what the same row computes alone (bitwise: fixed summation order, no
@@ -350,22 +350,30 @@ int dx_voc_pack_size(int Cout, int Cin, int taps, int up, int bf16, long* bytes)
  * Cout, 2 up) of ConvTranspose1d(stride up, padding up / 2), packed as up phases of 2 taps (output sample s up + r reads input
  * samples s + base_r and s + base_r + 1, base_r = -1 if r + up / 2 < up else 0). */
 int dx_voc_pack(const float* W, void* Wp, int Cout, int Cin, int taps, int up, int bf16, void* stream);
-/* Y = acc_mode( conv(lrelu?(X)) + bias (+ R) ): a dilated Conv1d ('same' padding dil (taps - 1) / 2; odd taps <= 11) or, with up > 1
+/* Y = acc_mode( conv(lrelu?(X)) + bias (+ R) ): a dilated Conv1d ('same' padding dil (taps - 1) / 2; odd taps <= 11, dil (taps - 1) <= 72; Cout in {16, 32, ..., 512}) or, with up > 1
  * and taps = 2, the polyphase ConvTranspose1d (N input rows -> N up output rows).  X element (b, n, c) at X[b sxb + n sxn + c sxc];
  * Y and R (optional residual, may equal Y; Y must not alias X) are channels-last with batch stride syb; a channels-last X is 16-byte aligned.  Input rows n >= min(frames[b] in_scale, N) are
  * zero.  acc_mode 0: Y = v, 1: Y += v, 2: Y = (Y + v) / 3 (the generator's stage mean over its three ResBlocks). */
 int dx_voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const float* bias, float* Y, long syb, const float* R,
                 const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in, int acc_mode,
                 int bf16, void* stream);
-/* One ResBlock1 pair in one launch (C in {32, 64}): Y = acc_mode( conv2(lrelu(conv1(lrelu(X)) + b1)) + b2 + X ), conv1 dilation dil,
+/* One ResBlock1 pair in one launch (C in {16, 32, 64}): Y = acc_mode( conv2(lrelu(conv1(lrelu(X)) + b1)) + b2 + X ), conv1 dilation dil,
  * conv2 dilation 1, both `taps` wide; the intermediate stays in LDS with its halo.  X, Y channels-last [B][N][C] with batch stride
  * sxb; Y must not alias X. */
 int dx_voc_pair(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y,
                 const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, void* stream);
+/* One ResBlock2 (the V3 generator) in one launch (C in {32, 64}; taps 3, 5 or 7; d1 (taps - 1) <= 18, d2 (taps - 1) <= 72):
+ * x1 = conv_d1(lrelu(X)) + b1 + X, Y = acc_mode( conv_d2(lrelu(x1)) + b2 + x1 ).  x1 is computed with the second conv's halo and stays on
+ * the CU: its bf16 / f32 operand copy in LDS, the fp32 values the second residual adds in registers.  X, Y as for dx_voc_pair. */
+int dx_voc_chain(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y,
+                 const int* frames, int scale, int B, int N, int C, int taps, int d1, int d2, int acc_mode, int bf16, void* stream);
 /* conv_post: Y[b][s] = clip(tanh(conv7(lrelu(X)) + bias), -1, 1) for s < min(frames[b] scale, N), 0 for the rest of the ncols samples.
  * X channels-last [B][N][32] (batch stride sxb), W the folded (1, 32, 7) fp32 weight. */
 int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
                 int B, int N, int ncols, void* stream);
+/* dx_voc_post for C input channels, C in {16, 32} (V2's last stage runs padded to 16): X [B][N][C], W the folded (1, C, 7) weight. */
+int dx_voc_post_c(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                  int B, int N, int ncols, int C, void* stream);
 /* The windowed forms: the streaming generator (vocoder.stream_plan).  A launch reads the chunk index c from the device int32 `cursor`
  * and computes rows [c == 0 ? 0 : c step + lag, (c + 1) step + lag) of its tile-row axis (the rows of X for the conv and the transposed
  * conv, whose output rows are those times up; the samples for the pair and conv_post), clipped by the row's valid length; its grid
@@ -381,8 +389,13 @@ int dx_voc_conv_win(const float* X, long sxb, long sxn, long sxc, const void* Wp
 int dx_voc_pair_win(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y, long syb,
                     const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, const int* cursor,
                     int step, int lag, int mx, int my, void* stream);
+int dx_voc_chain_win(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y, long syb,
+                     const int* frames, int scale, int B, int N, int C, int taps, int d1, int d2, int acc_mode, int bf16,
+                     const int* cursor, int step, int lag, int mx, int my, void* stream);
 int dx_voc_post_win(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
                     int B, int N, int ncols, const int* cursor, int step, int lag, int mx, int my, void* stream);
+int dx_voc_post_c_win(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                      int B, int N, int ncols, int C, const int* cursor, int step, int lag, int mx, int my, void* stream);
 /* *cursor += 1 by one thread: the last launch of a chunk, so that replaying the same launches computes the next window. */
 int dx_voc_stream_advance(int* cursor, void* stream);
 

@@ -1,11 +1,17 @@
-"""HiFi-GAN V1 vocoder throughput: B = 16 synthetic utterances of up to 850 frames (C4-like lengths), synthetic weights.
+"""HiFi-GAN vocoder throughput (V1, or V2 / V3 with --config): B = 16 synthetic utterances of up to 850 frames (C4-like lengths), synthetic weights.
 One JSON line: mel frames/s, seconds of 22.05 kHz audio per second and TFLOP/s against 614 MFLOP per frame, for the HIP path (f32, bf16),
 tests/vocoder_torch.py batched on the same GPU (fp32, bf16) and vocoder_torch at B = 1 per utterance (fp32: the reference's way; bf16).
 Every rate divides VALID frames by the time.  The HIP path computes valid frames only (tiles past a row's length write zeros); the batched
 torch rows compute the whole padded (B, 80, T_max) grid ('frames_computed'), the B = 1 rows exactly the valid frames, so
 'hip_bf16_over_torch_bf16_b1' compares equal work and 'hip_bf16_over_torch_bf16' what a caller with a padded batch gets.
 
-    python tools/bench_vocoder.py [--profile]      # --profile: + per-kernel times of one bf16 and one f32 HIP call
+    python tools/bench_vocoder.py [--config v1|v2|v3] [--profile] [--hip-only]
+
+--profile: + per-kernel times of one bf16 and one f32 HIP call; --hip-only: without the torch rows (whose first calls spend minutes in
+MIOpen's search over the 16 utterance lengths).
+
+--config v2 / v3: the same batch through the V2 / V3 generator (tests/vocoder_variants_torch.py as the torch rows), FLOP per frame
+counted from the configuration's own (unpadded) layer shapes; the default, v1, prints what it always printed.
 """
 import json
 import os
@@ -18,11 +24,24 @@ import torch  # noqa: E402
 
 from tests import vocoder_helpers as vh  # noqa: E402
 from tests import vocoder_torch  # noqa: E402
+from tests import vocoder_variants_torch as vt  # noqa: E402
 from ubisoft_laforge_daft_exprt_amd import profiling, vocoder as voc  # noqa: E402
 from ubisoft_laforge_daft_exprt_amd import _lib  # noqa: E402
 
 MFLOP_PER_FRAME = 614.0
 B, T_MAX = 16, 850
+
+
+def mflop_per_frame(cfg):
+    """2 x taps x Cin x Cout per output sample of every layer of the generator, per mel frame (V1: 614)"""
+    c, scale = cfg['upsample_initial_channel'], 1
+    flop = 2.0 * 7 * cfg['model_in_dim'] * c
+    for u, k, width in zip(cfg['upsample_rates'], cfg['upsample_kernel_sizes'], voc.stage_widths(cfg, padded=False)):
+        flop += 2.0 * k * c * width * scale                       # every input row meets all k taps of the transposed conv
+        c, scale = width, scale * u
+        for kk, ds in zip(cfg['resblock_kernel_sizes'], cfg['resblock_dilation_sizes']):
+            flop += 2.0 * kk * c * c * scale * len(ds) * (1 if str(cfg['resblock']) == '2' else 2)
+    return round((flop + 2.0 * 7 * c * scale) / 1e6, 1)
 
 
 def timed(fn, n=5, warm=2):
@@ -46,7 +65,15 @@ def rates(t, frames, computed=None):
 
 
 def main():
+    global MFLOP_PER_FRAME
     dev = 'cuda'
+    name = sys.argv[sys.argv.index('--config') + 1] if '--config' in sys.argv else 'v1'
+    if name not in voc.CONFIGS:
+        raise SystemExit(f'--config takes one of {sorted(voc.CONFIGS)}, got {name!r}')
+    cfg = voc.CONFIGS[name]()
+    torch_generator = vocoder_torch.generator if name == 'v1' else (lambda m, w: vt.generator(m, w, cfg))
+    if name != 'v1':
+        MFLOP_PER_FRAME = mflop_per_frame(cfg)
     g = torch.Generator().manual_seed(3)
     lengths = torch.randint(T_MAX // 2, T_MAX + 1, (B,), generator=g)
     lengths[0] = T_MAX
@@ -55,26 +82,29 @@ def main():
     for b, n in enumerate(lengths.tolist()):
         mels[b, :, n:] = 0
     lens_dev = lengths.to(dev)
-    sd = vh.state_dict()
+    sd = vh.state_dict() if name == 'v1' else vt.state_dict(name)
     out = {'workload': f'B={B} utterances, {frames} mel frames (max {T_MAX})', 'mflop_per_frame': MFLOP_PER_FRAME}
+    if name != 'v1':
+        out['config'] = name
     voc_by = {}
     with torch.no_grad():
         for prec in ('f32', 'bf16'):
-            v = voc.HiFiGanVocoder(sd, device=dev, precision=prec)
+            v = voc.HiFiGanVocoder(sd, config=cfg, device=dev, precision=prec)
             voc_by[prec] = v
             out[f'hip_{prec}'] = rates(timed(lambda: v.infer_batch(mels, lens_dev)), frames)
-        w32 = vocoder_torch.to(voc_by['f32'].weights, dev)
-        w16 = vocoder_torch.to(voc_by['f32'].weights, dev, torch.bfloat16)
-        padded = B * T_MAX
-        out['torch_fp32_batched'] = rates(timed(lambda: vocoder_torch.generator(mels, w32)), frames, padded)
-        m16 = mels.to(torch.bfloat16)
-        out['torch_bf16_batched'] = rates(timed(lambda: vocoder_torch.generator(m16, w16)), frames, padded)
-        per = [mels[b:b + 1, :, :n].contiguous() for b, n in enumerate(lengths.tolist())]
-        out['torch_fp32_b1'] = rates(timed(lambda: [vocoder_torch.generator(m, w32) for m in per], n=2, warm=1), frames, frames)
-        per16 = [m.to(torch.bfloat16) for m in per]
-        out['torch_bf16_b1'] = rates(timed(lambda: [vocoder_torch.generator(m, w16) for m in per16], n=2, warm=1), frames, frames)
-        out['hip_bf16_over_torch_bf16'] = round(out['torch_bf16_batched']['s'] / out['hip_bf16']['s'], 2)
-        out['hip_bf16_over_torch_bf16_b1'] = round(out['torch_bf16_b1']['s'] / out['hip_bf16']['s'], 2)
+        if '--hip-only' not in sys.argv:
+            w32 = vocoder_torch.to(voc_by['f32'].weights, dev)
+            w16 = vocoder_torch.to(voc_by['f32'].weights, dev, torch.bfloat16)
+            padded = B * T_MAX
+            out['torch_fp32_batched'] = rates(timed(lambda: torch_generator(mels, w32)), frames, padded)
+            m16 = mels.to(torch.bfloat16)
+            out['torch_bf16_batched'] = rates(timed(lambda: torch_generator(m16, w16)), frames, padded)
+            per = [mels[b:b + 1, :, :n].contiguous() for b, n in enumerate(lengths.tolist())]
+            out['torch_fp32_b1'] = rates(timed(lambda: [torch_generator(m, w32) for m in per], n=2, warm=1), frames, frames)
+            per16 = [m.to(torch.bfloat16) for m in per]
+            out['torch_bf16_b1'] = rates(timed(lambda: [torch_generator(m, w16) for m in per16], n=2, warm=1), frames, frames)
+            out['hip_bf16_over_torch_bf16'] = round(out['torch_bf16_batched']['s'] / out['hip_bf16']['s'], 2)
+            out['hip_bf16_over_torch_bf16_b1'] = round(out['torch_bf16_b1']['s'] / out['hip_bf16']['s'], 2)
         if '--profile' in sys.argv:
             geom = profiling.Geometry([lengths.tolist()])
             for prec in ('bf16', 'f32'):

@@ -12,7 +12,7 @@ per case:
 
 All times are host clocks around work that ends in a device synchronise; every shape is warmed by one untimed stream first.
 
-    python tools/bench_vocoder_stream.py [--quick]      # --quick: B = 1 and F = 32 only
+    python tools/bench_vocoder_stream.py [--quick] [--config v1|v2|v3]      # --quick: B = 1 and F = 32 only; --config: the V2 / V3 generator
 """
 import json
 import os
@@ -25,6 +25,7 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 from tests import vocoder_helpers as vh  # noqa: E402
+from tests import vocoder_variants_torch as vt  # noqa: E402
 from tools.bench_vocoder import B, T_MAX, timed  # noqa: E402
 from ubisoft_laforge_daft_exprt_amd import vocoder as voc  # noqa: E402
 
@@ -61,6 +62,10 @@ def whole_stream(v, mels, lens, F, use_graph):
 
 def main():
     quick = '--quick' in sys.argv
+    name = sys.argv[sys.argv.index('--config') + 1] if '--config' in sys.argv else 'v1'
+    if name not in voc.CONFIGS:
+        raise SystemExit(f'--config takes one of {sorted(voc.CONFIGS)}, got {name!r}')
+    cfg = voc.CONFIGS[name]()
     dev = 'cuda'
     g = torch.Generator().manual_seed(3)
     lengths = torch.randint(T_MAX // 2, T_MAX + 1, (B,), generator=g)
@@ -68,12 +73,14 @@ def main():
     mels = ((torch.randn(B, 80, T_MAX, generator=g) * 1.5 - 5.0).clamp(-11.5, 2.0)).to(dev)
     for b, n in enumerate(lengths.tolist()):
         mels[b, :, n:] = 0
-    sd = vh.state_dict()
+    sd = vh.state_dict() if name == 'v1' else vt.state_dict(name)
     ms = lambda t: None if t is None else round(t * 1e3, 3)
     out = {'workload': f'B = {B}: {int(lengths.sum())} mel frames (max {T_MAX}); B = 1: its first row, {T_MAX} frames'}
+    if name != 'v1':
+        out['config'] = name
     with torch.no_grad():
         for prec in ('f32', 'bf16'):
-            v = voc.HiFiGanVocoder(sd, device=dev, precision=prec)
+            v = voc.HiFiGanVocoder(sd, config=cfg, device=dev, precision=prec)
             for nb in ((1,) if quick else (1, B)):
                 m, lens = mels[:nb].contiguous(), lengths[:nb].tolist()
                 whole = timed(lambda: v.infer_batch(m, lens), n=3, warm=1)
@@ -88,7 +95,7 @@ def main():
                         'chunks': n, 'audio_s_per_chunk': round(F * 256 / 22050, 4), 'first_chunk_ms': ms(first),
                         'chunk_replayed_ms': ms(replayed), 'capture_chunk_ms': ms(capture), 'chunk_eager_ms': ms(eager_mean),
                         'streamed_total_s': round(total, 5), 'infer_batch_s': round(whole, 5), 'streamed_over_whole': round(total / whole, 3),
-                        'workspace': {'stream': s.workspace_bytes, 'infer_batch': nb * max(lens) * voc.WORKSPACE_BYTES_PER_FRAME}}
+                        'workspace': {'stream': s.workspace_bytes, 'infer_batch': nb * max(lens) * voc.workspace_bytes_per_frame(cfg)}}
     print(json.dumps(out))
 
 

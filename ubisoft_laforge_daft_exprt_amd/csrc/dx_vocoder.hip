@@ -1,4 +1,4 @@
-// HiFi-GAN V1 generator (reference src/daft_exprt/vocoder/hifigan.py) for inference: mel (B, 80, T) -> waveform (B, 256 T).
+// HiFi-GAN generators V1, V2 and V3 (reference src/daft_exprt/vocoder/hifigan.py) for inference: mel (B, 80, T) -> waveform (B, 256 T).
 //
 // Every convolution of the generator is one MFMA GEMM over a tile of 64 output samples of ONE batch row:
 //   out[m][n] = sum_t sum_c A[m - pad + t*dil][c] * W[t][c][n]
@@ -234,16 +234,20 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs w
     return;
   }
   const int h2 = (p.taps - 1) / 2, h1 = p.dil * h2;
-  const int rows = MIDR + 2 * h1, lda = KC + Op::PAD, ldm = C + Op::PAD;
+  // KP: C rounded up to whole K steps (C = 16 in bf16 mode is half a step: the pack holds zeros there, so A and M must hold zeros too)
+  const int KP = p.KST * Op::KS;
+  const int rows = MIDR + 2 * h1, lda = KC + Op::PAD, ldm = KP + Op::PAD;
   T* A = reinterpret_cast<T*>(voc_smem);
   T* M = A + rows * lda;
+  if (KP > C)                                        // columns C .. KP - 1 of M are operands too: zero (the first sync below orders this)
+    for (int e = threadIdx.x; e < MIDR * ldm; e += THREADS) M[e] = Op::cvt(0.f);
   const int NB = C / 16, WN = NB < 4 ? NB : 4, WM = 4 / WN, wn = w % WN, wm = w / WN;
   const float* X = p.X + b * p.sxb;
   f32x4 acc1[1][MI1];
 #pragma unroll
   for (int j = 0; j < MI1; ++j) acc1[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int c0 = 0; c0 < C; c0 += KC) {
-    const int kcw = min(KC, C - c0);
+  for (int c0 = 0; c0 < KP; c0 += KC) {
+    const int kcw = min(KC, KP - c0);
     __syncthreads();
     voc_stage<BF, WIN>(A, lda, rows, X, C, 1, s0 - h2 - h1, len, c0, kcw, C, 1, win.mx);
     __syncthreads();
@@ -291,14 +295,118 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs w
   }
 }
 
-// conv_post (32 -> 1, k = 7, padding 3) on lrelu(X), then tanh and the clip to [-1, 1]; one output sample per thread.
+struct ChainArgs {
+  const float* X; long sxb;
+  const uint4* W1; const float* b1; const uint4* W2; const float* b2;
+  float* Y; long syb;
+  const int* frames; int scale;
+  int N, C, taps, d1, d2, KST, acc_mode;
+};
+
+// One ResBlock2 (V3) in one launch: x1 = conv_d1(lrelu(X)) + b1 + X, Y = acc_mode( conv_d2(lrelu(x1)) + b2 + x1 ).
+// x1 is computed on 64 + 2 HR rows, HR = the second conv's halo h2 = d2 (taps - 1) / 2 rounded up to 16, and never leaves the CU:
+// lrelu(x1) goes to LDS as the second conv's operand (over the input window, which is dead by then) and the fp32 x1 stays in the
+// accumulators.  Because HR is whole row blocks, the 64 central rows of x1 sit on the same lanes and elements as the output's, HR / 16
+// row blocks further on: conv1 hands row blocks to the waves shifted by that many (wm1), so that the wave that owns an output block
+// also owns its x1 block, and the second residual is the fp32 x1 in both precision modes.  Rows of x1 outside [0, len) are 0, as the
+// two-conv form writes them.  Each sum runs taps-outer, K-steps-inner as in voc_conv_kernel, whatever the tile's start.
+template <bool BF, int MI1, int MI2, bool WIN>
+__global__ void __launch_bounds__(THREADS) voc_chain_kernel(ChainArgs p, WinArgs win) {
+  typedef DxMmaOp<BF> Op;
+  typedef typename Op::T T;
+  extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
+  const int b = blockIdx.y, C = p.C;
+  const int len = min(p.frames[b] * p.scale, p.N);
+  int lo, hi;
+  voc_window<WIN>(win, len, lo, hi);
+  const int s0 = lo + blockIdx.x * VT;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  float* Y = p.Y + b * p.syb;
+  if (WIN) {
+    if (s0 >= hi) return;
+  } else if (s0 >= len) {
+    for (int e = threadIdx.x; e < VT * C; e += THREADS) {
+      const int m = s0 + e / C;
+      if (m < p.N) Y[(long)m * C + e % C] = 0.f;
+    }
+    return;
+  }
+  const int hk = (p.taps - 1) / 2, h1 = p.d1 * hk, h2 = p.d2 * hk;
+  const int HR = (h2 + 15) & ~15, midr = VT + 2 * HR, MB1 = midr / 16;
+  const int KP = p.KST * Op::KS;
+  const int rows = midr + 2 * h1, lda = KC + Op::PAD, ldm = KP + Op::PAD;
+  T* A = reinterpret_cast<T*>(voc_smem);
+  T* M = A;                                          // lrelu(x1) overlays the input window once conv1 has read it
+  const int NB = C / 16, WN = NB < 4 ? NB : 4, WM = 4 / WN, wn = w % WN, wm = w / WN;
+  const int wm1 = (wm + HR / 16) % WM, joff = (wm + HR / 16 - wm1) / WM;     // x1 block wm1 + (joff + j) WM holds output block wm + j WM
+  const float* X = p.X + b * p.sxb;
+  f32x4 x1[1][MI1];
+#pragma unroll
+  for (int j = 0; j < MI1; ++j) x1[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int c0 = 0; c0 < KP; c0 += KC) {
+    const int kcw = min(KC, KP - c0);
+    __syncthreads();
+    voc_stage<BF, WIN>(A, lda, rows, X, C, 1, s0 - HR - h1, len, c0, kcw, C, 1, win.mx);
+    __syncthreads();
+    voc_mma<BF, 1, MI1>(A, lda, MB1, p.taps, p.d1, p.W1, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm1, WM, x1);
+  }
+  __syncthreads();                                   // every wave is done with A
+  const int n = wn * 16 + r;
+  {
+    const float bn = p.b1[n];
+#pragma unroll
+    for (int j = 0; j < MI1; ++j) {
+      const int mb = wm1 + j * WM;
+      if (mb < MB1) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int q = mb * 16 + 4 * g + e, s = s0 - HR + q;
+          float v = 0.f;
+          if (s >= 0 && s < len) v = x1[0][j][e] + bn + X[(long)(WIN ? s & win.mx : s) * C + n];
+          x1[0][j][e] = v;
+          M[q * ldm + n] = Op::cvt(lrelu(v));
+        }
+      }
+    }
+  }
+  __syncthreads();
+  f32x4 acc2[1][MI2];
+#pragma unroll
+  for (int j = 0; j < MI2; ++j) acc2[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  voc_mma<BF, 1, MI2>(M + (HR - h2) * ldm, ldm, VT / 16, p.taps, p.d2, p.W2, NB, p.KST, 0, p.KST, wn, WN, wm, WM, acc2);
+  const float bn = p.b2[n];
+#pragma unroll
+  for (int j2 = 0; j2 < MI2; ++j2) {
+    f32x4 res = f32x4{0.f, 0.f, 0.f, 0.f};           // the fp32 x1 of this output block: a wave-uniform pick, no dynamic indexing
+#pragma unroll
+    for (int j = 0; j < MI1; ++j)
+      if (j == joff + j2) res = x1[0][j];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int m = s0 + (wm + j2 * WM) * 16 + 4 * g + e;
+      if (WIN) {
+        if (m >= hi) continue;
+        const long o = (long)(m & win.my) * C + n;
+        Y[o] = voc_finish(acc2[0][j2][e] + bn + res[e], Y + o, p.acc_mode);
+        continue;
+      }
+      if (m >= p.N) continue;
+      const long o = (long)m * C + n;
+      float v = 0.f;
+      if (m < len) v = voc_finish(acc2[0][j2][e] + bn + res[e], Y + o, p.acc_mode);
+      Y[o] = v;
+    }
+  }
+}
+
+// conv_post (C -> 1, C = 32 or 16, k = 7, padding 3) on lrelu(X), then tanh and the clip to [-1, 1]; one output sample per thread.
 // Y row b holds ncols samples: those at or past the row's valid length are written as 0.  WIN: sample s of the window goes to column
 // s - c step of the chunk buffer.
-template <bool WIN>
+template <bool WIN, int C>
 __global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy,
                                                            const int* frames, int scale, int N, int ncols, WinArgs win) {
-  __shared__ float ws[32 * 7];
-  for (int e = threadIdx.x; e < 32 * 7; e += THREADS) ws[e] = W[e];
+  __shared__ float ws[C * 7];
+  for (int e = threadIdx.x; e < C * 7; e += THREADS) ws[e] = W[e];
   __syncthreads();
   const int b = blockIdx.y;
   const int len = min(frames[b] * scale, N);
@@ -317,9 +425,9 @@ __global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long 
     for (int t = 0; t < 7; ++t) {
       const int n = s - 3 + t;
       if (n < 0 || n >= len) continue;
-      const float4* xr = reinterpret_cast<const float4*>(x + (long)(WIN ? n & win.mx : n) * 32);
+      const float4* xr = reinterpret_cast<const float4*>(x + (long)(WIN ? n & win.mx : n) * C);
 #pragma unroll
-      for (int c4 = 0; c4 < 8; ++c4) {
+      for (int c4 = 0; c4 < C / 4; ++c4) {
         const float4 q = xr[c4];
         acc = __builtin_fmaf(lrelu(q.x), ws[(4 * c4 + 0) * 7 + t], acc);
         acc = __builtin_fmaf(lrelu(q.y), ws[(4 * c4 + 1) * 7 + t], acc);
@@ -387,6 +495,7 @@ int dispatch_conv(const ConvArgs& a, const WinArgs* win, int B, hipStream_t s) {
     case 16: return launch_conv<BF, 4, 4>(a, win, B, s);
     case 8: return launch_conv<BF, 2, 4>(a, win, B, s);
     case 4: return launch_conv<BF, 1, 4>(a, win, B, s);
+    case 1: return launch_conv<BF, 1, 1>(a, win, B, s);      // 16 columns: one column block, the four waves over the four row blocks
     default: return launch_conv<BF, 1, 2>(a, win, B, s);
   }
 }
@@ -395,12 +504,26 @@ template <bool BF, int MI1, int MI2>
 int launch_pair(const PairArgs& a, const WinArgs* win, int B, hipStream_t s) {
   typedef DxMmaOp<BF> Op;
   const int h1 = a.dil * (a.taps - 1) / 2;
-  const size_t smem = ((size_t)(MIDR + 2 * h1) * (KC + Op::PAD) + (size_t)MIDR * (a.C + Op::PAD)) * sizeof(typename Op::T);
+  const size_t smem = ((size_t)(MIDR + 2 * h1) * (KC + Op::PAD) + (size_t)MIDR * (a.KST * Op::KS + Op::PAD)) * sizeof(typename Op::T);
   if (win)
     hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2, true>), dim3(dx_cdiv(win->step + win->lag, VT), B), dim3(THREADS), smem, s, a, *win);
   else
     hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2, false>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a, WinArgs{});
   DX_LAUNCH_CHECK("dx_voc_pair");
+  return DX_OK;
+}
+
+// LDS: the input window, 64 + 2 HR + 2 h1 rows of 64 channels (x1's operand copy overlays it): 178 rows = 48.4 KB at most in f32 mode
+template <bool BF, int MI1, int MI2>
+int launch_chain(const ChainArgs& a, const WinArgs* win, int B, hipStream_t s) {
+  typedef DxMmaOp<BF> Op;
+  const int hk = (a.taps - 1) / 2, HR = (a.d2 * hk + 15) & ~15;
+  const size_t smem = (size_t)(VT + 2 * HR + 2 * a.d1 * hk) * (KC + Op::PAD) * sizeof(typename Op::T);
+  if (win)
+    hipLaunchKernelGGL((voc_chain_kernel<BF, MI1, MI2, true>), dim3(dx_cdiv(win->step + win->lag, VT), B), dim3(THREADS), smem, s, a, *win);
+  else
+    hipLaunchKernelGGL((voc_chain_kernel<BF, MI1, MI2, false>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a, WinArgs{});
+  DX_LAUNCH_CHECK("dx_voc_chain");
   return DX_OK;
 }
 
@@ -423,10 +546,13 @@ int voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const
              const int* frames, int in_scale, int B, int N, int Cin, int Cout, int taps, int dil, int up, int lrelu_in, int acc_mode,
              int bf16, const WinArgs* win, void* stream) {
   DX_REQUIRE(X && Wp && Y && frames, "dx_voc_conv: null pointer");
-  DX_REQUIRE(B > 0 && N > 0 && in_scale > 0 && Cin > 0 && (Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512),
-             "dx_voc_conv: bad shape (Cout in {32, 64, 128, 256, 512})");
-  DX_REQUIRE(up == 1 ? (taps % 2 == 1 && taps <= 11 && dil >= 1 && dil <= 5) : (taps == 2 && dil == 1 && up % 2 == 0 && up <= 8),
-             "dx_voc_conv: bad taps / dilation / upsampling (odd taps <= 11 with dilation <= 5, or a polyphase transposed conv: taps 2, even up <= 8)");
+  DX_REQUIRE(B > 0 && N > 0 && in_scale > 0 && Cin > 0 &&
+                 (Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512),
+             "dx_voc_conv: bad shape (Cout in {16, 32, 64, 128, 256, 512})");
+  // the LDS window is 64 + dil (taps - 1) rows of 64 channels: at most 136 rows, 37 KB in f32 mode
+  DX_REQUIRE(up == 1 ? (taps >= 1 && taps % 2 == 1 && taps <= 11 && dil >= 1 && dil * (taps - 1) <= 72)
+                     : (taps == 2 && dil == 1 && up >= 2 && up % 2 == 0 && up <= 8),
+             "dx_voc_conv: bad taps / dilation / upsampling (odd taps <= 11 with dilation (taps - 1) <= 72, or a polyphase transposed conv: taps 2, even up <= 8)");
   DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_conv: bad acc_mode / bf16");
   DX_REQUIRE((const void*)X != (const void*)Y, "dx_voc_conv: Y must not alias X (tiles read their neighbours' rows); R may alias Y");
   DX_REQUIRE(sxc != 1 || sxn < Cin || (Cin % 4 == 0 && sxn % 4 == 0 && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0),
@@ -446,18 +572,41 @@ int voc_pair(const float* X, long sxb, const void* W1, const float* b1, const vo
              const int* frames, int scale, int B, int N, int C, int taps, int dil, int acc_mode, int bf16, const WinArgs* win, void* stream) {
   DX_REQUIRE(X && W1 && b1 && W2 && b2 && Y && frames, "dx_voc_pair: null pointer");
   DX_REQUIRE(X != Y, "dx_voc_pair: Y must not alias X (tiles read their neighbours' rows)");
-  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && (C == 32 || C == 64) && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
-             "dx_voc_pair: bad shape (C in {32, 64}; sxb %% 4 == 0 and a 16-byte aligned X)");
+  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && (C == 16 || C == 32 || C == 64) && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
+             "dx_voc_pair: bad shape (C in {16, 32, 64}; sxb %% 4 == 0 and a 16-byte aligned X)");
   DX_REQUIRE(voc_taps_ok(taps, dil), "dx_voc_pair: bad taps / dilation (taps 3, 7 or 11; dilation 1, 3 or 5)");
   DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_pair: bad acc_mode / bf16");
   PairArgs a;
   a.X = X; a.sxb = sxb;
   a.W1 = reinterpret_cast<const uint4*>(W1); a.b1 = b1; a.W2 = reinterpret_cast<const uint4*>(W2); a.b2 = b2;
   a.Y = Y; a.syb = syb; a.frames = frames; a.scale = scale;
-  a.N = N; a.C = C; a.taps = taps; a.dil = dil; a.KST = C / (bf16 ? 32 : 16); a.acc_mode = acc_mode;
+  a.N = N; a.C = C; a.taps = taps; a.dil = dil; a.KST = dx_cdiv(C, bf16 ? 32 : 16); a.acc_mode = acc_mode;
   hipStream_t s = (hipStream_t)stream;
+  if (C == 16) return bf16 ? launch_pair<true, 2, 1>(a, win, B, s) : launch_pair<false, 2, 1>(a, win, B, s);
   if (C == 64) return bf16 ? launch_pair<true, 5, 4>(a, win, B, s) : launch_pair<false, 5, 4>(a, win, B, s);
   return bf16 ? launch_pair<true, 3, 2>(a, win, B, s) : launch_pair<false, 3, 2>(a, win, B, s);
+}
+
+// dx_voc_chain (win == nullptr; syb = sxb) and dx_voc_chain_win
+int voc_chain(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y, long syb,
+              const int* frames, int scale, int B, int N, int C, int taps, int d1, int d2, int acc_mode, int bf16, const WinArgs* win,
+              void* stream) {
+  DX_REQUIRE(X && W1 && b1 && W2 && b2 && Y && frames, "dx_voc_chain: null pointer");
+  DX_REQUIRE(X != Y, "dx_voc_chain: Y must not alias X (tiles read their neighbours' rows)");
+  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && (C == 32 || C == 64) && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
+             "dx_voc_chain: bad shape (C in {32, 64}; sxb %% 4 == 0 and a 16-byte aligned X)");
+  // ten row blocks of x1 at most (HR <= 48), and an input window of at most 178 rows
+  DX_REQUIRE((taps == 3 || taps == 5 || taps == 7) && d1 >= 1 && d2 >= 1 && d1 * (taps - 1) <= 18 && d2 * (taps - 1) <= 72,
+             "dx_voc_chain: bad taps / dilation (taps 3, 5 or 7; d1 (taps - 1) <= 18, d2 (taps - 1) <= 72)");
+  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_chain: bad acc_mode / bf16");
+  ChainArgs a;
+  a.X = X; a.sxb = sxb;
+  a.W1 = reinterpret_cast<const uint4*>(W1); a.b1 = b1; a.W2 = reinterpret_cast<const uint4*>(W2); a.b2 = b2;
+  a.Y = Y; a.syb = syb; a.frames = frames; a.scale = scale;
+  a.N = N; a.C = C; a.taps = taps; a.d1 = d1; a.d2 = d2; a.KST = C / (bf16 ? 32 : 16); a.acc_mode = acc_mode;
+  hipStream_t s = (hipStream_t)stream;
+  if (C == 64) return bf16 ? launch_chain<true, 10, 4>(a, win, B, s) : launch_chain<false, 10, 4>(a, win, B, s);
+  return bf16 ? launch_chain<true, 5, 2>(a, win, B, s) : launch_chain<false, 5, 2>(a, win, B, s);
 }
 
 }  // namespace
@@ -522,29 +671,66 @@ int dx_voc_pair_win(const float* X, long sxb, const void* W1, const float* b1, c
   return voc_pair(X, sxb, W1, b1, W2, b2, Y, syb, frames, scale, B, N, C, taps, dil, acc_mode, bf16, &w, stream);
 }
 
-int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
-                int B, int N, int ncols, void* stream) {
+int dx_voc_chain(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y,
+                 const int* frames, int scale, int B, int N, int C, int taps, int d1, int d2, int acc_mode, int bf16, void* stream) {
+  return voc_chain(X, sxb, W1, b1, W2, b2, Y, sxb, frames, scale, B, N, C, taps, d1, d2, acc_mode, bf16, nullptr, stream);
+}
+
+int dx_voc_chain_win(const float* X, long sxb, const void* W1, const float* b1, const void* W2, const float* b2, float* Y, long syb,
+                     const int* frames, int scale, int B, int N, int C, int taps, int d1, int d2, int acc_mode, int bf16,
+                     const int* cursor, int step, int lag, int mx, int my, void* stream) {
+  DX_REQUIRE(voc_win_ok(cursor, step, lag, mx, my, 0), "dx_voc_chain_win: bad window (cursor, step > 0, lag >= 0, masks 0 or 2^k - 1)");
+  DX_REQUIRE(C > 0 && (mx ? (long)(mx + 1) : (long)N) * C <= sxb && (my ? (long)(my + 1) : (long)N) * C <= syb,
+             "dx_voc_chain_win: a ring (or the N rows of an unringed tensor) does not fit its batch stride");
+  const WinArgs w = voc_win(cursor, step, lag, mx, my, 0);
+  return voc_chain(X, sxb, W1, b1, W2, b2, Y, syb, frames, scale, B, N, C, taps, d1, d2, acc_mode, bf16, &w, stream);
+}
+
+int dx_voc_post_c(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                  int B, int N, int ncols, int C, void* stream) {
   DX_REQUIRE(X && W && bias && Y && frames, "dx_voc_post: null pointer");
+  DX_REQUIRE(C == 16 || C == 32, "dx_voc_post: bad channel count (C in {16, 32})");
   DX_REQUIRE(B > 0 && N > 0 && scale > 0 && ncols >= N && ldy >= ncols && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
              "dx_voc_post: bad shape (ncols >= N, ldy >= ncols, sxb %% 4 == 0, a 16-byte aligned X)");
-  hipLaunchKernelGGL(voc_post_kernel<false>, dim3(dx_cdiv(ncols, THREADS), B), dim3(THREADS), 0, (hipStream_t)stream,
-                     X, sxb, W, bias, Y, ldy, frames, scale, N, ncols, WinArgs{});
+  const dim3 grid(dx_cdiv(ncols, THREADS), B);
+  if (C == 32)
+    hipLaunchKernelGGL((voc_post_kernel<false, 32>), grid, dim3(THREADS), 0, (hipStream_t)stream, X, sxb, W, bias, Y, ldy, frames, scale, N,
+                       ncols, WinArgs{});
+  else
+    hipLaunchKernelGGL((voc_post_kernel<false, 16>), grid, dim3(THREADS), 0, (hipStream_t)stream, X, sxb, W, bias, Y, ldy, frames, scale, N,
+                       ncols, WinArgs{});
   DX_LAUNCH_CHECK("dx_voc_post");
+  return DX_OK;
+}
+
+int dx_voc_post(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                int B, int N, int ncols, void* stream) {
+  return dx_voc_post_c(X, sxb, W, bias, Y, ldy, frames, scale, B, N, ncols, 32, stream);
+}
+
+int dx_voc_post_c_win(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
+                      int B, int N, int ncols, int C, const int* cursor, int step, int lag, int mx, int my, void* stream) {
+  DX_REQUIRE(X && W && bias && Y && frames, "dx_voc_post_win: null pointer");
+  DX_REQUIRE(C == 16 || C == 32, "dx_voc_post_win: bad channel count (C in {16, 32})");
+  DX_REQUIRE(voc_win_ok(cursor, step, lag, mx, my, 0) && my == 0, "dx_voc_post_win: bad window (cursor, step > 0, lag >= 0, mx 0 or 2^k - 1, my 0: the chunk buffer is not a ring)");
+  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && ncols >= step + lag && ldy >= ncols && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0 &&
+                 (mx ? (long)(mx + 1) : (long)N) * C <= sxb,
+             "dx_voc_post_win: bad shape (ncols >= step + lag, ldy >= ncols, sxb %% 4 == 0 and holding X's ring, a 16-byte aligned X)");
+  const WinArgs w = voc_win(cursor, step, lag, mx, 0, 0);
+  const dim3 grid(dx_cdiv(step + lag, THREADS), B);
+  if (C == 32)
+    hipLaunchKernelGGL((voc_post_kernel<true, 32>), grid, dim3(THREADS), 0, (hipStream_t)stream, X, sxb, W, bias, Y, ldy, frames, scale, N,
+                       ncols, w);
+  else
+    hipLaunchKernelGGL((voc_post_kernel<true, 16>), grid, dim3(THREADS), 0, (hipStream_t)stream, X, sxb, W, bias, Y, ldy, frames, scale, N,
+                       ncols, w);
+  DX_LAUNCH_CHECK("dx_voc_post_win");
   return DX_OK;
 }
 
 int dx_voc_post_win(const float* X, long sxb, const float* W, const float* bias, float* Y, int ldy, const int* frames, int scale,
                     int B, int N, int ncols, const int* cursor, int step, int lag, int mx, int my, void* stream) {
-  DX_REQUIRE(X && W && bias && Y && frames, "dx_voc_post_win: null pointer");
-  DX_REQUIRE(voc_win_ok(cursor, step, lag, mx, my, 0) && my == 0, "dx_voc_post_win: bad window (cursor, step > 0, lag >= 0, mx 0 or 2^k - 1, my 0: the chunk buffer is not a ring)");
-  DX_REQUIRE(B > 0 && N > 0 && scale > 0 && ncols >= step + lag && ldy >= ncols && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0 &&
-                 (mx ? (long)(mx + 1) : (long)N) * 32 <= sxb,
-             "dx_voc_post_win: bad shape (ncols >= step + lag, ldy >= ncols, sxb %% 4 == 0 and holding X's ring, a 16-byte aligned X)");
-  const WinArgs w = voc_win(cursor, step, lag, mx, 0, 0);
-  hipLaunchKernelGGL(voc_post_kernel<true>, dim3(dx_cdiv(step + lag, THREADS), B), dim3(THREADS), 0, (hipStream_t)stream,
-                     X, sxb, W, bias, Y, ldy, frames, scale, N, ncols, w);
-  DX_LAUNCH_CHECK("dx_voc_post_win");
-  return DX_OK;
+  return dx_voc_post_c_win(X, sxb, W, bias, Y, ldy, frames, scale, B, N, ncols, 32, cursor, step, lag, mx, my, stream);
 }
 
 int dx_voc_stream_advance(int* cursor, void* stream) {

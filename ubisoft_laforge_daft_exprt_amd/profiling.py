@@ -178,11 +178,11 @@ def price(name, a, geom: Geometry):
         return 'relu_bwd', 'hbm', None, 3 * a['n'] * 4
     if name == 'dx_colsum':
         return 'colsum', 'hbm', None, a['rows'] * a['C'] * (2 if a['x_bf16'] else 4)
-    if name in ('dx_voc_conv_win', 'dx_voc_pair_win', 'dx_voc_post_win'):       # the streaming forms: the rows of ONE interior window
+    if name in ('dx_voc_conv_win', 'dx_voc_pair_win', 'dx_voc_chain_win', 'dx_voc_post_win', 'dx_voc_post_c_win'):   # the streaming forms: the rows of ONE interior window
         return price(name[:-4], dict(a, window_rows=a['B'] * a['step']), geom)  # (B x step; chunk 0 computes lag more, the last chunks fewer)
     if name == 'dx_voc_stream_advance':
         return 'voc_stream_advance', 'hbm', None, 8
-    if name in ('dx_voc_conv', 'dx_voc_pair', 'dx_voc_post'):   # HiFi-GAN vocoder: N rows of samples, frames * scale of them valid
+    if name in ('dx_voc_conv', 'dx_voc_pair', 'dx_voc_chain', 'dx_voc_post', 'dx_voc_post_c'):   # HiFi-GAN vocoder: N rows of samples, frames * scale of them valid
         s = max(1, a['in_scale'] if name == 'dx_voc_conv' else a['scale'])
         rows = g('window_rows') or geom.rows(a['B'], a['N'] // s) * s
         op = 'bf16' if g('bf16') else 'f32'
@@ -193,7 +193,9 @@ def price(name, a, geom: Geometry):
             return f'{kind}<{op}>', 'mfma', 2.0 * a['taps'] * a['Cin'] * a['Cout'] * out_rows, byt
         if name == 'dx_voc_pair':                        # two convs, X read, Y written (+ read when accumulating)
             return f'voc_pair<{op}>', 'mfma', 2.0 * 2 * a['taps'] * a['C'] * a['C'] * rows, rows * a['C'] * 4 * (2 + (a['acc_mode'] > 0))
-        return 'voc_post', 'hbm', None, rows * 32 * 4 + a['B'] * a['ncols'] * 4
+        if name == 'dx_voc_chain':                       # a ResBlock2: two convs (the halo's recomputation is not credited), X read, Y written
+            return f'voc_chain<{op}>', 'mfma', 2.0 * 2 * a['taps'] * a['C'] * a['C'] * rows, rows * a['C'] * 4 * (2 + (a['acc_mode'] > 0))
+        return 'voc_post', 'hbm', None, rows * (a['C'] if name == 'dx_voc_post_c' else 32) * 4 + a['B'] * a['ncols'] * 4
     if name == 'dx_voc_pack':
         return 'voc_pack', 'hbm', None, a['Cout'] * a['Cin'] * a['taps'] * max(1, a['up']) * (4 + (2 if a['bf16'] else 4))
     if name == 'dx_disc_conv':                           # HiFi-GAN discriminators: rows of N positions, no lengths

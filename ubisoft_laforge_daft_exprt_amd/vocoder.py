@@ -1,6 +1,6 @@
-"""HiFi-GAN V1 vocoder on gfx950: mel spectrogram -> waveform (reference src/daft_exprt/vocoder/hifigan.py).
+"""HiFi-GAN vocoder (generators V1, V2 and V3) on gfx950: mel spectrogram -> waveform (reference src/daft_exprt/vocoder/hifigan.py).
 
-``HiFiGANGenerator`` owns the reference generator's weight-normed state-dict layout (234 tensors); ``HiFiGanVocoder`` /
+``HiFiGANGenerator`` owns the reference generator's weight-normed state-dict layout (234 tensors for V1 and V2, 69 for V3); ``HiFiGanVocoder`` /
 ``load_hifigan_vocoder`` are drop-ins for the reference helpers (``.infer``: one utterance, numpy in or out) and add
 ``.infer_batch``: a padded (B, 80, T_max) mel batch on the device -- what ``DaftExprt.inference`` and ``GraphedSynthesizer`` return --
 to (B, 256 T_max) audio on the device, row b bitwise equal to ``mel[b, :, :lengths[b]]`` vocoded alone -- and ``.stream``: the same
@@ -24,7 +24,7 @@ from .discriminators import _packed
 NEG_SLOPE = 0.1     # leaky-ReLU slope before every convolution (applied inside the kernels)
 HOP = 256           # waveform samples per mel frame: the product of the four upsampling factors
 
-# HiFi-GAN V1, the one configuration the kernels are built for: 80 mel bins into 512 channels; four (factor, transposed-conv width)
+# HiFi-GAN V1, the default configuration (V2 and V3: v2_config, v3_config below): 80 mel bins into 512 channels; four (factor, transposed-conv width)
 # stages that halve the channels; three ResBlock1 per stage with kernel widths 3, 7, 11, each at dilations 1, 3, 5; 22.05 kHz.
 N_MELS, WIDTH = 80, 512
 STAGES = ((8, 16), (8, 16), (2, 4), (2, 4))
@@ -39,30 +39,102 @@ def v1_config() -> dict:
                 resblock_kernel_sizes=list(RESBLOCK_WIDTHS), resblock_dilation_sizes=[list(RESBLOCK_DILATIONS) for _ in RESBLOCK_WIDTHS])
 
 
+def v2_config() -> dict:
+    """HiFi-GAN V2: V1 at a quarter of the width (128 channels into stages of 64, 32, 16 and 8)."""
+    return dict(v1_config(), upsample_initial_channel=128)
+
+
+def v3_config() -> dict:
+    """HiFi-GAN V3: 256 channels, three stages (8, 8, 4) of 128, 64 and 32 channels, three ResBlock2 per stage (two dilated convs with
+    a residual each) of widths 3, 5, 7."""
+    return dict(sampling_rate=22050, model_in_dim=N_MELS, upsample_initial_channel=256, resblock='2', upsample_rates=[8, 8, 4],
+                upsample_kernel_sizes=[16, 16, 8], resblock_kernel_sizes=[3, 5, 7], resblock_dilation_sizes=[[1, 2], [2, 6], [3, 12]])
+
+
+CONFIGS = {'v1': v1_config, 'v2': v2_config, 'v3': v3_config}     # the whitelist: the kernels are instantiated per width
 DEFAULT_CONFIG = v1_config()
 PRECISIONS = {'f32': 0, 'bf16': 1}
-WORKSPACE_BYTES_PER_FRAME = 5 * 8192 * 4    # five fp32 activation buffers of at most 8192 values per mel frame (C x samples per frame)
+MIN_WIDTH = 16                               # one MFMA column block: a narrower stage (V2's last, 8 channels) runs zero-padded to it
+WORKSPACE_BYTES_PER_FRAME = 5 * 8192 * 4    # V1: five fp32 activation buffers of at most 8192 values per mel frame (C x samples per frame)
 DEFAULT_WORKSPACE_BYTES = 4 << 30            # infer_batch's default bound: larger batches run in chunks of utterances
+# The ResBlock2 shapes (precision, channels, kernel width) that run as one dx_voc_chain launch: those for which it was measured faster
+# than two dx_voc_conv launches (DESIGN.md section 10; tools/bench_vocoder_chain.py).  With bf16 operands the block is bound by its
+# traffic and the fused form, which never writes x1, wins at widths 3 and 5; at width 7 the 36-row halo makes it compute 2.5 times
+# the first conv and it loses, as it does at every width in f32 mode, where the MFMAs run at the vector rate.  Every other shape, the
+# 128-wide stage among them (the kernel has no instantiation for it), runs as two dx_voc_conv launches.
+CHAIN_SHAPES = frozenset(('bf16', c, k) for c in (64, 32) for k in (3, 5))
 
 
 def check_config(config) -> dict:
-    """None -> V1; any other configuration than V1 (lists or tuples alike) raises NotImplementedError: there is no fallback."""
+    """None -> V1; V1, V2 and V3 (lists or tuples alike) pass; any other configuration raises NotImplementedError: there is no
+    fallback."""
     if config is None:
         return v1_config()
 
     def canon(v):
         return tuple(canon(x) for x in v) if isinstance(v, (list, tuple)) else str(v)
-    want = {k: canon(v) for k, v in v1_config().items()}
     got = {k: canon(v) for k, v in dict(config).items()}
-    if got != want:
-        raise NotImplementedError(f'the gfx950 HiFi-GAN kernels implement V1 only ({v1_config()}); got {dict(config)}')
+    if not any(got == {k: canon(v) for k, v in make().items()} for make in CONFIGS.values()):
+        raise NotImplementedError('the gfx950 HiFi-GAN kernels implement exactly three configurations, '
+                                  + '; '.join(f'{name.upper()} ({make()})' for name, make in CONFIGS.items()) + f'; got {dict(config)}')
     return dict(config)
+
+
+def stage_widths(config=None, padded=True) -> list:
+    """Channels of each upsampling stage; ``padded``: as the kernels run them (at least MIN_WIDTH)."""
+    cfg = check_config(config)
+    widths = [int(cfg['upsample_initial_channel']) >> (i + 1) for i in range(len(cfg['upsample_rates']))]
+    return [max(c, MIN_WIDTH) for c in widths] if padded else widths
+
+
+def workspace_bytes_per_frame(config=None) -> int:
+    """Bytes of ``infer_batch``'s activation workspace per mel frame of the longest row: five fp32 buffers of the widest tensor (padded
+    channels x samples per frame).  V1: WORKSPACE_BYTES_PER_FRAME."""
+    cfg = check_config(config)
+    widest, scale = int(cfg['upsample_initial_channel']), 1
+    for u, c in zip(cfg['upsample_rates'], stage_widths(cfg)):
+        scale *= int(u)
+        widest = max(widest, c * scale)
+    return 5 * widest * 4
+
+
+def pad_folded_weights(weights: dict, config=None) -> dict:
+    """{layer: (folded weight, bias)} with every stage narrower than MIN_WIDTH (V2's last: 8 channels) zero-padded to it: the stage's
+    transposed conv gets zero weights and a zero bias for output channels 8-15, its ResBlock convs zero rows, columns and biases there,
+    and conv_post zero weights for input channels 8-15.  Those channels are then exactly 0 through every lrelu, residual and
+    (y + v) / 3 -- a sum of zeros plus a zero bias -- and the real channels get the same sums plus added zeros, so the waveform is the
+    unpadded generator's.  Layers of the other stages are returned as they are."""
+    cfg = check_config(config)
+    n_blocks = len(cfg['resblock_kernel_sizes'])
+    out = dict(weights)
+
+    def pad(name, dims):                 # zero-pad the listed dims of the weight (and the bias, if dim 0 of a Conv1d is among them)
+        w, b = out[name]
+        for d in dims:
+            if w.shape[d] < MIN_WIDTH:
+                shape = list(w.shape)
+                shape[d] = MIN_WIDTH - w.shape[d]
+                w = torch.cat([w, w.new_zeros(shape)], dim=d)
+        if b.shape[0] < MIN_WIDTH and name != 'conv_post':
+            b = torch.cat([b, b.new_zeros(MIN_WIDTH - b.shape[0])])
+        out[name] = (w.contiguous(), b.contiguous())
+
+    real = stage_widths(cfg, padded=False)
+    for i, c in enumerate(real):
+        if c >= MIN_WIDTH:
+            continue
+        pad(f'ups.{i}', (1,))                                         # ConvTranspose1d weight is (Cin, Cout, k)
+        for name in weights:
+            if name.startswith('resblocks.') and i * n_blocks <= int(name.split('.')[1]) < (i + 1) * n_blocks:
+                pad(name, (0, 1))
+        pad('conv_post', (1,))
+    return out
 
 
 # ---- the streaming plan (host only) ----------------------------------------------------------------------------------------------
 class StreamPlan:
     """What ``stream_plan`` returns.  ``tensors``: {name: {'scale' samples per mel frame, 'channels', 'lag', 'left', 'ring'}} for every
-    tensor between two layers; ``launches``: the chunk's launches in order, each a dict (kind 'conv' / 'pair' / 'post', layer names, the
+    tensor between two layers; ``launches``: the chunk's launches in order, each a dict (kind 'conv' / 'pair' / 'chain' / 'post', layer names, the
     names of its tensors 'x', 'y', 'r', the shape, 'scale' = tile rows per frame, 'step' = chunk_frames * scale, 'lag', and its 'left' /
     'right' reach in rows of x); ``lookahead``: mel frames past a chunk's own that the chunk reads."""
 
@@ -73,18 +145,20 @@ class StreamPlan:
         return sum(batch * t['ring'] * t['channels'] * 4 for t in self.tensors.values())
 
 
-def stream_plan(config=None, chunk_frames=32) -> StreamPlan:
-    """The schedule of the chunked generator.  After chunk c, rows [0, min(len, (c + 1) F scale + lag)) of a tensor exist; chunk c
+def stream_plan(config=None, chunk_frames=32, precision='f32') -> StreamPlan:
+    """The schedule of the chunked generator (``precision``: V3 fuses some ResBlock2 under bf16 only, CHAIN_SHAPES).  After chunk c, rows [0, min(len, (c + 1) F scale + lag)) of a tensor exist; chunk c
     computes rows [c F scale + lag (0 for c = 0), (c + 1) F scale + lag) of it, F = chunk_frames.
 
     Lags come from walking the generator backwards from conv_post's output (lag 0): a tensor's lag is the largest, over the launches that
     read it, of that launch's own lag (in the tensor's rows) plus its right reach -- dil (k - 1) / 2 for a dilated conv, that plus
-    (k - 1) / 2 for a fused pair, 3 for conv_post, 1 for a polyphase transposed conv (output row s up + r reads input rows s + base_r and
+    (k - 1) / 2 for a fused pair, (d1 + d2) (k - 1) / 2 for a fused ResBlock2 chain, 3 for conv_post, 1 for a polyphase transposed conv (output row s up + r reads input rows s + base_r and
     s + base_r + 1, base_r in {-1, 0}), whose output lag is rounded up to a multiple of up so that its window is whole input rows.  A
     residual and an accumulated output are read at the launch's own rows.  Row n of a tensor lives at slot n & (ring - 1); the ring is
     the power of two that holds the chunk-0 window (F scale + lag) and, for every reader, F scale + (lag - reader's lag) + the reader's
     left reach: what is resident between the oldest row a reader of chunk c still needs and the newest row chunk c has written."""
     cfg = check_config(config)
+    if precision not in PRECISIONS:
+        raise ValueError(f'stream_plan: precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
     F = int(chunk_frames)
     if F < 1:
         raise ValueError(f'stream_plan: chunk_frames must be >= 1, got {chunk_frames}')
@@ -102,17 +176,26 @@ def stream_plan(config=None, chunk_frames=32) -> StreamPlan:
     x, scale = tensor('conv_pre', 1, c), 1
     conv('conv_pre', 'mel', x, cfg['model_in_dim'], c, 7, 1, 1, 0, 0, 1, 3)
     ks, ds = cfg['resblock_kernel_sizes'], cfg['resblock_dilation_sizes']
-    for i, u in enumerate(cfg['upsample_rates']):
-        up_out = tensor(f'ups.{i}', scale * u, c // 2)
-        conv(f'ups.{i}', x, up_out, c, c // 2, 2, 1, u, 1, 0, scale, 1)
-        scale, c = scale * u, c // 2
+    resblock2 = str(cfg['resblock']) == '2'
+    for i, (u, cs) in enumerate(zip(cfg['upsample_rates'], stage_widths(cfg))):     # cs: the stage's channels as they run (padded)
+        up_out = tensor(f'ups.{i}', scale * u, cs)
+        conv(f'ups.{i}', x, up_out, c, cs, 2, 1, u, 1, 0, scale, 1)
+        scale, c = scale * u, cs
         total = tensor(f'sum.{i}', scale, c)
         for j, k in enumerate(ks):
             name, src, h = f'resblocks.{i * len(ks) + j}', up_out, (k - 1) // 2
+            last = len(ds[j]) - 1
+            if resblock2 and last == 1 and (precision, c, k) in CHAIN_SHAPES:    # both dilations of the ResBlock2 in one launch
+                reach = (ds[j][0] + ds[j][1]) * h
+                L.append(dict(kind='chain', layer=f'{name}.convs.0', layer2=f'{name}.convs.1', x=src, y=total, r=None, cin=c, cout=c,
+                              taps=k, dil=ds[j][0], dil2=ds[j][1], up=1, lrelu=1, acc=min(j, 2), scale=scale, left=reach, right=reach))
+                continue
             for p, d in enumerate(ds[j]):
-                dst = total if p == 2 else tensor(f'{name}.x{p}', scale, c)
-                acc = min(j, 2) if p == 2 else 0
-                if c <= 64:
+                dst = total if p == last else tensor(f'{name}.x{p}', scale, c)
+                acc = min(j, 2) if p == last else 0
+                if resblock2:                                                 # x <- conv_d(lrelu x) + x
+                    conv(f'{name}.convs.{p}', src, dst, c, c, k, d, 1, 1, acc, scale, d * h, r=src)
+                elif c <= 64:
                     L.append(dict(kind='pair', layer=f'{name}.convs1.{p}', layer2=f'{name}.convs2.{p}', x=src, y=dst, r=None, cin=c, cout=c,
                                   taps=k, dil=d, up=1, lrelu=1, acc=acc, scale=scale, left=d * h + h, right=d * h + h))
                 else:
@@ -159,10 +242,16 @@ class _WNConv(nn.Module):
 
 
 class _ResBlock1(nn.Module):
-    def __init__(self, channels, k):
+    def __init__(self, channels, k, dilations):
         super().__init__()
-        self.convs1 = nn.ModuleList([_WNConv((channels, channels, k), channels) for _ in range(3)])
-        self.convs2 = nn.ModuleList([_WNConv((channels, channels, k), channels) for _ in range(3)])
+        self.convs1 = nn.ModuleList([_WNConv((channels, channels, k), channels) for _ in dilations])
+        self.convs2 = nn.ModuleList([_WNConv((channels, channels, k), channels) for _ in dilations])
+
+
+class _ResBlock2(nn.Module):
+    def __init__(self, channels, k, dilations):
+        super().__init__()
+        self.convs = nn.ModuleList([_WNConv((channels, channels, k), channels) for _ in dilations])
 
 
 class HiFiGANGenerator(nn.Module):
@@ -176,8 +265,11 @@ class HiFiGANGenerator(nn.Module):
         self.conv_pre = _WNConv((c0, self.config['model_in_dim'], 7), c0)
         self.ups = nn.ModuleList([_WNConv((c0 >> i, c0 >> (i + 1), k), c0 >> (i + 1))
                                   for i, k in enumerate(self.config['upsample_kernel_sizes'])])
-        self.resblocks = nn.ModuleList([_ResBlock1(c0 >> (i + 1), k) for i in range(4) for k in self.config['resblock_kernel_sizes']])
-        self.conv_post = _WNConv((1, c0 >> 4, 7), 1)
+        block = _ResBlock2 if str(self.config['resblock']) == '2' else _ResBlock1
+        widths = stage_widths(self.config, padded=False)        # the checkpoint's own widths: padding happens after folding
+        self.resblocks = nn.ModuleList([block(c, k, d) for c in widths
+                                        for k, d in zip(self.config['resblock_kernel_sizes'], self.config['resblock_dilation_sizes'])])
+        self.conv_post = _WNConv((1, widths[-1], 7), 1)
 
     def layer_names(self):
         return [n[:-len('.bias')] for n, _ in self.named_parameters() if n.endswith('.bias')]
@@ -215,8 +307,35 @@ def _checkpoint_state(checkpoint) -> dict:
     return checkpoint
 
 
+def config_from_state(state: dict) -> dict:
+    """The configuration a generator state dict was saved under, from conv_pre's width, the number of ``ups`` and the ResBlock kind
+    (``convs1`` / ``convs2``: ResBlock1; ``convs``: ResBlock2); NotImplementedError if they match none of V1, V2, V3."""
+    if 'conv_pre.bias' not in state:
+        raise KeyError("generator checkpoint has no bias for 'conv_pre'")
+    width = int(state['conv_pre.bias'].shape[0])
+    n_ups = len({k.split('.')[1] for k in state if k.startswith('ups.')})
+    kind = '2' if any(k.startswith('resblocks.0.convs.') for k in state) else '1'
+    for make in CONFIGS.values():
+        cfg = make()
+        if (cfg['upsample_initial_channel'], len(cfg['upsample_rates']), cfg['resblock']) == (width, n_ups, kind):
+            return cfg
+    raise NotImplementedError(f'a generator of {width} channels, {n_ups} upsampling stages and ResBlock{kind} is none of HiFi-GAN V1 '
+                              f'(512, 4, ResBlock1), V2 (128, 4, ResBlock1), V3 (256, 3, ResBlock2)')
+
+
 class HiFiGanVocoder:
-    """Drop-in for the reference ``HiFiGanVocoder`` on gfx950.  ``checkpoint_path``: a local generator checkpoint (or its loaded dict)."""
+    """Drop-in for the reference ``HiFiGanVocoder`` on gfx950.  ``checkpoint_path``: a local generator checkpoint (or its loaded dict);
+    ``config``: None (V1) or one of ``v1_config()``, ``v2_config()``, ``v3_config()``.  ``from_checkpoint`` reads it off the weights."""
+
+    @classmethod
+    def from_checkpoint(cls, checkpoint, device='cuda', precision='f32'):
+        """A vocoder for a V1, V2 or V3 checkpoint (a local path or its loaded dict), the configuration taken from the shapes."""
+        if checkpoint is None:
+            raise ValueError('from_checkpoint: checkpoint_path is required (a local HiFi-GAN generator checkpoint)')
+        state = _checkpoint_state(checkpoint)
+        vocoder = cls(state, config=config_from_state(state), device=device, precision=precision)
+        vocoder.checkpoint_path = checkpoint
+        return vocoder
 
     def __init__(self, checkpoint_path=None, config=None, device='cuda', precision='f32'):
         if checkpoint_path is None:
@@ -257,15 +376,16 @@ class HiFiGanVocoder:
                 raise RuntimeError('HiFiGanVocoder runs on the GPU (gfx950 HIP kernels); there is no CPU path')
             dev = lambda t: t.to(self.device).contiguous()
             P = {}
-            w, b = self.weights['conv_pre']
+            weights = pad_folded_weights(self.weights, self.config)     # a stage narrower than 16 channels runs zero-padded to 16
+            w, b = weights['conv_pre']
             P['conv_pre'] = (self._pack(w), dev(b))
             for i, u in enumerate(self.config['upsample_rates']):
-                w, b = self.weights[f'ups.{i}']
+                w, b = weights[f'ups.{i}']
                 P[f'ups.{i}'] = (self._pack(w, up=u), dev(b))
-            for name, (w, b) in self.weights.items():
+            for name, (w, b) in weights.items():
                 if name.startswith('resblocks.'):
                     P[name] = (self._pack(w), dev(b))
-            w, b = self.weights['conv_post']
+            w, b = weights['conv_post']
             P['conv_post'] = (dev(w), dev(b))
             self._packs = P
         return self._packs
@@ -314,7 +434,7 @@ class HiFiGanVocoder:
         chunk_frames)) steps, each yielding (audio (B, 256 chunk_frames) fp32 on the device, valid (B,) int64 on the device).  Step c
         holds samples [256 c chunk_frames, 256 (c + 1) chunk_frames) of every row, bit for bit what ``infer_batch`` writes there;
         ``valid`` counts those that belong to the row (0 once the row has ended; the rest of its chunk is 0).  Every step runs the same
-        61 launches (the generator's 60 and the cursor's advance) on ring buffers whose size depends on chunk_frames and B alone (``stream.workspace_bytes``); with ``use_graph``
+        launches (the generator's -- 60 for V1 -- and the cursor's advance) on ring buffers whose size depends on chunk_frames and B alone (``stream.workspace_bytes``); with ``use_graph``
         they are captured once, while the second chunk is due, and replayed from then on.  ``clone=False`` yields the stream's own
         buffer, overwritten by the next step.  The mel is read in place until the last step: leave it unchanged meanwhile."""
         return VocoderStream(self, mels, lengths, chunk_frames, use_graph, clone)
@@ -324,8 +444,8 @@ class HiFiGanVocoder:
         out_lens: one small device-to-host copy sizes the work).  -> (audio (B, 256 T_max) fp32 on the device, sample_lengths).
         Row b is bitwise ``mel[b, :, :lengths[b]]`` vocoded alone; samples at or past 256 lengths[b] are 0.  max_workspace_bytes
         bounds the activation workspace: the batch then runs in chunks of consecutive utterances (bitwise the same result).  A chunk
-        of b utterances whose longest has n frames takes b * n * WORKSPACE_BYTES_PER_FRAME (160 KB per frame, sized by the LONGEST row:
-        2.2 GB for 16 rows of 850 frames); one utterance longer than the bound still runs, alone.  None: no bound, one chunk.
+        of b utterances whose longest has n frames takes b * n * workspace_bytes_per_frame(config) (V1 and V3: 160 KB per frame, V2: 80 KB;
+        sized by the LONGEST row: 2.2 GB for 16 rows of 850 frames of V1); one utterance longer than the bound still runs, alone.  None: no bound, one chunk.
         Nothing is returned before the last sample exists: ``stream`` yields the same samples chunk by chunk, in a workspace that does
         not grow with the length."""
         mels, host, frames, sample_lengths = self._check_batch('infer_batch', mels, lengths)
@@ -333,12 +453,13 @@ class HiFiGanVocoder:
         dev = mels.device
         P = self._device_weights()
         audio = torch.empty(B, T * HOP, dtype=torch.float32, device=dev)
+        per_frame = workspace_bytes_per_frame(self.config)
         b0 = 0
         while b0 < B:
             b1, n = b0 + 1, max(1, host[b0])
             while b1 < B:
                 n2 = max(n, host[b1])
-                if max_workspace_bytes is not None and (b1 + 1 - b0) * n2 * WORKSPACE_BYTES_PER_FRAME > max_workspace_bytes:
+                if max_workspace_bytes is not None and (b1 + 1 - b0) * n2 * per_frame > max_workspace_bytes:
                     break
                 b1, n = b1 + 1, n2
             self._run(P, mels, frames, audio, b0, b1, n)
@@ -346,12 +467,12 @@ class HiFiGanVocoder:
         return audio, sample_lengths
 
     def _run(self, P, mels, frames, audio, b0, b1, N):
-        """Utterances b0 .. b1-1 with N frames of work each (N >= their lengths): 60 launches."""
+        """Utterances b0 .. b1-1 with N frames of work each (N >= their lengths): 60 launches for V1, 42 for V2, 23 for V3 (19 with bf16 operands)."""
         L, st = lib(), _stream(mels.device)
         bf16 = PRECISIONS[self.precision]
         B, T = b1 - b0, mels.shape[2]
         n_mel = mels.shape[1]
-        ws = torch.empty(5, B * N * 8192, dtype=torch.float32, device=mels.device)
+        ws = torch.empty(5, B * N * (workspace_bytes_per_frame(self.config) // 20), dtype=torch.float32, device=mels.device)
         S, U, Pb, Q, M = (ws[i].data_ptr() for i in range(5))
         fr = frames.data_ptr() + 4 * b0
         c = self.config['upsample_initial_channel']
@@ -360,17 +481,29 @@ class HiFiGanVocoder:
                       fr, 1, B, N, n_mel, c, 7, 1, 1, 0, 0, bf16, st)
         rows, scale = N, 1
         ks, ds = self.config['resblock_kernel_sizes'], self.config['resblock_dilation_sizes']
-        for i, u in enumerate(self.config['upsample_rates']):
+        resblock2 = str(self.config['resblock']) == '2'
+        for i, (u, cs) in enumerate(zip(self.config['upsample_rates'], stage_widths(self.config))):
             w, b = P[f'ups.{i}']
-            L.dx_voc_conv(S, rows * c, c, 1, w.data_ptr(), b.data_ptr(), U, rows * u * (c // 2), None,
-                          fr, scale, B, rows, c, c // 2, 2, 1, u, 1, 0, bf16, st)
-            rows, scale, c = rows * u, scale * u, c // 2
+            L.dx_voc_conv(S, rows * c, c, 1, w.data_ptr(), b.data_ptr(), U, rows * u * cs, None,
+                          fr, scale, B, rows, c, cs, 2, 1, u, 1, 0, bf16, st)
+            rows, scale, c = rows * u, scale * u, cs
             for j, k in enumerate(ks):
-                src = U
+                src, last = U, len(ds[j]) - 1
+                name = f'resblocks.{i * len(ks) + j}'
+                if resblock2 and last == 1 and (self.precision, c, k) in CHAIN_SHAPES:
+                    (w1, b1), (w2, b2) = P[f'{name}.convs.0'], P[f'{name}.convs.1']
+                    L.dx_voc_chain(U, rows * c, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), S,
+                                   fr, scale, B, rows, c, k, ds[j][0], ds[j][1], min(j, 2), bf16, st)
+                    continue
                 for p, d in enumerate(ds[j]):
-                    dst = (Pb, Q, S)[p]
-                    acc = min(j, 2) if p == 2 else 0              # the stage sum: first ResBlock writes, second adds, third adds and / 3
-                    name = f'resblocks.{i * len(ks) + j}'
+                    dst = S if p == last else (Pb, Q)[p]
+                    acc = min(j, 2) if p == last else 0           # the stage sum: first ResBlock writes, second adds, third adds and / 3
+                    if resblock2:
+                        w1, b1 = P[f'{name}.convs.{p}']
+                        L.dx_voc_conv(src, rows * c, c, 1, w1.data_ptr(), b1.data_ptr(), dst, rows * c, src,
+                                      fr, scale, B, rows, c, c, k, d, 1, 1, acc, bf16, st)
+                        src = dst
+                        continue
                     (w1, b1), (w2, b2) = P[f'{name}.convs1.{p}'], P[f'{name}.convs2.{p}']
                     if c <= 64:
                         L.dx_voc_pair(src, rows * c, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), dst,
@@ -382,8 +515,8 @@ class HiFiGanVocoder:
                                       fr, scale, B, rows, c, c, k, 1, 1, 1, acc, bf16, st)
                     src = dst
         w, b = P['conv_post']
-        L.dx_voc_post(S, rows * c, w.data_ptr(), b.data_ptr(), audio.data_ptr() + 4 * b0 * T * HOP, T * HOP,
-                      fr, scale, B, rows, T * HOP, st)
+        L.dx_voc_post_c(S, rows * c, w.data_ptr(), b.data_ptr(), audio.data_ptr() + 4 * b0 * T * HOP, T * HOP,
+                        fr, scale, B, rows, T * HOP, c, st)
 
 
 class VocoderStream:
@@ -399,7 +532,7 @@ class VocoderStream:
             raise ValueError(f'stream: chunk_frames must be >= 1, got {chunk_frames}')
         self.mels, host, self.frames, _ = vocoder._check_batch('stream', mels, lengths)
         self.packs = vocoder._device_weights()
-        self.plan = stream_plan(vocoder.config, int(chunk_frames))
+        self.plan = stream_plan(vocoder.config, int(chunk_frames), vocoder.precision)
         self.bf16 = PRECISIONS[vocoder.precision]
         self.use_graph, self.clone, self.tail = bool(use_graph), bool(clone), tail
         B, dev = self.mels.shape[0], self.mels.device
@@ -430,8 +563,8 @@ class VocoderStream:
             N, cin, cout = T * ln['scale'], ln['cin'], ln['cout']
             if ln['kind'] == 'post':
                 X, nx = ring(ln['x'])
-                L.dx_voc_post_win(X, nx * cin, w.data_ptr(), b.data_ptr(), self.audio.data_ptr(), self.chunk_samples, fr, ln['scale'], B, N,
-                                  self.chunk_samples, cur, ln['step'], ln['lag'], nx - 1, 0, st)
+                L.dx_voc_post_c_win(X, nx * cin, w.data_ptr(), b.data_ptr(), self.audio.data_ptr(), self.chunk_samples, fr, ln['scale'], B,
+                                    N, self.chunk_samples, cin, cur, ln['step'], ln['lag'], nx - 1, 0, st)
                 continue
             Y, ny = ring(ln['y'])
             if ln['x'] == 'mel':
@@ -443,6 +576,11 @@ class VocoderStream:
                 w2, b2 = self.packs[ln['layer2']]
                 L.dx_voc_pair_win(X, sxb, w.data_ptr(), b.data_ptr(), w2.data_ptr(), b2.data_ptr(), Y, ny * cout, fr, ln['scale'], B, N, cin,
                                   ln['taps'], ln['dil'], ln['acc'], self.bf16, cur, ln['step'], ln['lag'], mx, ny - 1, st)
+                continue
+            if ln['kind'] == 'chain':
+                w2, b2 = self.packs[ln['layer2']]
+                L.dx_voc_chain_win(X, sxb, w.data_ptr(), b.data_ptr(), w2.data_ptr(), b2.data_ptr(), Y, ny * cout, fr, ln['scale'], B, N, cin,
+                                   ln['taps'], ln['dil'], ln['dil2'], ln['acc'], self.bf16, cur, ln['step'], ln['lag'], mx, ny - 1, st)
                 continue
             R, nr = ring(ln['r']) if ln['r'] is not None else (None, 1)
             L.dx_voc_conv_win(X, sxb, sxn, sxc, w.data_ptr(), b.data_ptr(), Y, ny * cout, R, nr * cout, fr, ln['scale'], B, N, cin, cout,
