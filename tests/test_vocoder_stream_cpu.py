@@ -1,65 +1,15 @@
 """CPU checks of the streaming vocoder's host side: the plan's lags and rings by interval bookkeeping, the plan's schedule run in
 float64 on ring buffers against the plain-torch generator, and argument validation."""
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from tests import vocoder_helpers as vh
 from tests import vocoder_torch
+from tests.vocoder_stream_helpers import emulate, simulate
 from ubisoft_laforge_daft_exprt_amd import vocoder as voc
 
 CHUNKS = (1, 3, 8, 32)
 LENGTHS = (1, 13, 14, 65, 300)
-
-
-def _window(ln, c, length):
-    """rows [lo, hi) of the launch's tile-row axis in chunk c, for an utterance of ``length`` frames"""
-    lo = 0 if c == 0 else c * ln['step'] + ln['lag']
-    return lo, min((c + 1) * ln['step'] + ln['lag'], length * ln['scale'])
-
-
-def _simulate(plan, length):
-    """Runs the plan on row NUMBERS: every tensor is a ring of row numbers.  A read asserts that the row was computed and still sits in
-    its slot -- which also catches any earlier write that landed on a row a later launch still reads -- and a write that the row is new."""
-    slots = {n: np.full(t['ring'], -1) for n, t in plan.tensors.items()}                       # slot -> row number held
-    writes = {n: np.zeros(length * t['scale'], dtype=np.int64) for n, t in plan.tensors.items()}   # row -> times written
-    audio = np.zeros(length * voc.HOP, dtype=np.int64)
-
-    def read(name, a, b, who):
-        t = plan.tensors[name]
-        n = np.arange(max(a, 0), min(b, length * t['scale']))
-        assert (writes[name][n] > 0).all(), (who, name, 'reads a row that is not computed yet')
-        assert (slots[name][n & (t['ring'] - 1)] == n).all(), (who, name, 'reads a row that was evicted from its ring')
-
-    for c in range(max(1, -(-length // plan.chunk_frames))):
-        for ln in plan.launches:
-            lo, hi = _window(ln, c, length)
-            if hi <= lo:
-                continue
-            who, up = (c, ln['layer']), ln['up']
-            if ln['x'] == 'mel':
-                assert hi - 1 + ln['right'] < (c + 1) * plan.chunk_frames + plan.lookahead
-            else:
-                read(ln['x'], lo - ln['left'], hi + ln['right'], who)
-            if ln['r'] is not None:
-                read(ln['r'], lo * up, hi * up, who)
-            if ln['y'] == 'audio':
-                assert c * ln['step'] <= lo and hi <= (c + 1) * ln['step']
-                audio[lo:hi] += 1
-                continue
-            t = plan.tensors[ln['y']]
-            n = np.arange(lo * up, hi * up)
-            if ln['acc']:
-                read(ln['y'], lo * up, hi * up, who)
-            else:
-                assert (writes[ln['y']][n] == 0).all(), (who, 'writes a row twice')
-                assert len(set((n & (t['ring'] - 1)).tolist())) == len(n), (who, 'one launch writes two rows to one slot')
-                slots[ln['y']][n & (t['ring'] - 1)] = n
-            writes[ln['y']][n] += 1
-    for name in plan.tensors:                          # every row exactly once (three times for a stage sum: write, add, add and / 3)
-        assert (writes[name] == sum(1 for ln in plan.launches if ln['y'] == name)).all(), name
-    assert (audio == 1).all()
 
 
 @pytest.mark.parametrize('chunk_frames', CHUNKS)
@@ -76,7 +26,7 @@ def test_plan_bookkeeping(chunk_frames):
     sums = [plan.tensors[f'sum.{i}']['lag'] for i in range(4)]
     assert sums[3] == 3                                # conv_post's right reach
     for length in LENGTHS:
-        _simulate(plan, length)
+        simulate(plan, length)
 
 
 def test_ring_sizes_do_not_depend_on_the_length_and_grow_with_the_chunk():
@@ -103,72 +53,13 @@ def reference64(weights64):
         return mel, {n: vocoder_torch.generator(mel[:, :, :n], weights64)[0] for n in (14, 41)}
 
 
-def _rows(ring, a, b, length):
-    """logical rows [a, b) of a ring (rows, C): zeros outside [0, length)"""
-    n = torch.arange(a, b)
-    out = ring[n & (ring.shape[0] - 1)].clone()
-    out[(n < 0) | (n >= length)] = 0
-    return out
-
-
-def _emulate(plan, mel, length, W):
-    """The plan's launches with F.conv1d / F.conv_transpose1d on float64 rings; -> the concatenated chunks."""
-    lr = lambda v: F.leaky_relu(v, 0.1)
-    rings = {n: torch.full((t['ring'], t['channels']), float('nan'), dtype=torch.float64) for n, t in plan.tensors.items()}
-    chunks = []
-    for c in range(max(1, -(-length // plan.chunk_frames))):
-        out = torch.zeros(plan.chunk_frames * voc.HOP, dtype=torch.float64)
-        for ln in plan.launches:
-            lo, hi = _window(ln, c, length)
-            if hi <= lo:
-                continue
-            n_x = length * ln['scale']
-            a, b = lo - ln['left'], hi + ln['right']
-            if ln['x'] == 'mel':
-                idx = torch.arange(a, b)
-                x = mel[0, :, idx.clamp(0, length - 1)].T.clone()
-                x[(idx < 0) | (idx >= length)] = 0
-            else:
-                x = _rows(rings[ln['x']], a, b, n_x)
-            w, bias = W[ln['layer']]
-            xin = (lr(x) if ln['lrelu'] else x).T[None]
-            if ln['kind'] == 'post':
-                y = torch.tanh(F.conv1d(xin, w, bias))[0, 0]
-                out[lo - c * ln['step']: hi - c * ln['step']] = y
-                continue
-            up = ln['up']
-            if ln['kind'] == 'pair':
-                h = (ln['taps'] - 1) // 2
-                t = F.conv1d(xin, w, bias, dilation=ln['dil'])[0].T                  # rows [lo - h, hi + h)
-                s = torch.arange(lo - h, hi + h)
-                t[(s < 0) | (s >= n_x)] = 0
-                w2, b2 = W[ln['layer2']]
-                y = F.conv1d(lr(t).T[None], w2, b2)[0].T + _rows(rings[ln['x']], lo, hi, n_x)
-            elif up > 1:
-                y = F.conv_transpose1d(xin, w, bias, stride=up, padding=up // 2)[0].T      # rows [(lo - 1) up, (hi + 1) up)
-                y = y[up: up + (hi - lo) * up]
-            else:
-                y = F.conv1d(xin, w, bias, dilation=ln['dil'])[0].T
-            ring = rings[ln['y']]
-            slot = torch.arange(lo * up, hi * up) & (ring.shape[0] - 1)
-            if ln['r'] is not None:
-                y = y + _rows(rings[ln['r']], lo * up, hi * up, n_x * up)
-            if ln['acc'] == 1:
-                y = ring[slot] + y
-            elif ln['acc'] == 2:
-                y = (ring[slot] + y) / 3
-            ring[slot] = y
-        chunks.append(out)
-    return torch.cat(chunks)
-
-
 @pytest.mark.parametrize('chunk_frames', [3, 8])
 @pytest.mark.parametrize('length', [14, 41])
 def test_schedule_in_float64_equals_the_whole_generator(weights64, reference64, length, chunk_frames):
     mel, refs = reference64
     plan = voc.stream_plan(None, chunk_frames)
     with torch.no_grad():
-        got = _emulate(plan, mel[:, :, :length], length, weights64)
+        got = emulate(plan, mel[:, :, :length], length, weights64)
     ref = refs[length]
     assert got.shape[0] == -(-length // chunk_frames) * chunk_frames * voc.HOP
     err = (got[:ref.shape[0]] - ref).abs().max().item()

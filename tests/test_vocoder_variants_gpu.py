@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import helpers
-from tests import vocoder_variants_torch as vt
+from tests import vocoder_helpers as vh
 from ubisoft_laforge_daft_exprt_amd import vocoder as voc
 from ubisoft_laforge_daft_exprt_amd._lib import lib
 
@@ -24,16 +24,16 @@ def _stream():
 
 @pytest.fixture(scope='module')
 def vocoders():
-    return {(n, p): voc.HiFiGanVocoder(vt.state_dict(n), config=CONFIGS[n](), device=DEV, precision=p)
-            for n in vt.NAMES for p in ('f32', 'bf16')}
+    return {(n, p): voc.HiFiGanVocoder(vh.state_dict(n), config=CONFIGS[n](), device=DEV, precision=p)
+            for n in vh.VARIANTS for p in ('f32', 'bf16')}
 
 
 @pytest.fixture(scope='module')
 def batch():
     """{name: (mels (3, 80, 40) of lengths (40, 13, 1) from the fixture, zero past each row's end)}"""
     out = {}
-    for name in vt.NAMES:
-        gold = vt.golden(name)
+    for name in vh.VARIANTS:
+        gold = vh.variant_golden(name)
         mels = torch.zeros(len(BATCH), 80, max(BATCH))
         for b, n in enumerate(BATCH):
             mels[b, :, :n] = torch.from_numpy(gold['mels'][gold['lengths'].index(n)])
@@ -47,9 +47,9 @@ def whole(vocoders, batch):
     return {key: v.infer_batch(batch[key[0]], list(BATCH))[0] for key, v in vocoders.items()}
 
 
-@pytest.mark.parametrize('name', vt.NAMES)
+@pytest.mark.parametrize('name', vh.VARIANTS)
 def test_f32_matches_reference_golden(vocoders, name):
-    gold = vt.golden(name)
+    gold = vh.variant_golden(name)
     for n, mel, ref in zip(gold['lengths'], gold['mels'], gold['wavs']):
         got = vocoders[name, 'f32'].infer(mel)
         err = np.abs(got - ref)
@@ -58,11 +58,11 @@ def test_f32_matches_reference_golden(vocoders, name):
         assert err.max() <= 1e-5 and err.mean() <= 1e-6, (n, err.max(), err.mean())
 
 
-@pytest.mark.parametrize('name', vt.NAMES)
+@pytest.mark.parametrize('name', vh.VARIANTS)
 def test_bf16_against_f32_snr_is_at_the_all_bfloat16_reference(vocoders, name):
     """Only the MFMA operands are rounded here (activations, residuals and sums stay fp32), so the SNR against the f32 mode is no lower
     than that of the reference run wholly in bfloat16 against its fp64 run (the fixture's figure), less 1 dB for the summation order."""
-    gold = vt.golden(name)
+    gold = vh.variant_golden(name)
     for n, mel, floor in zip(gold['lengths'], gold['mels'], gold['bf16_snr_db']):
         a = vocoders[name, 'f32'].infer(mel).astype(np.float64)
         b = vocoders[name, 'bf16'].infer(mel).astype(np.float64)
@@ -72,7 +72,7 @@ def test_bf16_against_f32_snr_is_at_the_all_bfloat16_reference(vocoders, name):
 
 
 @pytest.mark.parametrize('precision', ['f32', 'bf16'])
-@pytest.mark.parametrize('name', vt.NAMES)
+@pytest.mark.parametrize('name', vh.VARIANTS)
 def test_batch_rows_equal_utterances_alone_bitwise(vocoders, batch, whole, name, precision):
     v, mels, audio = vocoders[name, precision], batch[name], whole[name, precision]
     assert audio.shape == (len(BATCH), 256 * max(BATCH))
@@ -93,7 +93,7 @@ def _collect(stream):
 
 @pytest.mark.parametrize('chunk_frames', [4, 32])
 @pytest.mark.parametrize('precision', ['f32', 'bf16'])
-@pytest.mark.parametrize('name', vt.NAMES)
+@pytest.mark.parametrize('name', vh.VARIANTS)
 def test_streamed_equals_whole_bitwise(vocoders, batch, whole, name, precision, chunk_frames):
     v, mels, ref = vocoders[name, precision], batch[name], whole[name, precision]
     sizes = set()

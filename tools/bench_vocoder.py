@@ -10,7 +10,7 @@ torch rows compute the whole padded (B, 80, T_max) grid ('frames_computed'), the
 --profile: + per-kernel times of one bf16 and one f32 HIP call; --hip-only: without the torch rows (whose first calls spend minutes in
 MIOpen's search over the 16 utterance lengths).
 
---config v2 / v3: the same batch through the V2 / V3 generator (tests/vocoder_variants_torch.py as the torch rows), FLOP per frame
+--config v2 / v3: the same batch through the V2 / V3 generator (the same torch rows), FLOP per frame
 counted from the configuration's own (unpadded) layer shapes; the default, v1, prints what it always printed.
 """
 import json
@@ -24,7 +24,6 @@ import torch  # noqa: E402
 
 from tests import vocoder_helpers as vh  # noqa: E402
 from tests import vocoder_torch  # noqa: E402
-from tests import vocoder_variants_torch as vt  # noqa: E402
 from ubisoft_laforge_daft_exprt_amd import profiling, vocoder as voc  # noqa: E402
 from ubisoft_laforge_daft_exprt_amd import _lib  # noqa: E402
 
@@ -71,7 +70,7 @@ def main():
     if name not in voc.CONFIGS:
         raise SystemExit(f'--config takes one of {sorted(voc.CONFIGS)}, got {name!r}')
     cfg = voc.CONFIGS[name]()
-    torch_generator = vocoder_torch.generator if name == 'v1' else (lambda m, w: vt.generator(m, w, cfg))
+    torch_generator = lambda m, w: vocoder_torch.generator(m, w, cfg)
     if name != 'v1':
         MFLOP_PER_FRAME = mflop_per_frame(cfg)
     g = torch.Generator().manual_seed(3)
@@ -82,7 +81,7 @@ def main():
     for b, n in enumerate(lengths.tolist()):
         mels[b, :, n:] = 0
     lens_dev = lengths.to(dev)
-    sd = vh.state_dict() if name == 'v1' else vt.state_dict(name)
+    sd = vh.state_dict(name)
     out = {'workload': f'B={B} utterances, {frames} mel frames (max {T_MAX})', 'mflop_per_frame': MFLOP_PER_FRAME}
     if name != 'v1':
         out['config'] = name

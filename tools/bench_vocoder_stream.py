@@ -25,7 +25,6 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 from tests import vocoder_helpers as vh  # noqa: E402
-from tests import vocoder_variants_torch as vt  # noqa: E402
 from tools.bench_vocoder import B, T_MAX, timed  # noqa: E402
 from ubisoft_laforge_daft_exprt_amd import vocoder as voc  # noqa: E402
 
@@ -73,7 +72,7 @@ def main():
     mels = ((torch.randn(B, 80, T_MAX, generator=g) * 1.5 - 5.0).clamp(-11.5, 2.0)).to(dev)
     for b, n in enumerate(lengths.tolist()):
         mels[b, :, n:] = 0
-    sd = vh.state_dict() if name == 'v1' else vt.state_dict(name)
+    sd = vh.state_dict(name)
     ms = lambda t: None if t is None else round(t * 1e3, 3)
     out = {'workload': f'B = {B}: {int(lengths.sum())} mel frames (max {T_MAX}); B = 1: its first row, {T_MAX} frames'}
     if name != 'v1':

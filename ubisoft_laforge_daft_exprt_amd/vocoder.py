@@ -12,6 +12,8 @@ csrc/dx_vocoder.hip; there is no PyTorch fallback.  Checkpoints are read from a 
 """
 from __future__ import annotations
 
+import functools
+import json
 import os
 
 import numpy as np
@@ -90,12 +92,7 @@ def stage_widths(config=None, padded=True) -> list:
 def workspace_bytes_per_frame(config=None) -> int:
     """Bytes of ``infer_batch``'s activation workspace per mel frame of the longest row: five fp32 buffers of the widest tensor (padded
     channels x samples per frame).  V1: WORKSPACE_BYTES_PER_FRAME."""
-    cfg = check_config(config)
-    widest, scale = int(cfg['upsample_initial_channel']), 1
-    for u, c in zip(cfg['upsample_rates'], stage_widths(cfg)):
-        scale *= int(u)
-        widest = max(widest, c * scale)
-    return 5 * widest * 4
+    return 5 * 4 * max(t['channels'] * t['scale'] for t in generator_launches(config).tensors.values())
 
 
 def pad_folded_weights(weights: dict, config=None) -> dict:
@@ -131,12 +128,108 @@ def pad_folded_weights(weights: dict, config=None) -> dict:
     return out
 
 
+# ---- the generator's launches (host only) ----------------------------------------------------------------------------------------
+class GeneratorLaunches:
+    """What ``generator_launches`` returns, shared between its callers (copy before writing).  ``tensors``: {name: {'scale' samples per
+    mel frame, 'channels', 'slot'}} for every tensor between two layers; ``launches``, ``len()`` of them: in order, each a dict (kind
+    'conv' / 'pair' / 'chain' / 'post', layer names, the names of its tensors 'x', 'y', 'r', the shape, 'scale' = tile rows per frame,
+    and its 'left' / 'right' reach in rows of x)."""
+
+    def __init__(self, tensors, launches):
+        self.tensors, self.launches = tensors, launches
+
+    def __len__(self):
+        return len(self.launches)
+
+
+def generator_launches(config=None, precision='f32') -> GeneratorLaunches:
+    """The generator as the launches that compute it, built once per (configuration, precision): what ``infer_batch`` issues on whole
+    tensors and ``stream_plan`` schedules on rings.  A ResBlock runs one of three ways: a ResBlock2 of a shape that is faster fused as
+    one 'chain'; a ResBlock1 pair at 64 channels or fewer as one 'pair'; anything else as a 'conv' per convolution, a ResBlock1's
+    through a 'mid' tensor.
+    'slot': which fifth of ``infer_batch``'s workspace holds the tensor -- 0: conv_pre and the stage sums, 1: a stage's transposed conv,
+    2 and 3: a ResBlock's x0 and x1, 4: mid.  Two tensors share a slot only when the first is dead before the second is written, and no
+    launch reads and writes one slot (tests/test_vocoder_launches_cpu.py walks the launches to check both)."""
+    if precision not in PRECISIONS:
+        raise ValueError(f'generator_launches: precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
+    return _generator_launches(json.dumps(check_config(config), sort_keys=True), precision)       # lists and tuples dump alike
+
+
+@functools.lru_cache(maxsize=None)
+def _generator_launches(config_json, precision):
+    cfg = json.loads(config_json)
+    c = cfg['upsample_initial_channel']
+    T, L = {}, []
+
+    def tensor(name, scale, channels, slot):
+        T[name] = dict(scale=scale, channels=channels, slot=slot)
+        return name
+
+    def launch(layer, x, y, cin, cout, taps, dil, up, lrelu, acc, scale, reach, r=None, kind='conv', **second):
+        L.append(dict(kind=kind, layer=layer, x=x, y=y, r=r, cin=cin, cout=cout, taps=taps, dil=dil, up=up, lrelu=lrelu, acc=acc,
+                      scale=scale, left=reach, right=reach, **second))
+
+    x, scale = tensor('conv_pre', 1, c, 0), 1
+    launch('conv_pre', 'mel', x, cfg['model_in_dim'], c, 7, 1, 1, 0, 0, 1, 3)
+    ks, ds = cfg['resblock_kernel_sizes'], cfg['resblock_dilation_sizes']
+    resblock2 = str(cfg['resblock']) == '2'
+    for i, (u, cs) in enumerate(zip(cfg['upsample_rates'], stage_widths(cfg))):     # cs: the stage's channels as they run (padded)
+        up_out = tensor(f'ups.{i}', scale * u, cs, 1)
+        launch(f'ups.{i}', x, up_out, c, cs, 2, 1, u, 1, 0, scale, 1)
+        scale, c = scale * u, cs
+        total = tensor(f'sum.{i}', scale, c, 0)
+        for j, k in enumerate(ks):
+            name, src, h = f'resblocks.{i * len(ks) + j}', up_out, (k - 1) // 2
+            last = len(ds[j]) - 1
+            if resblock2 and last == 1 and (precision, c, k) in CHAIN_SHAPES:    # both dilations of the ResBlock2 in one launch
+                launch(f'{name}.convs.0', src, total, c, c, k, ds[j][0], 1, 1, min(j, 2), scale, (ds[j][0] + ds[j][1]) * h, kind='chain',
+                     layer2=f'{name}.convs.1', dil2=ds[j][1])
+                continue
+            for p, d in enumerate(ds[j]):
+                dst = total if p == last else tensor(f'{name}.x{p}', scale, c, 2 + p)
+                acc = min(j, 2) if p == last else 0           # the stage sum: first ResBlock writes, second adds, third adds and / 3
+                if resblock2:                                                 # x <- conv_d(lrelu x) + x
+                    launch(f'{name}.convs.{p}', src, dst, c, c, k, d, 1, 1, acc, scale, d * h, r=src)
+                elif c <= 64:
+                    launch(f'{name}.convs1.{p}', src, dst, c, c, k, d, 1, 1, acc, scale, d * h + h, kind='pair', layer2=f'{name}.convs2.{p}')
+                else:
+                    mid = tensor(f'{name}.mid{p}', scale, c, 4)
+                    launch(f'{name}.convs1.{p}', src, mid, c, c, k, d, 1, 1, 0, scale, d * h)
+                    launch(f'{name}.convs2.{p}', mid, dst, c, c, k, 1, 1, 1, acc, scale, h, r=src)
+                src = dst
+        x = total
+    launch('conv_post', x, 'audio', c, 1, 7, 1, 1, 1, 0, scale, 3, kind='post')
+    return GeneratorLaunches(T, L)
+
+
+def _issue(L, ln, packs, x, y, r, frames, B, N, bf16, window, st):
+    """One launch of ``generator_launches`` as its call into the library.  ``x``, ``y``, ``r`` (None without a residual): where the
+    launch's tensors are, each as (pointer, batch stride, row stride, channel stride, ring mask -- 0: not a ring); ``N``: the rows of
+    x; ``window``: None for the whole tensors, or (cursor, step, lag) for the windowed entry point of the same name."""
+    (X, sxb, sxn, sxc, mx), (Y, syb, _, _, my) = x, y
+    kind, whole, masks = ln['kind'], window is None, (mx, my)
+    w, b = packs[ln['layer']]
+    if kind == 'conv':
+        R, srb, _, _, mr = (None, ln['cout'], 0, 0, 0) if r is None else r
+        args = (X, sxb, sxn, sxc, w.data_ptr(), b.data_ptr(), Y, syb, R) + (() if whole else (srb,)) + (
+            frames, ln['scale'], B, N, ln['cin'], ln['cout'], ln['taps'], ln['dil'], ln['up'], ln['lrelu'], ln['acc'], bf16)
+        masks = (mx, my, mr)
+    elif kind == 'post':                                  # y: the audio, its batch stride the row's samples
+        args = (X, sxb, w.data_ptr(), b.data_ptr(), Y, syb, frames, ln['scale'], B, N, syb, ln['cin'])
+    else:                                                 # 'pair' and 'chain': two layers, the second dilation the chain's alone
+        w2, b2 = packs[ln['layer2']]
+        args = (X, sxb, w.data_ptr(), b.data_ptr(), w2.data_ptr(), b2.data_ptr(), Y) + (() if whole else (syb,)) + (
+            frames, ln['scale'], B, N, ln['cin'], ln['taps'], ln['dil']) + ((ln['dil2'],) if kind == 'chain' else ()) + (ln['acc'], bf16)
+    entry = 'dx_voc_post_c' if kind == 'post' else 'dx_voc_' + kind
+    tail = () if whole else (*window, *masks)
+    getattr(L, entry + ('_win' if tail else ''))(*args, *tail, st)
+
+
 # ---- the streaming plan (host only) ----------------------------------------------------------------------------------------------
 class StreamPlan:
-    """What ``stream_plan`` returns.  ``tensors``: {name: {'scale' samples per mel frame, 'channels', 'lag', 'left', 'ring'}} for every
-    tensor between two layers; ``launches``: the chunk's launches in order, each a dict (kind 'conv' / 'pair' / 'chain' / 'post', layer names, the
-    names of its tensors 'x', 'y', 'r', the shape, 'scale' = tile rows per frame, 'step' = chunk_frames * scale, 'lag', and its 'left' /
-    'right' reach in rows of x); ``lookahead``: mel frames past a chunk's own that the chunk reads."""
+    """What ``stream_plan`` returns.  ``tensors``: ``generator_launches``' with 'lag', 'left' and 'ring' added; ``launches``: the chunk's
+    launches in order, ``generator_launches``' with 'step' = chunk_frames * scale and 'lag' added; ``lookahead``: mel frames past a
+    chunk's own that the chunk reads."""
 
     def __init__(self, chunk_frames, tensors, launches, lookahead):
         self.chunk_frames, self.tensors, self.launches, self.lookahead = chunk_frames, tensors, launches, lookahead
@@ -146,7 +239,8 @@ class StreamPlan:
 
 
 def stream_plan(config=None, chunk_frames=32, precision='f32') -> StreamPlan:
-    """The schedule of the chunked generator (``precision``: V3 fuses some ResBlock2 under bf16 only, CHAIN_SHAPES).  After chunk c, rows [0, min(len, (c + 1) F scale + lag)) of a tensor exist; chunk c
+    """The schedule of the chunked generator: ``generator_launches(config, precision)`` with a lag for every tensor and launch and a ring
+    for every tensor.  After chunk c, rows [0, min(len, (c + 1) F scale + lag)) of a tensor exist; chunk c
     computes rows [c F scale + lag (0 for c = 0), (c + 1) F scale + lag) of it, F = chunk_frames.
 
     Lags come from walking the generator backwards from conv_post's output (lag 0): a tensor's lag is the largest, over the launches that
@@ -156,56 +250,12 @@ def stream_plan(config=None, chunk_frames=32, precision='f32') -> StreamPlan:
     residual and an accumulated output are read at the launch's own rows.  Row n of a tensor lives at slot n & (ring - 1); the ring is
     the power of two that holds the chunk-0 window (F scale + lag) and, for every reader, F scale + (lag - reader's lag) + the reader's
     left reach: what is resident between the oldest row a reader of chunk c still needs and the newest row chunk c has written."""
-    cfg = check_config(config)
-    if precision not in PRECISIONS:
-        raise ValueError(f'stream_plan: precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
     F = int(chunk_frames)
     if F < 1:
         raise ValueError(f'stream_plan: chunk_frames must be >= 1, got {chunk_frames}')
-    c = cfg['upsample_initial_channel']
-    T, L = {}, []
-
-    def tensor(name, scale, channels):
-        T[name] = dict(scale=scale, channels=channels, lag=0, left=0, ring=0)
-        return name
-
-    def conv(layer, x, y, cin, cout, taps, dil, up, lrelu, acc, scale, reach, r=None):
-        L.append(dict(kind='conv', layer=layer, x=x, y=y, r=r, cin=cin, cout=cout, taps=taps, dil=dil, up=up, lrelu=lrelu, acc=acc,
-                      scale=scale, left=reach, right=reach))
-
-    x, scale = tensor('conv_pre', 1, c), 1
-    conv('conv_pre', 'mel', x, cfg['model_in_dim'], c, 7, 1, 1, 0, 0, 1, 3)
-    ks, ds = cfg['resblock_kernel_sizes'], cfg['resblock_dilation_sizes']
-    resblock2 = str(cfg['resblock']) == '2'
-    for i, (u, cs) in enumerate(zip(cfg['upsample_rates'], stage_widths(cfg))):     # cs: the stage's channels as they run (padded)
-        up_out = tensor(f'ups.{i}', scale * u, cs)
-        conv(f'ups.{i}', x, up_out, c, cs, 2, 1, u, 1, 0, scale, 1)
-        scale, c = scale * u, cs
-        total = tensor(f'sum.{i}', scale, c)
-        for j, k in enumerate(ks):
-            name, src, h = f'resblocks.{i * len(ks) + j}', up_out, (k - 1) // 2
-            last = len(ds[j]) - 1
-            if resblock2 and last == 1 and (precision, c, k) in CHAIN_SHAPES:    # both dilations of the ResBlock2 in one launch
-                reach = (ds[j][0] + ds[j][1]) * h
-                L.append(dict(kind='chain', layer=f'{name}.convs.0', layer2=f'{name}.convs.1', x=src, y=total, r=None, cin=c, cout=c,
-                              taps=k, dil=ds[j][0], dil2=ds[j][1], up=1, lrelu=1, acc=min(j, 2), scale=scale, left=reach, right=reach))
-                continue
-            for p, d in enumerate(ds[j]):
-                dst = total if p == last else tensor(f'{name}.x{p}', scale, c)
-                acc = min(j, 2) if p == last else 0
-                if resblock2:                                                 # x <- conv_d(lrelu x) + x
-                    conv(f'{name}.convs.{p}', src, dst, c, c, k, d, 1, 1, acc, scale, d * h, r=src)
-                elif c <= 64:
-                    L.append(dict(kind='pair', layer=f'{name}.convs1.{p}', layer2=f'{name}.convs2.{p}', x=src, y=dst, r=None, cin=c, cout=c,
-                                  taps=k, dil=d, up=1, lrelu=1, acc=acc, scale=scale, left=d * h + h, right=d * h + h))
-                else:
-                    mid = tensor(f'{name}.mid{p}', scale, c)
-                    conv(f'{name}.convs1.{p}', src, mid, c, c, k, d, 1, 1, 0, scale, d * h)
-                    conv(f'{name}.convs2.{p}', mid, dst, c, c, k, 1, 1, 1, acc, scale, h, r=src)
-                src = dst
-        x = total
-    L.append(dict(kind='post', layer='conv_post', x=x, y='audio', r=None, cin=c, cout=1, taps=7, dil=1, up=1, lrelu=1, acc=0, scale=scale,
-                  left=3, right=3))
+    generator = generator_launches(config, precision)
+    T = {name: dict(t, lag=0, left=0, ring=0) for name, t in generator.tensors.items()}
+    L = [dict(ln) for ln in generator.launches]              # copies: the pass below writes 'lag' and 'step' into them
     lookahead = 0
     for ln in reversed(L):                                  # every reader of a tensor comes after its writer: lags settle backwards
         up = ln['up']
@@ -347,6 +397,7 @@ class HiFiGanVocoder:
         self.config = generator.config
         self.checkpoint_path = checkpoint_path
         self.precision = precision
+        self.topology = generator_launches(self.config, precision)     # what infer_batch issues; stream_plan schedules the same list
         self.device = torch.device(device)
         state = _checkpoint_state(checkpoint_path)
         layers = generator.layer_names()
@@ -434,7 +485,8 @@ class HiFiGanVocoder:
         chunk_frames)) steps, each yielding (audio (B, 256 chunk_frames) fp32 on the device, valid (B,) int64 on the device).  Step c
         holds samples [256 c chunk_frames, 256 (c + 1) chunk_frames) of every row, bit for bit what ``infer_batch`` writes there;
         ``valid`` counts those that belong to the row (0 once the row has ended; the rest of its chunk is 0).  Every step runs the same
-        launches (the generator's -- 60 for V1 -- and the cursor's advance) on ring buffers whose size depends on chunk_frames and B alone (``stream.workspace_bytes``); with ``use_graph``
+        launches (the ``len(generator_launches(config, precision))`` of the generator and the cursor's advance) on ring buffers whose
+        size depends on chunk_frames and B alone (``stream.workspace_bytes``); with ``use_graph``
         they are captured once, while the second chunk is due, and replayed from then on.  ``clone=False`` yields the stream's own
         buffer, overwritten by the next step.  The mel is read in place until the last step: leave it unchanged meanwhile."""
         return VocoderStream(self, mels, lengths, chunk_frames, use_graph, clone)
@@ -467,56 +519,17 @@ class HiFiGanVocoder:
         return audio, sample_lengths
 
     def _run(self, P, mels, frames, audio, b0, b1, N):
-        """Utterances b0 .. b1-1 with N frames of work each (N >= their lengths): 60 launches for V1, 42 for V2, 23 for V3 (19 with bf16 operands)."""
+        """Utterances b0 .. b1-1 with N frames of work each (N >= their lengths): the ``len(generator_launches(config, precision))``
+        launches, every tensor whole ((B, N scale, channels), channels last) in its slot of a workspace of five."""
         L, st = lib(), _stream(mels.device)
-        bf16 = PRECISIONS[self.precision]
-        B, T = b1 - b0, mels.shape[2]
-        n_mel = mels.shape[1]
+        B, n_mel, T = b1 - b0, mels.shape[1], mels.shape[2]
         ws = torch.empty(5, B * N * (workspace_bytes_per_frame(self.config) // 20), dtype=torch.float32, device=mels.device)
-        S, U, Pb, Q, M = (ws[i].data_ptr() for i in range(5))
-        fr = frames.data_ptr() + 4 * b0
-        c = self.config['upsample_initial_channel']
-        w, b = P['conv_pre']
-        L.dx_voc_conv(mels.data_ptr() + 4 * b0 * n_mel * T, n_mel * T, 1, T, w.data_ptr(), b.data_ptr(), S, N * c, None,
-                      fr, 1, B, N, n_mel, c, 7, 1, 1, 0, 0, bf16, st)
-        rows, scale = N, 1
-        ks, ds = self.config['resblock_kernel_sizes'], self.config['resblock_dilation_sizes']
-        resblock2 = str(self.config['resblock']) == '2'
-        for i, (u, cs) in enumerate(zip(self.config['upsample_rates'], stage_widths(self.config))):
-            w, b = P[f'ups.{i}']
-            L.dx_voc_conv(S, rows * c, c, 1, w.data_ptr(), b.data_ptr(), U, rows * u * cs, None,
-                          fr, scale, B, rows, c, cs, 2, 1, u, 1, 0, bf16, st)
-            rows, scale, c = rows * u, scale * u, cs
-            for j, k in enumerate(ks):
-                src, last = U, len(ds[j]) - 1
-                name = f'resblocks.{i * len(ks) + j}'
-                if resblock2 and last == 1 and (self.precision, c, k) in CHAIN_SHAPES:
-                    (w1, b1), (w2, b2) = P[f'{name}.convs.0'], P[f'{name}.convs.1']
-                    L.dx_voc_chain(U, rows * c, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), S,
-                                   fr, scale, B, rows, c, k, ds[j][0], ds[j][1], min(j, 2), bf16, st)
-                    continue
-                for p, d in enumerate(ds[j]):
-                    dst = S if p == last else (Pb, Q)[p]
-                    acc = min(j, 2) if p == last else 0           # the stage sum: first ResBlock writes, second adds, third adds and / 3
-                    if resblock2:
-                        w1, b1 = P[f'{name}.convs.{p}']
-                        L.dx_voc_conv(src, rows * c, c, 1, w1.data_ptr(), b1.data_ptr(), dst, rows * c, src,
-                                      fr, scale, B, rows, c, c, k, d, 1, 1, acc, bf16, st)
-                        src = dst
-                        continue
-                    (w1, b1), (w2, b2) = P[f'{name}.convs1.{p}'], P[f'{name}.convs2.{p}']
-                    if c <= 64:
-                        L.dx_voc_pair(src, rows * c, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), dst,
-                                      fr, scale, B, rows, c, k, d, acc, bf16, st)
-                    else:
-                        L.dx_voc_conv(src, rows * c, c, 1, w1.data_ptr(), b1.data_ptr(), M, rows * c, None,
-                                      fr, scale, B, rows, c, c, k, d, 1, 1, 0, bf16, st)
-                        L.dx_voc_conv(M, rows * c, c, 1, w2.data_ptr(), b2.data_ptr(), dst, rows * c, src,
-                                      fr, scale, B, rows, c, c, k, 1, 1, 1, acc, bf16, st)
-                    src = dst
-        w, b = P['conv_post']
-        L.dx_voc_post_c(S, rows * c, w.data_ptr(), b.data_ptr(), audio.data_ptr() + 4 * b0 * T * HOP, T * HOP,
-                        fr, scale, B, rows, T * HOP, c, st)
+        slots = [ws[i].data_ptr() for i in range(5)]
+        at = {'mel': (mels.data_ptr() + 4 * b0 * n_mel * T, n_mel * T, 1, T, 0), 'audio': (audio.data_ptr() + 4 * b0 * T * HOP, T * HOP, 0, 0, 0), None: None}
+        at.update((name, (slots[t['slot']], N * t['scale'] * t['channels'], t['channels'], 1, 0)) for name, t in self.topology.tensors.items())
+        fr, bf16 = frames.data_ptr() + 4 * b0, PRECISIONS[self.precision]
+        for ln in self.topology.launches:
+            _issue(L, ln, P, at[ln['x']], at[ln['y']], at[ln['r']], fr, B, N * ln['scale'], bf16, None, st)
 
 
 class VocoderStream:
@@ -542,6 +555,10 @@ class VocoderStream:
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.audio = torch.zeros(B, self.chunk_samples, dtype=torch.float32, device=dev)
         self.workspace_bytes = self.plan.ring_bytes(B) + self.audio.numel() * 4 + 4
+        n_mel, T = self.mels.shape[1:]
+        # where _issue finds every tensor: the mel in place, the chunk buffer, its ring (row n at slot n & (ring - 1))
+        self.at = {'mel': (self.mels.data_ptr(), n_mel * T, 1, T, 0), 'audio': (self.audio.data_ptr(), self.chunk_samples, 0, 0, 0), None: None}
+        self.at.update((name, (self.rings[name].data_ptr(), t['ring'] * t['channels'], t['channels'], 1, t['ring'] - 1)) for name, t in self.plan.tensors.items())
         start = torch.arange(self.n_chunks, device=dev)[:, None] * self.chunk_samples
         self.valid = (self.frames.to(torch.long)[None, :] * HOP - start).clamp(0, self.chunk_samples)       # (chunks, B)
         self.graph, self.captures, self.done = None, 0, 0
@@ -555,37 +572,10 @@ class VocoderStream:
     def _launch(self):
         """The launches of one chunk, the same for every chunk: the window comes from the device cursor, which the last one advances."""
         L, st = lib(), _stream(self.mels.device)
-        B, n_mel, T = self.mels.shape
-        fr, cur = self.frames.data_ptr(), self.cursor.data_ptr()
-        ring = lambda name: (self.rings[name].data_ptr(), self.plan.tensors[name]['ring'])
+        B, T = self.mels.shape[0], self.mels.shape[2]
+        fr, cur, at = self.frames.data_ptr(), self.cursor.data_ptr(), self.at
         for ln in self.plan.launches:
-            w, b = self.packs[ln['layer']]
-            N, cin, cout = T * ln['scale'], ln['cin'], ln['cout']
-            if ln['kind'] == 'post':
-                X, nx = ring(ln['x'])
-                L.dx_voc_post_c_win(X, nx * cin, w.data_ptr(), b.data_ptr(), self.audio.data_ptr(), self.chunk_samples, fr, ln['scale'], B,
-                                    N, self.chunk_samples, cin, cur, ln['step'], ln['lag'], nx - 1, 0, st)
-                continue
-            Y, ny = ring(ln['y'])
-            if ln['x'] == 'mel':
-                X, sxb, sxn, sxc, mx = self.mels.data_ptr(), n_mel * T, 1, T, 0
-            else:
-                X, nx = ring(ln['x'])
-                sxb, sxn, sxc, mx = nx * cin, cin, 1, nx - 1
-            if ln['kind'] == 'pair':
-                w2, b2 = self.packs[ln['layer2']]
-                L.dx_voc_pair_win(X, sxb, w.data_ptr(), b.data_ptr(), w2.data_ptr(), b2.data_ptr(), Y, ny * cout, fr, ln['scale'], B, N, cin,
-                                  ln['taps'], ln['dil'], ln['acc'], self.bf16, cur, ln['step'], ln['lag'], mx, ny - 1, st)
-                continue
-            if ln['kind'] == 'chain':
-                w2, b2 = self.packs[ln['layer2']]
-                L.dx_voc_chain_win(X, sxb, w.data_ptr(), b.data_ptr(), w2.data_ptr(), b2.data_ptr(), Y, ny * cout, fr, ln['scale'], B, N, cin,
-                                   ln['taps'], ln['dil'], ln['dil2'], ln['acc'], self.bf16, cur, ln['step'], ln['lag'], mx, ny - 1, st)
-                continue
-            R, nr = ring(ln['r']) if ln['r'] is not None else (None, 1)
-            L.dx_voc_conv_win(X, sxb, sxn, sxc, w.data_ptr(), b.data_ptr(), Y, ny * cout, R, nr * cout, fr, ln['scale'], B, N, cin, cout,
-                              ln['taps'], ln['dil'], ln['up'], ln['lrelu'], ln['acc'], self.bf16, cur, ln['step'], ln['lag'], mx, ny - 1,
-                              nr - 1, st)
+            _issue(L, ln, self.packs, at[ln['x']], at[ln['y']], at[ln['r']], fr, B, T * ln['scale'], self.bf16, (cur, ln['step'], ln['lag']), st)
         if self.tail is not None:
             self.tail(self.audio)
         L.dx_voc_stream_advance(cur, st)
