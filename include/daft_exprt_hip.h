@@ -293,7 +293,17 @@ int dx_loss_finalize_dyn(const float* ce, const float* spk_w_dev, float spk_w, c
  * masks: (B, T, 3, 8) uint32 written by fwd (ReLU sign bits: the network is frozen, so the backward needs no activations), read by bwd.
  * Only tokens n < lens[b] are produced (the loss and the model mask the rest).  Every entry point with 16-bit packs also exists as <name>_f16.
  * rows_exist (optional, device int32 [B], as in dx_conv_gemm): frames n >= rows_exist[b] are the convolutions' zero padding although T frames
- * are stored (fwd ignores the mel there, bwd ignores dpp / masks there); NULL: all T frames exist. */
+ * are stored (fwd ignores the mel there, bwd ignores dpp / masks there); NULL: all T frames exist.
+ * What callers (and tests/test_pitch_exact_gpu.py) may rely on, with E = min(rows_exist[b], T) and len = min(lens[b], T) <= E:
+ *   - the mel of every frame n < E is a convolution input, the frames at and past len included (only pp and dmel stop at len);
+ *   - fwd writes pp[b][n] for n < len and nothing else of pp; bwd adds to dmel[b][:][n] for n < len and touches nothing else of dmel;
+ *   - dpp[b][n] must be zero for n >= len (dx_pitch_grad writes it so): bwd reads dpp up to the end of the last tile's window and does not
+ *     mask it by len, and the mask frames it needs past len are exactly those that a zero there leaves;
+ *   - mask words: bit c % 32 of word c / 32 of (b, n, l) is "pre-activation of channel c of layer l at frame n > 0" (strictly).  For len > 0, fwd
+ *     writes the words of layer l on every frame n < min(len + 3 - l, T) at least (to the end of the last tile's window; zeros at n >= E),
+ *     and bwd's result depends on them for n <= len + 2 - l, n < E only: one frame further out per layer below the last, because the
+ *     gradient at frame len - 1 comes through frame len of layer 2, len + 1 of layer 1 and len + 2 of layer 0.  Words of other frames may
+ *     hold anything.  An utterance with lens[b] <= 0 runs no tile: nothing of it is read or written. */
 int dx_pitch_chain_fwd(const float* mel, int B, int M, int T, const int* lens, const void* w0, const void* w1, const void* w2,
                        const float* b0, const float* b1, const float* b2, const float* s0, const float* s1, const float* s2,
                        const float* t0, const float* t1, const float* t2, const float* w3, float b3, float* pp, void* masks,
