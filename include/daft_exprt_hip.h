@@ -409,6 +409,32 @@ int dx_voc_post_c_win(const float* X, long sxb, const float* W, const float* bia
 /* *cursor += 1 by one thread: the last launch of a chunk, so that replaying the same launches computes the next window. */
 int dx_voc_stream_advance(int* cursor, void* stream);
 
+/* ---- HiFi-GAN generator training, f32 operands (csrc/dx_vocoder_bwd.hip) -----------------------------------------------------------
+ * The data gradients of the generator are dx_voc_conv launches on packs built by the host (vocoder_train.py); these are the rest of the
+ * backward.  frames / scale as above: rows at or past min(frames[b] scale, N) read as zero and are written as zero.  No atomics: partial
+ * sums go to the caller's workspace and are added in a fixed order, so two calls give the same bits. */
+/* bytes of the workspace dx_voc_wgrad needs for this shape (up > 1: a transposed conv, taps = 3) */
+int dx_voc_wgrad_size(int B, int N, int Cin, int Cout, int taps, int up, long* bytes);
+/* Weight and bias gradient of one convolution (v_mfma_f32_16x16x4_f32, the position as the MFMA k):
+ *   up == 1: G (Cout, Cin, taps), G[co][ci][t] = sum_b sum_n act(X[b][n - dil (taps - 1) / 2 + t dil][ci]) dY[b][n][co]
+ *   up > 1 (even, taps = 3, dil = 1): G (Cin, Cout, 2 up) of ConvTranspose1d(stride up, padding up / 2) with N INPUT rows, from the
+ *            view of its output gradient (N up, Cout) as (N, up Cout): G[ci][co][d up + r + up / 2] = sum act(X[b][m][ci]) dY[b][m + d][r Cout + co]
+ *   dbias (optional) [Cout] = sum of dY over rows (and phases).
+ * X element (b, n, c) at X[b sxb + n sxn + c sxc] (conv_pre reads the (B, 80, T) mel in place); dY element (b, n, c) at
+ * dY[b dyb + n ldy + dyc + c], ldy >= dyc + up Cout.  act 0: identity, 1: leaky-ReLU(0.1).  Cin, Cout multiples of 16 up to 512. */
+int dx_voc_wgrad(const float* X, long sxb, long sxn, long sxc, const float* dY, long dyb, int ldy, int dyc, float* G, float* dbias,
+                 float* workspace, long workspace_bytes, const int* frames, int scale, int B, int N, int Cin, int Cout, int taps, int dil,
+                 int up, int act, void* stream);
+/* dX = (acc ? dX : 0) + (R ? R : 0) + gscale lrelu'(Xs) U, the product and the sum one fma; (B, N, C) channels-last tensors, contiguous;
+ * Xs NULL: slope 1; R may equal dX.  lrelu'(x) = 1 for x > 0, else 0.1. */
+int dx_voc_act_bwd(const float* Xs, const float* U, const float* R, float* dX, const int* frames, int scale, int B, int N, int C,
+                   float gscale, int acc, void* stream);
+int dx_voc_post_bwd_size(int B, int N, int C, long* bytes);
+/* conv_post backward from its saved output Y = clip(tanh z) and the upstream dY (both (B, ldy)): dz = dY (1 - Y^2), 0 past the length;
+ * dX[b][n][c] = lrelu'(X) sum_t dz[n + 3 - t] W[c][t]; dW (1, C, 7) and db (1) by the fixed-order two-stage sum.  C in {16, 32}. */
+int dx_voc_post_bwd(const float* X, long sxb, const float* W, const float* Y, const float* dY, int ldy, float* dX, float* dW, float* db,
+                    float* workspace, long workspace_bytes, const int* frames, int scale, int B, int N, int C, void* stream);
+
 /* ---- mel front end (reference extract_features.py mel_spectrogram_HiFi, vocoder/dataset.py mel_spectrogram, center = False;
  * csrc/dx_mel.hip) ------------------------------------------------------------------------------------------------------------
  * n_fft = win = 1024, hop = 256, reflect padding of 384 samples per side with each row's own first / last samples.  kmax: the bins

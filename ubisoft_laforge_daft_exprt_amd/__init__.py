@@ -11,6 +11,7 @@ from .functional import manual_seed  # noqa: F401
 from .ops import set_precision, get_precision, Runtime  # noqa: F401
 from .vocoder import HiFiGANGenerator, HiFiGanVocoder, VocoderStream, load_hifigan_vocoder, stream_plan  # noqa: F401
 from .vocoder import v1_config, v2_config, v3_config, workspace_bytes_per_frame  # noqa: F401
+from .vocoder_train import backward_launches  # noqa: F401
 from .mel import MelSpectrogram, mel_filter_bank, mel_spectrogram, mel_spectrogram_HiFi  # noqa: F401
 from .griffin_lim import GriffinLim, GriffinLimVocoder, griffin_lim_reconstruction_from_mel_spec  # noqa: F401
 from .speech import SpeechSynthesizer, condition_external_prosody, symbol_prosody, to_pcm16  # noqa: F401

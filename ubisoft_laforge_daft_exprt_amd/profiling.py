@@ -196,6 +196,16 @@ def price(name, a, geom: Geometry):
         if name == 'dx_voc_chain':                       # a ResBlock2: two convs (the halo's recomputation is not credited), X read, Y written
             return f'voc_chain<{op}>', 'mfma', 2.0 * 2 * a['taps'] * a['C'] * a['C'] * rows, rows * a['C'] * 4 * (2 + (a['acc_mode'] > 0))
         return 'voc_post', 'hbm', None, rows * (a['C'] if name == 'dx_voc_post_c' else 32) * 4 + a['B'] * a['ncols'] * 4
+    if name == 'dx_voc_wgrad':                           # generator training: both operands read once per tap, N rows, frames * scale valid
+        s = max(1, a['scale'])
+        rows = geom.rows(a['B'], a['N'] // s) * s
+        k = 2 * a['up'] if a['up'] > 1 else a['taps']
+        byt = rows * k * (a['Cin'] + a['Cout']) * 4 + a['Cout'] * a['Cin'] * k * 4
+        return 'voc_wgrad<f32>', 'mfma', 2.0 * k * a['Cin'] * a['Cout'] * rows, byt
+    if name == 'dx_voc_act_bwd':                         # U read, dX written, Xs / R / dX read when present
+        return 'voc_act_bwd', 'hbm', None, a['B'] * a['N'] * a['C'] * 4 * (2 + has('Xs') + has('R') + (a['acc'] > 0))
+    if name == 'dx_voc_post_bwd':                        # X read, dX written, Y and dY read
+        return 'voc_post_bwd', 'hbm', None, a['B'] * a['N'] * (2 * a['C'] + 2) * 4
     if name == 'dx_voc_pack':
         return 'voc_pack', 'hbm', None, a['Cout'] * a['Cin'] * a['taps'] * max(1, a['up']) * (4 + (2 if a['bf16'] else 4))
     if name == 'dx_disc_conv':                           # HiFi-GAN discriminators: rows of N positions, no lengths

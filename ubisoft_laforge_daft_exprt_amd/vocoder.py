@@ -142,27 +142,32 @@ class GeneratorLaunches:
         return len(self.launches)
 
 
-def generator_launches(config=None, precision='f32') -> GeneratorLaunches:
+def generator_launches(config=None, precision='f32', training=False) -> GeneratorLaunches:
     """The generator as the launches that compute it, built once per (configuration, precision): what ``infer_batch`` issues on whole
     tensors and ``stream_plan`` schedules on rings.  A ResBlock runs one of three ways: a ResBlock2 of a shape that is faster fused as
     one 'chain'; a ResBlock1 pair at 64 channels or fewer as one 'pair'; anything else as a 'conv' per convolution, a ResBlock1's
     through a 'mid' tensor.
     'slot': which fifth of ``infer_batch``'s workspace holds the tensor -- 0: conv_pre and the stage sums, 1: a stage's transposed conv,
     2 and 3: a ResBlock's x0 and x1, 4: mid.  Two tensors share a slot only when the first is dead before the second is written, and no
-    launch reads and writes one slot (tests/test_vocoder_launches_cpu.py walks the launches to check both)."""
+    launch reads and writes one slot (tests/test_vocoder_launches_cpu.py walks the launches to check both).
+    ``training``: the list ``HiFiGANGenerator.forward`` runs when gradients are wanted ('f32' only): 'conv' and 'post' launches alone,
+    and every tensor in a 'slot' of its own, so that the input of every convolution -- conv_pre, each ups.i, each ResBlock's x_p and
+    mid_p, each sum.i -- is still there when ``vocoder_train.backward_launches`` reads it."""
     if precision not in PRECISIONS:
         raise ValueError(f'generator_launches: precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
-    return _generator_launches(json.dumps(check_config(config), sort_keys=True), precision)       # lists and tuples dump alike
+    if training and precision != 'f32':
+        raise ValueError(f"generator_launches: the training list exists for precision 'f32' only, got {precision!r}")
+    return _generator_launches(json.dumps(check_config(config), sort_keys=True), precision, bool(training))       # lists and tuples dump alike
 
 
 @functools.lru_cache(maxsize=None)
-def _generator_launches(config_json, precision):
+def _generator_launches(config_json, precision, training=False):
     cfg = json.loads(config_json)
     c = cfg['upsample_initial_channel']
     T, L = {}, []
 
     def tensor(name, scale, channels, slot):
-        T[name] = dict(scale=scale, channels=channels, slot=slot)
+        T[name] = dict(scale=scale, channels=channels, slot=len(T) if training else slot)
         return name
 
     def launch(layer, x, y, cin, cout, taps, dil, up, lrelu, acc, scale, reach, r=None, kind='conv', **second):
@@ -181,7 +186,7 @@ def _generator_launches(config_json, precision):
         for j, k in enumerate(ks):
             name, src, h = f'resblocks.{i * len(ks) + j}', up_out, (k - 1) // 2
             last = len(ds[j]) - 1
-            if resblock2 and last == 1 and (precision, c, k) in CHAIN_SHAPES:    # both dilations of the ResBlock2 in one launch
+            if not training and resblock2 and last == 1 and (precision, c, k) in CHAIN_SHAPES:    # both dilations of the ResBlock2 in one launch
                 launch(f'{name}.convs.0', src, total, c, c, k, ds[j][0], 1, 1, min(j, 2), scale, (ds[j][0] + ds[j][1]) * h, kind='chain',
                      layer2=f'{name}.convs.1', dil2=ds[j][1])
                 continue
@@ -190,10 +195,10 @@ def _generator_launches(config_json, precision):
                 acc = min(j, 2) if p == last else 0           # the stage sum: first ResBlock writes, second adds, third adds and / 3
                 if resblock2:                                                 # x <- conv_d(lrelu x) + x
                     launch(f'{name}.convs.{p}', src, dst, c, c, k, d, 1, 1, acc, scale, d * h, r=src)
-                elif c <= 64:
+                elif c <= 64 and not training:
                     launch(f'{name}.convs1.{p}', src, dst, c, c, k, d, 1, 1, acc, scale, d * h + h, kind='pair', layer2=f'{name}.convs2.{p}')
                 else:
-                    mid = tensor(f'{name}.mid{p}', scale, c, 4)
+                    mid = tensor(f'{name}.mid{p}', scale, c, 4)            # training keeps every mid_p: the name carries p
                     launch(f'{name}.convs1.{p}', src, mid, c, c, k, d, 1, 1, 0, scale, d * h)
                     launch(f'{name}.convs2.{p}', mid, dst, c, c, k, 1, 1, 1, acc, scale, h, r=src)
                 src = dst
@@ -305,12 +310,19 @@ class _ResBlock2(nn.Module):
 
 
 class HiFiGANGenerator(nn.Module):
-    """The reference generator's parameters (weight-normed keys and shapes).  It holds weights only: the forward is
-    ``HiFiGanVocoder``, which runs the folded weights through the HIP kernels."""
+    """The reference generator (weight-normed keys and shapes).  ``generator(x)``, x a (B, 80, T) fp32 mel on the device -> (B, 1, 256 T),
+    the reference's signature; ``lengths``: optional frame counts per row, ``infer_batch``'s semantics (samples at or past 256
+    lengths[b] are 0, and constant).  With grad mode on and a parameter that requires grad, the forward runs the training launch list
+    and ``backward()`` leaves ``.grad`` on every weight_g, weight_v and bias (vocoder_train.py: f32 operands only, once per forward, no
+    gradient to the mel); otherwise it is ``HiFiGanVocoder(state_dict).infer_batch``, bit for bit."""
 
-    def __init__(self, config=None):
+    def __init__(self, config=None, precision='f32'):
         super().__init__()
+        if precision not in PRECISIONS:
+            raise ValueError(f'HiFiGANGenerator: precision must be one of {sorted(PRECISIONS)}, got {precision!r}')
         self.config = check_config(config)
+        self.precision = precision
+        self._inference = None                                  # (parameter versions, the HiFiGanVocoder of those weights)
         c0 = self.config['upsample_initial_channel']
         self.conv_pre = _WNConv((c0, self.config['model_in_dim'], 7), c0)
         self.ups = nn.ModuleList([_WNConv((c0 >> i, c0 >> (i + 1), k), c0 >> (i + 1))
@@ -327,6 +339,10 @@ class HiFiGANGenerator(nn.Module):
     def folded(self) -> dict:
         """-> {layer: (weight, bias)} with weight norm folded (CPU fp32)."""
         return fold_state_dict({k: v.detach().cpu() for k, v in self.state_dict().items()}, self.layer_names())
+
+    def forward(self, x, lengths=None):
+        from .vocoder_train import generator_forward
+        return generator_forward(self, x, lengths)
 
 
 def fold_state_dict(state: dict, layers) -> dict:
@@ -402,7 +418,7 @@ class HiFiGanVocoder:
         state = _checkpoint_state(checkpoint_path)
         layers = generator.layer_names()
         self.weights = fold_state_dict(state, layers)          # {layer: (folded weight, bias)}, CPU fp32: what the kernels run
-        # ``generator``: the checkpoint's weight-normed parameters (CPU, frozen; no forward -- ``infer`` / ``infer_batch`` are the
+        # ``generator``: the checkpoint's weight-normed parameters (CPU, frozen: ``infer`` / ``infer_batch`` are this object's
         # forward).  None for a checkpoint that is already folded: there are no weight_g / weight_v to hold.
         self.generator = None
         if all(n + '.weight_v' in state for n in layers):
