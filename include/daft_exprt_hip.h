@@ -598,6 +598,38 @@ int dx_disc_first_bwd(const float* dZ, const float* W, float* dy, long sdb, int 
  * dropped); accumulate = 1 adds to dx. */
 int dx_disc_pool_bwd(const float* dy, float* dx, int R, int T, int accumulate, void* stream);
 
+/* ---- HiFi-GAN discriminators, the discriminator step (csrc/dx_disc_wgrad.hip) ---------------------------------
+ * The gradient of loss_disc with respect to the folded (weight, bias) of every layer, over all rows of a pass (real rows first), f32
+ * operands only.  Buffers and row addressing are the forward's; the data gradient between the layers is dx_disc_conv_dgrad with
+ * R = G = the whole stored map and gw_fm -> a device zero.  No atomics: every sum runs over a fixed number of runs, a function of the
+ * shape alone, whose partial sums go through the caller's workspace and are added in order by a second launch. */
+/* bytes of workspace dx_disc_wgrad needs; splits (may be null): the number of runs its k axis is cut into */
+int dx_disc_wgrad_size(int rows, int N, int Cin, int Cout, int groups, int taps, int stride, int pad, long* bytes, int* splits);
+/* Weight gradient of dx_disc_conv's layer.  A: the layer's input map (rows of N positions, Cin channels, strides sxb, sxr, sxn), dZ:
+ * its pre-activation gradient (rows of Nout = (N + 2 pad - taps) / stride + 1 positions, Cout channels, strides szb, szr, szn) ->
+ * G (Cout, Cin / groups, taps), G[co][ci][t] = sum over rows and m < Nout of A[row][m stride - pad + t][group(co) Cin / groups + ci]
+ * dZ[row][m][co] (positions outside [0, N) read as zero), and dbias[co] = sum dZ[row][m][co].  v_mfma_f32_16x16x4_f32, the flattened
+ * (row, m) sequence as k.  taps <= 41, stride <= 4, pad <= 20; channels per group: in 8, 16, 32 or a multiple of 64, out 16, 32 or a
+ * multiple of 64.  A and dZ 16-byte aligned with strides % 4 == 0; workspace 16-byte aligned. */
+int dx_disc_wgrad(const float* A, long sxb, long sxr, long sxn, const float* dZ, long szb, long szr, long szn, float* G, float* dbias,
+                  void* workspace, long workspace_bytes, int rows, int rdiv, int N, int Cin, int Cout, int groups, int taps, int stride,
+                  int pad, void* stream);
+int dx_disc_post_wgrad_size(int rows, int N, int C, int taps, long* bytes);
+/* The score seed and the Cout = 1 last layer: dS[row][m] = gw[0] s_scale (S[row][m] - 1) for row < half_rows (the real rows),
+ * gw[0] s_scale S[row][m] for the others (the generated rows); s_scale = 2 / numel of one half of the scores.  dZ[row][n][c] =
+ * (A[row][n][c] > 0 ? 1 : 0.1) sum_t dS[row][n + (taps - 1) / 2 - t] W[c][t], A the last conv layer's stored map; dW[c][t] = sum
+ * dS[row][m] A[row][m - (taps - 1) / 2 + t][c]; db[0] = sum dS, added in double.  S is addressed with (ssb, ssr, ssn), A and dZ with
+ * (sxb, sxr, sxn) and C channels; W the folded (1, C, taps); odd taps <= 8; dZ must not alias A; workspace 8-byte aligned. */
+int dx_disc_post_wgrad(const float* S, long ssb, long ssr, long ssn, const float* W, const float* A, float* dZ, long sxb, long sxr, long sxn,
+                       const float* gw, float s_scale, float* dW, float* db, void* workspace, long workspace_bytes, int rows,
+                       int half_rows, int rdiv, int N, int C, int taps, void* stream);
+int dx_disc_first_wgrad_size(int R, int T, int p, int Cout, int taps, int stride, int pad, long* bytes);
+/* The Cin = 1 first layer: x [R][sxb] waveforms of T samples read through the period view (H = ceil(T / p) rows of p columns, the
+ * tail reflect-padded while reading, as dx_disc_first reads), dZ [R][Hout][p][Cout] -> dW (Cout, 1, taps), dW[co][t] = sum
+ * x_view[b][m stride - pad + t][column] dZ[b][m][column][co], and db[co] = sum dZ.  Cout a divisor of 256, taps <= 16. */
+int dx_disc_first_wgrad(const float* x, long sxb, int T, const float* dZ, float* dW, float* db, void* workspace, long workspace_bytes, int R,
+                        int p, int Cout, int taps, int stride, int pad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,10 +6,14 @@ profiling.price() from the launches themselves, and per-kernel times with TFLOP/
 Times are host clocks around work that ends in a device synchronise, after warm-up; the per-kernel figures bracket each launch with
 events (profiling.py), in a pass of their own.  Needs a GPU: there is no fallback.
 
-    python tools/bench_discriminators.py [--backward]
+    python tools/bench_discriminators.py [--backward | --train]
 
 ``--backward`` measures the generator side instead: ``losses()``, ``generator_loss_grad()`` (the same pass + the backward to the
 generated waveform), the per-kernel split of the backward, and torch autograd of the restatement (forward + backward) on the same GPU.
+
+``--train`` measures the discriminator step (f32): ``losses()``, ``discriminator_loss_grad(power_iterations=0)`` (the same pass + the
+gradient of loss_disc to all 154 parameters), the per-kernel split of the step, and torch fp32 autograd of the restatement from the
+folded weights to loss_disc (forward + backward to the 56 folded (weight, bias) pairs) on the same GPU.
 """
 import json
 import os
@@ -68,11 +72,58 @@ def backward_main():
     print(json.dumps(out))
 
 
+STEP_KERNELS = ('dx_disc_wgrad', 'dx_disc_post_wgrad', 'dx_disc_first_wgrad', 'dx_disc_conv_dgrad', 'dx_disc_dgrad_pack')
+
+
+def train_main():
+    dev = 'cuda'
+    y, y_hat = (t.to(dev) for t in dh.make_inputs(T, 9, batch=B))
+    states = dh.state_dicts()
+    out = {'workload': f'B={B} segments of {T} samples, real + generated; loss_disc to all 154 parameters'}
+    geom = profiling.Geometry([[1]])
+    D = disc.HiFiGanDiscriminators(states, device=dev)
+    with torch.no_grad():
+        t_fwd = timed(lambda: D.losses(y, y_hat))
+    t_all = timed(lambda: D.discriminator_loss_grad(y, y_hat, power_iterations=0))
+    recs = []
+    old = _lib.set_timer(recs)
+    D.discriminator_loss_grad(y, y_hat, power_iterations=0)
+    _lib.set_timer(old)
+    torch.cuda.synchronize()
+    step = [r for r in recs if r[0] in STEP_KERNELS]
+    flops = sum(profiling.price(name, args, geom)[2] or 0.0 for name, args, _, _ in step)
+    out['hip_f32'] = {'losses_s': round(t_fwd, 6), 'discriminator_loss_grad_s': round(t_all, 6), 'step_s': round(t_all - t_fwd, 6),
+                      'step_launches': len(step), 'step_tflop': round(flops / 1e12, 4), 'over_losses': round(t_all / t_fwd, 2)}
+    out['profile_step_f32'] = profiling.summarize(step, geom, 'f32')
+    layers = {}                                     # the weight-gradient launches by layer class: [launches, us, FLOPs]
+    for name, args, ev0, ev1 in step:
+        if name == 'dx_disc_wgrad':
+            key = '{Cin}->{Cout} k{taps} s{stride} g{groups}'.format(**args)
+            e = layers.setdefault(key, [0, 0.0, 0.0])
+            e[0] += 1
+            e[1] += ev0.elapsed_time(ev1) * 1e3
+            e[2] += profiling.price(name, args, geom)[2]
+    out['wgrad_by_layer_class'] = {k: {'launches': n, 'total_us': round(us, 1), 'tflops': round(fl / us / 1e6, 2)} for k, (n, us, fl) in layers.items()}
+    folded ={'mpd': {k: (w.reshape(w.shape[0], w.shape[1], w.shape[2]).to(dev), b.to(dev)) for k, (w, b) in disc.fold_state_dict(states['mpd']).items()},
+              'msd': {k: (w.to(dev), b.to(dev)) for k, (w, b) in disc.fold_state_dict(states['msd']).items()}}
+
+    def autograd():
+        leaves = {d: {k: (w.detach().requires_grad_(True), b.detach().requires_grad_(True)) for k, (w, b) in f.items()} for d, f in folded.items()}
+        six = disc_torch.six_losses(disc_torch.mpd(y, y_hat, leaves['mpd']), disc_torch.msd(y, y_hat, leaves['msd']))
+        (six['loss_disc_f'] + six['loss_disc_s']).backward()
+        return leaves
+    out['torch_fp32_autograd'] = {'s': round(timed(autograd, n=5, warm=2), 6)}
+    out['hip_f32_over_torch_fp32'] = round(out['torch_fp32_autograd']['s'] / out['hip_f32']['discriminator_loss_grad_s'], 2)
+    print(json.dumps(out))
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit('bench_discriminators needs a GPU')
     if '--backward' in sys.argv[1:]:
         return backward_main()
+    if '--train' in sys.argv[1:]:
+        return train_main()
     dev = 'cuda'
     y, y_hat = (t.to(dev) for t in dh.make_inputs(T, 9, batch=B))
     states = dh.state_dicts()

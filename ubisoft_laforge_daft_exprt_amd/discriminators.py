@@ -1,5 +1,5 @@
-"""HiFi-GAN discriminators on gfx950 (reference src/daft_exprt/vocoder/discriminators.py): the forward, the GAN losses, and the
-backward of the generator-side losses to the generated waveform.
+"""HiFi-GAN discriminators on gfx950 (reference src/daft_exprt/vocoder/discriminators.py): the forward, the GAN losses, the
+backward of the generator-side losses to the generated waveform, and the discriminator step (loss_disc to every parameter).
 
 ``MultiPeriodDiscriminator`` / ``DiscriminatorP`` and ``MultiScaleDiscriminator`` / ``DiscriminatorS`` own exactly the reference's
 state-dict keys and shapes (90 and 80 tensors), so ``load_state_dict(strict=True)`` takes the ``['mpd']`` / ``['msd']`` entries of a
@@ -10,13 +10,18 @@ per layer.  The feature maps are permuted VIEWS of the kernels' channels-last bu
 Weight folding, once and lazily (``refresh_weights()`` drops the folded copies; ``load_state_dict`` calls it):
   * weight norm (``weight_g`` / ``weight_v``): ``torch._weight_norm(v, g, 0)``;
   * spectral norm (the first MSD sub-discriminator: ``weight_orig`` / ``weight_u`` / ``weight_v``; told apart by ``weight_orig``):
-    EVAL-mode semantics, ``W = weight_orig / (u . (W_mat v))`` with the stored ``u`` and ``v``.  The reference's train-mode power
-    iteration is NOT done and ``.train()`` does not change the forward.
+    EVAL-mode semantics, ``W = weight_orig / (u . (W_mat v))`` with the stored ``u`` and ``v``.  ``.train()`` does not change the
+    forward; the reference's train-mode power iteration runs only where it is asked for, ``discriminator_loss_grad(...,
+    power_iterations=n)``.
 
 ``forward``, ``losses`` and the three loss functions have no backward: with grad mode on, an input (or a parameter of the module) that
 requires grad raises instead of returning a silently detached result.  The parameters are created with ``requires_grad=False``.
-The one backward that exists is ``HiFiGanDiscriminators.generator_losses`` / ``generator_loss_grad`` (csrc/dx_disc_bwd.hip): the
-gradient of loss_gen and loss_fm of both discriminators with respect to ``y_hat`` only; ``y`` and the weights are constants.
+Two backwards exist, both on ``HiFiGanDiscriminators``, neither through the parameters' autograd:
+  * ``generator_losses`` / ``generator_loss_grad`` (csrc/dx_disc_bwd.hip): the gradient of loss_gen and loss_fm of both
+    discriminators with respect to ``y_hat`` only; ``y`` and the weights are constants;
+  * ``discriminator_loss_grad`` / ``discriminator_backward`` (csrc/dx_disc_wgrad.hip, f32 only): the gradient of loss_disc_f and
+    loss_disc_s with respect to every ``nn.Parameter`` of both discriminators, returned as tensors or added into ``.grad``; both
+    waveforms are constants and the parameters stay frozen leaves.
 
 ``discriminator_loss``, ``generator_loss`` and ``feature_loss`` keep the reference signatures and run through ``dx_disc_losses``.
 The one deviation: the per-sub-discriminator entries are 0-d device tensors where the reference returns ``.item()`` floats (no host
@@ -143,6 +148,51 @@ def _check_differentiable(owner, y, y_hat):
         raise RuntimeError('the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels); there is no CPU path')
 
 
+def _check_train(owner, y):
+    """The guards of the discriminator step: the parameters stay frozen leaves (their gradients are returned, or added to ``.grad``)."""
+    if owner.precision != 'f32':
+        raise RuntimeError(f"HiFiGanDiscriminators: gradients exist for precision 'f32' only, got {owner.precision!r}")
+    if any(q.requires_grad for m in (owner.mpd, owner.msd) for q in m.parameters()):
+        raise RuntimeError('the discriminator step keeps the parameters frozen (requires_grad=False) and hands their gradients out itself: '
+                           'a parameter requires grad')
+    if y.device.type != 'cuda':
+        raise RuntimeError('the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels); there is no CPU path')
+
+
+def _check_power_iterations(n):
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f'power_iterations must be a non-negative integer, got {n!r}')
+    return n
+
+
+def power_iterate(weight, u, v, n, eps=1e-12):
+    """``n`` steps of torch.nn.utils.spectral_norm's train-mode power iteration on ``weight`` (Cout, ...), IN PLACE on ``u`` (Cout) and
+    ``v`` (the rest): v <- normalize(W^T u), u <- normalize(W v), W = weight as a (Cout, -1) matrix.  ``n = 0`` touches nothing.
+    -> sigma = u . (W v), 0-d.  Any device; no gradient."""
+    with torch.no_grad():
+        w = weight.detach().reshape(weight.shape[0], -1)
+        for _ in range(_check_power_iterations(n)):
+            torch.nn.functional.normalize(torch.mv(w.t(), u), dim=0, eps=eps, out=v)
+            torch.nn.functional.normalize(torch.mv(w, v), dim=0, eps=eps, out=u)
+        return torch.dot(u, torch.mv(w, v))
+
+
+def _norm_backward(conv, name, dw, db, out):
+    """The folded pair's gradient (dw in the kernels' (Cout, Cin / groups, taps), db) -> the gradients of ``conv``'s own parameters,
+    into ``out`` under the state-dict keys: torch's backward of the weight norm, or of W / sigma with u and v constants."""
+    out[name + '.bias'] = db
+    with torch.enable_grad():
+        if isinstance(conv, _SNConv):
+            w0 = conv.weight_orig.detach().requires_grad_(True)
+            sigma = torch.dot(conv.weight_u, torch.mv(w0.reshape(w0.shape[0], -1), conv.weight_v))
+            w = w0 / sigma
+            out[name + '.weight_orig'], = torch.autograd.grad(w, (w0,), dw.view_as(w))
+        else:
+            g, v = conv.weight_g.detach().requires_grad_(True), conv.weight_v.detach().requires_grad_(True)
+            w = torch._weight_norm(v, g, 0)
+            out[name + '.weight_g'], out[name + '.weight_v'] = torch.autograd.grad(w, (g, v), dw.view_as(w))
+
+
 def _check_run(module, *xs):
     if torch.is_grad_enabled() and (any(t.requires_grad for t in xs) or any(q.requires_grad for q in module.parameters())):
         raise RuntimeError('the discriminators are forward only: their backward is not built, and an input or parameter requires grad '
@@ -254,6 +304,54 @@ class _SubDiscriminator(nn.Module):
         _, cout, k, s, _, pad = self.LAYERS[0]
         L.dx_disc_first_bwd(cur.data_ptr(), P['convs.0'][0].data_ptr(), dy.data_ptr(), dy.shape[1], T, B, p, cout, k, s, pad,
                             int(accumulate), st)
+
+    def _wgrad_workspace(self, R, T, p):
+        """-> bytes of the largest workspace the weight-gradient kernels of this sub-discriminator ask for on R rows of T samples."""
+        L, nb = lib(), torch.zeros(1, dtype=torch.long)
+        _, cout, k, s, _, pad = self.LAYERS[0]
+        L.dx_disc_first_wgrad_size(R, T, p, cout, k, s, pad, nb.data_ptr())
+        need = int(nb.item())
+        N = conv_out(-(-T // p), k, s, pad)
+        for cin, cout, k, s, g, pad in self.LAYERS[1:]:
+            L.dx_disc_wgrad_size(R * p, N, cin, cout, g, k, s, pad, nb.data_ptr(), None)
+            need = max(need, int(nb.item()))
+            N = conv_out(N, k, s, pad)
+        L.dx_disc_post_wgrad_size(R * p, N, POST[0], POST[2], nb.data_ptr())
+        return max(need, int(nb.item()))
+
+    def _run_wgrad(self, x2, score, fmaps, B, p, gw, dz, ws, zero):
+        """The discriminator step of one sub-discriminator (csrc/dx_disc_wgrad.hip): x2 (2B, T) its input, score (2B, N, p) and the
+        channels-last maps of a pass, real rows first; gw -> ONE device float, the upstream gradient of its discriminator loss; dz two
+        buffers for the pre-activation gradients of all 2B rows; ws the workspace; zero -> a device zero (dx_disc_conv_dgrad's
+        feature-matching weight) -> {layer: (dW (Cout, Cin / groups, taps), db)} of the folded pairs.  Top down, each layer's weight
+        gradient launched before its data gradient, so the two dz buffers suffice."""
+        L, st, dev = lib(), _stream(score.device), score.device
+        P, D = self._device_weights(), self._dgrad_weights()
+        N, C, R = score.shape[1], POST[0], 2 * B
+        last = fmaps[-1]
+        cur, nxt = dz
+        out = {}
+        dW, db = _fresh((POST[1], C, POST[2]), dev), _fresh((POST[1],), dev)
+        L.dx_disc_post_wgrad(score.data_ptr(), N * p, 1, p, P['conv_post'][0].data_ptr(), last.data_ptr(), cur.data_ptr(), N * p * C, C, p * C, gw,
+                             2.0 / (score.numel() // 2), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), R * p, B * p, p, N, C, POST[2], st)
+        out['conv_post'] = (dW, db)
+        for i in range(len(self.LAYERS) - 1, 0, -1):
+            cin, cout, k, s, grp, pad = self.LAYERS[i]
+            below = fmaps[i - 1]
+            n_in, n_out = below.shape[1], fmaps[i].shape[1]
+            dW, db = _fresh((cout, cin // grp, k), dev), _fresh((cout,), dev)
+            L.dx_disc_wgrad(below.data_ptr(), n_in * p * cin, cin, p * cin, cur.data_ptr(), n_out * p * cout, cout, p * cout, dW.data_ptr(),
+                            db.data_ptr(), ws.data_ptr(), ws.numel(), R * p, p, n_in, cin, cout, grp, k, s, pad, st)
+            out[f'convs.{i}'] = (dW, db)
+            L.dx_disc_conv_dgrad(cur.data_ptr(), n_out * p * cout, cout, p * cout, D[i].data_ptr(), nxt.data_ptr(), below.data_ptr(),
+                                 below.data_ptr(), n_in * p * cin, cin, p * cin, zero, 0.0, R * p, p, n_in, cin, cout, grp, k, s, pad, 1, 0, st)
+            cur, nxt = nxt, cur
+        _, cout, k, s, _, pad = self.LAYERS[0]
+        dW, db = _fresh((cout, 1, k), dev), _fresh((cout,), dev)
+        L.dx_disc_first_wgrad(x2.data_ptr(), x2.shape[1], x2.shape[1], cur.data_ptr(), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), R, p,
+                              cout, k, s, pad, st)
+        out['convs.0'] = (dW, db)
+        return out
 
     def _run(self, x2, p, alloc):
         """x2 (R, T) fp32 contiguous on the device, period p (1: no folding) -> (scores (R, N, p), [channels-last feature maps
@@ -386,7 +484,8 @@ class MultiScaleDiscriminator(_MultiDiscriminator):
 
     _views = staticmethod(_views_s)
 
-    def _run(self, x2, alloc):
+    def _run(self, x2, alloc, inputs=None):
+        """``inputs``: a list that receives the (R, T_i) input of each sub-discriminator (the waveforms, then the two pooled buffers)."""
         out = []
         for i, d in enumerate(self.discriminators):
             if i:
@@ -394,6 +493,8 @@ class MultiScaleDiscriminator(_MultiDiscriminator):
                 pooled = alloc((R, T // 2 + 1), x2.device)
                 lib().dx_disc_pool(x2.data_ptr(), pooled.data_ptr(), R, T, _stream(x2.device))
                 x2 = pooled
+            if inputs is not None:
+                inputs.append(x2)
             out.append(d._run(x2, 1, alloc))
         return out
 
@@ -511,10 +612,12 @@ class HiFiGanDiscriminators:
         self.msd.to(self.device).eval()
         self._plans = {}
 
-    def _pass(self, y, y_hat, differentiable=False):
+    def _pass(self, y, y_hat, differentiable=False, train=False):
         _check_inputs(y, y_hat)
         _check_reflect(y.shape[2], PERIODS)
-        if differentiable:
+        if train:
+            _check_train(self, y)
+        elif differentiable:
             _check_differentiable(self, y, y_hat)
         else:
             _check_run(self.mpd, y, y_hat)
@@ -528,7 +631,8 @@ class HiFiGanDiscriminators:
         plan['f'].reset()
         plan['s'].reset()
         mpd = self.mpd._run(x2, plan['f'])
-        msd = self.msd._run(x2, plan['s'])
+        plan['inputs'] = [x2] * len(PERIODS)         # the (2B, T_i) input of every sub-discriminator, for the first layers' weight gradients
+        msd = self.msd._run(x2, plan['s'], plan['inputs'])
         return plan, B, mpd, msd
 
     def losses(self, y, y_hat) -> dict:
@@ -602,6 +706,82 @@ class HiFiGanDiscriminators:
                 if gw is None:                       # uploaded once per plan: a captured graph must not copy from host memory
                     gw = plan['gw'][key] = torch.tensor(key, dtype=torch.float32).to(y.device)
             return four, self._backward(state, gw)
+
+    # ---- the discriminator step: loss_disc to every parameter (csrc/dx_disc_wgrad.hip) ---------------------------------
+    def _spectral_layers(self):
+        return [c for d in self.msd.discriminators if d.use_spectral_norm for c in list(d.convs) + [d.conv_post]]
+
+    def discriminator_loss_grad(self, y, y_hat, weights=(1.0, 1.0), power_iterations=1):
+        """-> ({'loss_disc_f', 'loss_disc_s'}, {'mpd': {state-dict key: gradient}, 'msd': {...}}): the two discriminator losses (the
+        bits of ``losses()``) and the gradient of ``weights[0] loss_disc_f + weights[1] loss_disc_s`` with respect to every
+        ``nn.Parameter`` of both discriminators (154 tensors, each in its parameter's own shape), without autograd.  ``weights``: two
+        floats or an fp32 device tensor of 2, read on the device.  Both waveforms are constants (``y_hat`` is detached, as the reference
+        passes ``y_g_hat.detach()``); the parameters stay ``requires_grad=False``.  Precision 'f32' only.
+
+        ``power_iterations`` = n > 0 first runs n steps of the spectral norm's power iteration on the eight spectral-normed layers,
+        writing ``weight_u`` / ``weight_v`` in place and dropping their folded packs (``eps`` 1e-12, as torch.nn.utils.spectral_norm);
+        n = 0 is the eval-mode fold of ``forward``.  The gradient of ``weight_orig`` goes through W / sigma with u and v constants, as
+        torch's.  Deviation from the reference: its train-mode ``msd(y, y_hat)`` calls the spectral sub-discriminator twice, so it
+        iterates twice per step and the real and the generated rows see sigmas of successive iterations; here both halves share one
+        pass and one sigma.  At the fixed point of the iteration the two agree."""
+        n = _check_power_iterations(power_iterations)
+        with torch.no_grad():
+            _check_inputs(y, y_hat)
+            _check_reflect(y.shape[2], PERIODS)
+            _check_train(self, y)
+            dev, key = y.device, None
+            if torch.is_tensor(weights):
+                if weights.shape != (2,) or weights.dtype != torch.float32 or weights.device != dev:
+                    raise ValueError('weights: two floats or an fp32 tensor of 2 on the inputs\' device')
+                gw = weights.detach().contiguous()
+            else:
+                key = tuple(float(w) for w in weights)
+                if len(key) != 2:
+                    raise ValueError('weights: two floats or an fp32 tensor of 2 on the inputs\' device')
+            if n:
+                for c in self._spectral_layers():
+                    power_iterate(c.weight_orig, c.weight_u, c.weight_v, n)
+                for d in self.msd.discriminators:
+                    if d.use_spectral_norm:
+                        d.refresh_weights()
+            plan, B, mpd, msd = self._pass(y, y_hat, train=True)
+            six = self._losses(plan, B, mpd, msd, y.device)
+            if key is not None:
+                gw = plan['gw'].get(key)
+                if gw is None:                       # uploaded once per plan, as generator_loss_grad's
+                    gw = plan['gw'][key] = torch.tensor(key, dtype=torch.float32).to(dev)
+            subs = list(zip(self.mpd.discriminators, mpd, [d.period for d in self.mpd.discriminators], [0] * len(mpd))) + \
+                list(zip(self.msd.discriminators, msd, [1] * len(msd), [1] * len(msd)))
+            inputs = plan['inputs']
+            if plan.get('train') is None:
+                biggest = max(f.numel() for _, fm in mpd + msd for f in fm)
+                need = max(d._wgrad_workspace(2 * B, x.shape[1], p) for (d, _, p, _), x in zip(subs, inputs))
+                plan['train'] = {'dz': (_fresh((biggest,), dev), _fresh((biggest,), dev)), 'zero': torch.zeros(1, dtype=torch.float32, device=dev),
+                                 'ws': torch.empty(need, dtype=torch.uint8, device=dev)}
+            tr = plan['train']
+            grads = {'mpd': {}, 'msd': {}}
+            for j, ((d, (score, fmaps), p, which), x) in enumerate(zip(subs, inputs)):
+                folded = d._run_wgrad(x, score, fmaps, B, p, gw.data_ptr() + 4 * which, tr['dz'], tr['ws'], tr['zero'].data_ptr())
+                i = j if which == 0 else j - len(mpd)
+                for name, (dw, db) in folded.items():
+                    conv = d.conv_post if name == 'conv_post' else d.convs[int(name[len('convs.'):])]
+                    _norm_backward(conv, f'discriminators.{i}.{name}', dw, db, grads['msd' if which else 'mpd'])
+            return {'loss_disc_f': six['loss_disc_f'], 'loss_disc_s': six['loss_disc_s']}, grads
+
+    def discriminator_backward(self, y, y_hat, weights=(1.0, 1.0), power_iterations=1):
+        """``discriminator_loss_grad`` whose gradients are ADDED into each parameter's ``.grad`` (created where it is None) -> the two
+        losses.  The parameters stay frozen leaves: an optimiser steps whatever has a ``.grad``, so the discriminator step is
+        ``optim_d.zero_grad(); D.discriminator_backward(y, y_hat); optim_d.step(); D.mpd.refresh_weights(); D.msd.refresh_weights()``."""
+        two, grads = self.discriminator_loss_grad(y, y_hat, weights, power_iterations)
+        with torch.no_grad():
+            for tag, module in (('mpd', self.mpd), ('msd', self.msd)):
+                for key, q in module.named_parameters():
+                    g = grads[tag][key]
+                    if q.grad is None:
+                        q.grad = g.clone()
+                    else:
+                        q.grad.add_(g)
+        return two
 
 
 class _GeneratorLosses(torch.autograd.Function):

@@ -244,6 +244,18 @@ def price(name, a, geom: Geometry):
         return 'disc_pool_bwd', 'hbm', None, a['R'] * (a['T'] // 2 + 1 + a['T'] * (2 if g('accumulate') else 1)) * 4
     if name == 'dx_disc_dgrad_pack':
         return 'disc_dgrad_pack', 'hbm', None, a['Cout'] * (a['Cin'] // a['groups']) * a['taps'] * (4 + (2 if a['bf16'] else 4))
+    if name == 'dx_disc_wgrad':                          # the forward layer's FLOPs; A and dZ read once per tap group at best, G written
+        nout = (a['N'] + 2 * a['pad'] - a['taps']) // a['stride'] + 1
+        cin_g = a['Cin'] // a['groups']
+        byt = a['rows'] * (a['N'] * a['Cin'] + nout * a['Cout']) * 4 + a['Cout'] * (cin_g * a['taps'] + 1) * 4
+        kind = 'disc_wgrad_grouped' if a['groups'] > 1 else 'disc_wgrad'
+        return f'{kind}<f32>', 'mfma', 2.0 * a['rows'] * nout * a['taps'] * cin_g * a['Cout'], byt
+    if name == 'dx_disc_post_wgrad':                     # the scores and the last map read, dZ written, the map read again for dW
+        return 'disc_post_wgrad', 'hbm', None, a['rows'] * a['N'] * (1 + 3 * a['C']) * 4
+    if name == 'dx_disc_first_wgrad':                    # dZ and the waveform read once
+        h = -(-a['T'] // a['p'])
+        hout = (h + 2 * a['pad'] - a['taps']) // a['stride'] + 1
+        return 'disc_first_wgrad', 'hbm', None, a['R'] * (hout * a['p'] * a['Cout'] + a['T']) * 4
     if name == 'dx_mel':                                 # valid frames only: DFT GEMM (2 kmax outputs of 1024) + mel GEMM per frame
         frames = geom.rows(a['B'], a['T_max'])
         flops = 2.0 * frames * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])
