@@ -630,6 +630,31 @@ int dx_disc_first_wgrad_size(int R, int T, int p, int Cout, int taps, int stride
 int dx_disc_first_wgrad(const float* x, long sxb, int T, const float* dZ, float* dW, float* db, void* workspace, long workspace_bytes, int R,
                         int p, int Cout, int taps, int stride, int pad, void* stream);
 
+/* ---- HiFi-GAN fine-tuning, the optimiser step (csrc/dx_vocoder_optim.hip) ---------------------------------------
+ * Reference call sites: torch.optim.AdamW over generator.parameters() and over chain(msd.parameters(), mpd.parameters())
+ * (vocoder/finetune_hifigan.py:130-135), optim_d.step() (:226), optim_g.step() (:243), with torch.nn.utils.weight_norm's backward and
+ * fold around them.  One launch steps every tensor of one optimiser from a job table in DEVICE memory.
+ *
+ * A job is 11 longs on the host: kind, R, n, then the device addresses v, g, dW, m_v, s_v, m_g, s_g, W.
+ *   kind 1, weight-normed: v (R, n) with contiguous rows, g (R), the norm over each row (torch._weight_norm(v, g, 0)); dW the gradient
+ *     of the FOLDED weight in v's layout; m_*, s_* AdamW's exp_avg and exp_avg_sq of v and g; W (R, n) receives the folded weight.
+ *     Per row: nrm = |v_r|, dg = <dW_r, v_r> / nrm, dv = (g / nrm) (dW_r - (dg / nrm) v_r); AdamW on (g, dg) and on (v_r, dv);
+ *     W_r = g' v'_r / |v'_r| from the values as stored.  n <= 6144.  A row with |v_r| = 0 gives non-finite values, as torch does.
+ *   kind 0, plain: AdamW on the n elements of v with the gradient dW and the moments m_v, s_v; R = 1; g, m_g, s_g, W are not read.
+ * AdamW as torch defines it: p <- p (1 - lr wd); m <- b1 m + (1 - b1) grad; s <- b2 s + (1 - b2) grad^2;
+ * p <- p - (lr / (1 - b1^step)) m / (sqrt(s) / sqrt(1 - b2^step) + eps); the factors are formed on the host in double.
+ * v, dW, m_v, s_v, W 16-byte aligned, g, m_g, s_g 4-byte.  Fixed-order sums, no atomics: the result bits depend on the job alone, not
+ * on the other jobs of the table. */
+/* bytes of the table for these jobs (host memory, checked as dx_wn_adamw_table checks them) and the number of workgroups of a launch */
+int dx_wn_adamw_table_size(const long* jobs, int njobs, long* bytes, int* blocks);
+/* checks every job and lays the table out in HOST memory (`table`, `bytes` as reported); the caller copies it to the device */
+int dx_wn_adamw_table(const long* jobs, int njobs, void* table, long bytes);
+/* the step: in place on v, g and the moments, W written; table: the device copy; step >= 1, betas in [0, 1) */
+int dx_wn_adamw(const void* table, int njobs, int blocks, double lr, double beta1, double beta2, double eps, double weight_decay, int step,
+                void* stream);
+/* W of every weight-normed job from its stored v and g, through the step's own fold code (the same bits); plain jobs are skipped */
+int dx_wn_fold(const void* table, int njobs, int blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,3 +17,5 @@ from .griffin_lim import GriffinLim, GriffinLimVocoder, griffin_lim_reconstructi
 from .speech import SpeechSynthesizer, condition_external_prosody, symbol_prosody, to_pcm16  # noqa: F401
 from .discriminators import (DiscriminatorP, DiscriminatorS, HiFiGanDiscriminators, MultiPeriodDiscriminator,  # noqa: F401
                              MultiScaleDiscriminator, discriminator_loss, feature_loss, generator_loss)
+from .vocoder_optim import NormedAdamW  # noqa: F401
+from .vocoder_finetune import HiFiGanFineTuner  # noqa: F401

@@ -235,11 +235,24 @@ class _SubDiscriminator(nn.Module):
         self.conv_post = conv_cls((POST[1], POST[0], POST[2]) + tail)
         self._packs = None
         self._dgrad = None
+        self._folded = None
 
-    def refresh_weights(self):
-        """Drop the folded, packed device weights: the next forward folds the current parameters again."""
+    def refresh_weights(self, folded=None):
+        """Drop the folded, packed device weights: the next forward folds the current parameters again.  ``folded``: {layer: (W, bias)}
+        that the caller vouches to BE the fold of the current parameters (vocoder_optim.NormedAdamW.folded(): the optimiser kernel
+        writes W as it steps g and v); the next packs are built from these tensors instead of folding with torch.  They are dropped
+        again by any ``load_state_dict``, ``.to()`` or plain ``refresh_weights()``."""
         self._packs = None
         self._dgrad = None
+        if folded is not None:
+            names = [f'convs.{i}' for i in range(len(self.convs))] + ['conv_post']
+            if sorted(folded) != sorted(names):
+                raise ValueError(f'refresh_weights: folded must hold exactly the layers {names}, got {sorted(folded)}')
+            for n in names:
+                w, v = folded[n][0], (self.conv_post if n == 'conv_post' else self.convs[int(n[len('convs.'):])]).weight_v
+                if w.numel() != v.numel() or w.device != v.device or w.dtype != torch.float32 or not w.is_contiguous():
+                    raise ValueError(f'refresh_weights: the folded weight of {n} must be contiguous fp32 with weight_v\'s {v.numel()} elements on {v.device}')
+        self._folded = folded
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
@@ -249,10 +262,13 @@ class _SubDiscriminator(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         self._packs = None                      # .to() / .cuda(): the packs follow the parameters
         self._dgrad = None
+        self._folded = None
         return super()._apply(fn, *args, **kwargs)
 
     def folded(self) -> dict:
         """-> {layer: (weight (Cout, Cin / groups, taps), bias)} on the parameters' device."""
+        if self._folded is not None:             # handed in by refresh_weights(folded): views, no fold here
+            return {n: (w.detach().view(w.shape[0], w.shape[1], w.shape[2]), b.detach()) for n, (w, b) in self._folded.items()}
         out = fold_state_dict({k: v.detach() for k, v in self.state_dict().items()})
         return {n: (w.reshape(w.shape[0], w.shape[1], w.shape[2]).contiguous(), b) for n, (w, b) in out.items()}
 
@@ -427,9 +443,13 @@ class DiscriminatorS(_SubDiscriminator):
 
 
 class _MultiDiscriminator(nn.Module):
-    def refresh_weights(self):
-        for d in self.discriminators:
-            d.refresh_weights()
+    def refresh_weights(self, folded=None):
+        """``folded``: {'discriminators.<i>.<layer>': (W, bias)}, see _SubDiscriminator.refresh_weights; a sub-discriminator none of whose
+        layers is named (the spectral-normed one) folds its own parameters as before."""
+        for i, d in enumerate(self.discriminators):
+            prefix = f'discriminators.{i}.'
+            own = None if folded is None else {k[len(prefix):]: v for k, v in folded.items() if k.startswith(prefix)}
+            d.refresh_weights(own or None)
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
@@ -711,7 +731,7 @@ class HiFiGanDiscriminators:
     def _spectral_layers(self):
         return [c for d in self.msd.discriminators if d.use_spectral_norm for c in list(d.convs) + [d.conv_post]]
 
-    def discriminator_loss_grad(self, y, y_hat, weights=(1.0, 1.0), power_iterations=1):
+    def discriminator_loss_grad(self, y, y_hat, weights=(1.0, 1.0), power_iterations=1, folded=False):
         """-> ({'loss_disc_f', 'loss_disc_s'}, {'mpd': {state-dict key: gradient}, 'msd': {...}}): the two discriminator losses (the
         bits of ``losses()``) and the gradient of ``weights[0] loss_disc_f + weights[1] loss_disc_s`` with respect to every
         ``nn.Parameter`` of both discriminators (154 tensors, each in its parameter's own shape), without autograd.  ``weights``: two
@@ -723,7 +743,12 @@ class HiFiGanDiscriminators:
         n = 0 is the eval-mode fold of ``forward``.  The gradient of ``weight_orig`` goes through W / sigma with u and v constants, as
         torch's.  Deviation from the reference: its train-mode ``msd(y, y_hat)`` calls the spectral sub-discriminator twice, so it
         iterates twice per step and the real and the generated rows see sigmas of successive iterations; here both halves share one
-        pass and one sigma.  At the fixed point of the iteration the two agree."""
+        pass and one sigma.  At the fixed point of the iteration the two agree.
+
+        ``folded=True`` stops before torch's weight-norm backward: a weight-normed layer's entry is then the pair (dW, db) of its FOLDED
+        weight (dW in the kernels' (Cout, Cin / groups, taps), weight_v's memory layout) under the key ``discriminators.<i>.<layer>``,
+        which is what vocoder_optim.NormedAdamW.step takes; a spectral-normed layer's entries are unchanged.  The losses are the same
+        bits either way."""
         n = _check_power_iterations(power_iterations)
         with torch.no_grad():
             _check_inputs(y, y_hat)
@@ -761,11 +786,14 @@ class HiFiGanDiscriminators:
             tr = plan['train']
             grads = {'mpd': {}, 'msd': {}}
             for j, ((d, (score, fmaps), p, which), x) in enumerate(zip(subs, inputs)):
-                folded = d._run_wgrad(x, score, fmaps, B, p, gw.data_ptr() + 4 * which, tr['dz'], tr['ws'], tr['zero'].data_ptr())
+                pairs = d._run_wgrad(x, score, fmaps, B, p, gw.data_ptr() + 4 * which, tr['dz'], tr['ws'], tr['zero'].data_ptr())
                 i = j if which == 0 else j - len(mpd)
-                for name, (dw, db) in folded.items():
+                for name, (dw, db) in pairs.items():
                     conv = d.conv_post if name == 'conv_post' else d.convs[int(name[len('convs.'):])]
-                    _norm_backward(conv, f'discriminators.{i}.{name}', dw, db, grads['msd' if which else 'mpd'])
+                    if folded and not isinstance(conv, _SNConv):
+                        grads['msd' if which else 'mpd'][f'discriminators.{i}.{name}'] = (dw, db)
+                    else:
+                        _norm_backward(conv, f'discriminators.{i}.{name}', dw, db, grads['msd' if which else 'mpd'])
             return {'loss_disc_f': six['loss_disc_f'], 'loss_disc_s': six['loss_disc_s']}, grads
 
     def discriminator_backward(self, y, y_hat, weights=(1.0, 1.0), power_iterations=1):

@@ -256,6 +256,14 @@ def price(name, a, geom: Geometry):
         h = -(-a['T'] // a['p'])
         hout = (h + 2 * a['pad'] - a['taps']) // a['stride'] + 1
         return 'disc_first_wgrad', 'hbm', None, a['R'] * (hout * a['p'] * a['Cout'] + a['T']) * 4
+    if name in ('dx_wn_adamw', 'dx_wn_fold'):            # the job table is in device memory: its owner logged the element counts
+        from . import vocoder_optim
+        normed, plain = vocoder_optim.TABLE_LOG.get(a['table'], (None, None))
+        if normed is None:
+            return name[3:], 'hbm', None, None
+        if name == 'dx_wn_fold':                         # v read, W written
+            return 'wn_fold', 'hbm', None, normed * 8
+        return 'wn_adamw', 'hbm', None, normed * 32 + plain * 28      # dW, v, m, s read; v, m, s (and W) written
     if name == 'dx_mel':                                 # valid frames only: DFT GEMM (2 kmax outputs of 1024) + mel GEMM per frame
         frames = geom.rows(a['B'], a['T_max'])
         flops = 2.0 * frames * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])

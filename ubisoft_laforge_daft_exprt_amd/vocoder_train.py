@@ -14,7 +14,9 @@ Weight norm is autograd's: the module folds ``torch._weight_norm(v, g, 0)`` on t
 ``pad_folded_weights``; the autograd function takes the folded (weight, bias) pairs and returns their gradients, from which PyTorch
 derives those of g and v (the padded channels' gradients fall away in ``cat``'s backward).
 
-Not here: the fused pair / chain in training, an optimiser, graph capture of the step, the discriminators' weight
+``generator_forward_folded`` is the same forward from folded leaves the caller owns (the fine-tuning loop).
+
+Not here: the fused pair / chain in training, graph capture of the step, the discriminators' weight
 gradients, the gradient to the mel, bf16 operands."""
 from __future__ import annotations
 
@@ -264,6 +266,41 @@ def generator_forward(module, x, lengths=None):
             module._inference = (key, HiFiGanVocoder(state, config=module.config, device=dev, precision=module.precision))
         audio, _ = module._inference[1].infer_batch(x, lengths)
         return audio[:, None, :]
+    weights = {}
+    for name in module.layer_names():
+        m = module.get_submodule(name)
+        weights[name] = (torch._weight_norm(m.weight_v, m.weight_g, 0), m.bias)
+    return _forward_folded(module, x, lengths, weights)
+
+
+def generator_forward_folded(module, x, folded, lengths=None):
+    """``HiFiGANGenerator.forward`` in training from caller-owned folded weights: ``folded`` {layer: (W, bias)}, W in weight_v's shape --
+    leaves that require grad, e.g. vocoder_optim.NormedAdamW(..., leaves=True).folded().  After ``backward()`` their ``.grad`` is the
+    gradient of the folded weight; torch's weight-norm fold and its backward never run.  The caller vouches that W is the fold of the
+    module's parameters."""
+    if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != module.config['model_in_dim']:
+        raise ValueError(f'HiFiGANGenerator: x must be a (B, {module.config["model_in_dim"]}, T) mel, got '
+                         f'{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}')
+    names = module.layer_names()
+    if sorted(folded) != sorted(names):
+        raise ValueError('generator_forward_folded: folded must hold exactly the generator\'s layers')
+    for name in names:
+        w, v = folded[name][0], module.get_submodule(name).weight_v
+        if w.shape != v.shape or w.device != v.device or w.dtype != torch.float32:
+            raise ValueError(f'generator_forward_folded: the folded weight of {name} must be fp32 of shape {tuple(v.shape)} on {v.device}')
+    if x.device.type != 'cuda' or folded[names[0]][0].device.type != 'cuda':
+        raise RuntimeError('HiFiGANGenerator runs on the GPU (gfx950 HIP kernels); there is no CPU path')
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError('HiFiGANGenerator: x requires grad, and there is no gradient to the mel (dx_voc_conv has no 80-column form)')
+    if lengths is None:
+        lengths = [x.shape[2]] * x.shape[0]
+    return _forward_folded(module, x, lengths, {name: folded[name] for name in names})
+
+
+def _forward_folded(module, x, lengths, weights):
+    """The training forward after the fold: weights {layer: (folded weight, bias)} in layer order, unpadded."""
+    B, _, T = x.shape
+    dev = weights['conv_pre'][0].device
     if module.precision != 'f32':
         raise RuntimeError(f"HiFiGANGenerator: gradients exist for precision 'f32' only, got {module.precision!r}")
     mel = x.detach().float().contiguous()
@@ -274,10 +311,6 @@ def generator_forward(module, x, lengths=None):
     if frames.shape != (B,):
         raise ValueError(f'HiFiGANGenerator: {frames.numel()} lengths for a batch of {B}')
     names = tuple(module.layer_names())
-    weights = {}
-    for name in names:
-        m = module.get_submodule(name)
-        weights[name] = (torch._weight_norm(m.weight_v, m.weight_g, 0), m.bias)
     weights = pad_folded_weights(weights, module.config)
     flat = [t for name in names for t in weights[name]]
     audio = _GeneratorFunction.apply(mel, frames, json.dumps(module.config, sort_keys=True), names, *flat)
