@@ -1,0 +1,649 @@
+"""The LayerNorm row passes restated: float64 references, host-rebuilt dropout masks, a-priori bounds, fp32 emulations of the four
+summation trees, and the inputs of tests/test_ln_exact_cpu.py and tests/test_ln_exact_gpu.py.
+
+The family (head of csrc/dx_rows.hip):   z = drop_pre(a) + res,   y = mask(film(drop_post(LN(z)))),   and its backward as
+``ln_bwd_kernel`` states it.  It is stated four times with four trees for the sum over a row's C channels; ``n`` below counts the
+roundings on the longest path of that sum:
+
+  'rowvec'      ln_fwd_kernel / ln_bwd_kernel / ln_row_finish (csrc/dx_rowvec.h ``for (e < E) s += z[e]`` then ``row_sum``): a lane sums its
+                E = C / LPR channels serially, then log2(LPR) xor-shuffles.  C = 128: 7 + 4 = 11;  C = 1024: 15 + 6 = 21.
+  'pair32'      both epilogues of ff_pair_kernel (csrc/dx_ffpair.hip ``(z[0] + z[1]) + (z[2] + z[3])`` then ``off = 1 .. 16``): 2 + 5 = 7.
+  'serial8x16'  the LayerNorm-backward prologue of dx_ff_block_bwd (``for (e < 8) s1 += g[e]`` then ``off = 1 .. 8``): 7 + 4 = 11.
+
+hipcc contracts a * b + c into one fma; a contraction removes a rounding, so every bound below holds for either form and the emulations
+run both.
+
+Bounds (u = 2^-24, u_h the 16-bit unit roundoff, all magnitudes from the float64 restatement, fixed before any device run):
+
+  forward, on the fp32 z the stage was handed:
+    dmu     = (n + 1) u mean|z|                                   |mean_dev - mean| <= dmu + u |mean|
+    rel_var = ((n + 4) u var + (dmu + u max|d|)^2) / (var + eps) + 2 u          d = z - mean
+    rel_rs  = rel_var / 2 + 4 u                                   |rstd_dev - rstd| <= rstd rel_rs
+    |dy_ln| <= |w| rstd (dmu + |d| (rel_rs + 4 u)) + 2 u |y_ln| + u |b|
+    then one rounding per dropout factor, |gamma| x the bound + u |gamma t| + u |y| for FiLM, and u_h |y| for a 16-bit store
+    (+ 2^-25 in fp16: half a subnormal step, the spacing below 2^-14 being 2^-24 whatever the value).
+  backward, on the z / mean / rstd the kernel was handed (g = dy gamma post w, xh = (z - mean) rstd, s2 = mean(g xh)):
+    |ddz|  <= rstd u (4 |g| + (n + 4) mean|g| + |xh| ((n + 8) mean|g xh| + 3 |s2|)) + 2 u |dz|
+    da: x the keep factor + u |da|;  16-bit stores + u_h |value|.
+  16-bit-stored rows are held to more than that: the stored number must lie between the 16-bit roundings of (reference - fp32 bound) and
+  (reference + fp32 bound) (``between16``), which for most elements is one number.
+  channel sums (dw, dbias, dfilm): (chain + 6) u sum|terms| + chain u |base|, chain = the real length of the longest addition chain:
+    rows a lane adds serially + the shuffles over a wave's row groups + the LDS fold + the blocks whose atomics meet on the address.
+"""
+import math
+
+import numpy as np
+import torch
+
+from tests.helpers import dx_rand64_fields
+
+U = 2.0 ** -24
+EPS = float(np.float32(1e-5))
+U_H = {'bf16': 2.0 ** -8, 'fp16': 2.0 ** -11}
+SUB_H = {'bf16': 0.0, 'fp16': 2.0 ** -25}       # half a subnormal step of the 16-bit type, where fp32 values can reach it
+H16 = {'bf16': torch.bfloat16, 'fp16': torch.float16}
+SENTINEL = -12345.5
+TERM_ROUNDINGS = 6                  # roundings inside one term of a channel sum (d = dy gamma post, xh, ln, the product)
+TREE_N = {('rowvec', 128): 11, ('rowvec', 1024): 21, ('pair32', 128): 7, ('serial8x16', 128): 11}
+
+
+def f32(x):
+    return float(np.float32(x))
+
+
+def cpu(t, dtype=None):
+    t = t.detach().cpu()
+    return t if dtype is None else t.to(dtype)
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# launch rules of dx_ln_fwd / dx_ln_bwd, restated
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def row_vec(C):
+    """(lanes per row, rows per wave, channels per lane) of RowVec<C>"""
+    lpr = 64 if C >= 256 else 16
+    return lpr, 64 // lpr, C // lpr
+
+
+def fwd_rows_per_sweep(rows, C):
+    """rows one pass of ln_fwd_kernel's grid-stride loop covers: row_grid caps the grid at 8192 wave-rows of 4 waves"""
+    rpw = row_vec(C)[1]
+    grid = min((rows + 3) // 4, 8192)
+    return (cdiv(grid, rpw) if C == 128 else grid) * 4 * rpw
+
+
+def fwd_passes(rows, C):
+    return cdiv(rows, fwd_rows_per_sweep(rows, C))
+
+
+def bwd_form(B, N, C):
+    """(waves per block, rows per block) dx_ln_bwd picks"""
+    big = C == 128 and B * N >= 16384
+    return (16, 192) if big else (4, 32 if C == 1024 else 64)
+
+
+def bwd_chain(B, N, C, per_utterance):
+    """longest addition chain of a channel sum of ln_bwd_kernel: serial rows of a lane, shuffles over the wave's row groups, the LDS
+    fold ((a + b) + (c + d) per four waves, then serially), the atomics of the blocks that meet on the address"""
+    waves, rpb = bwd_form(B, N, C)
+    rpw = row_vec(C)[1]
+    serial = cdiv(min(rpb, N), waves * rpw)
+    fold = 2 + waves // 4
+    blocks = cdiv(N, rpb) * (1 if per_utterance else B)
+    return serial + int(math.log2(rpw)) + fold + blocks
+
+
+def ff_tile(B, N):
+    """tokens per tile of ff_pair_kernel: 126 once there are 96 such tiles, else 62 (ubisoft_laforge_daft_exprt_amd/ops.py, dx_ffpair.hip)"""
+    return 126 if B * cdiv(N, 126) >= 96 else 62
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# dropout masks, rebuilt on the host
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def thresh(p):
+    return int(np.rint(np.float32(p) * np.float32(65536.0)))
+
+
+def inv_keep(p):
+    return float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+
+
+def keep_factors(seed, seed_offset, rows, C, p):
+    """float64 (len(rows), C): inv_keep where element row * C + c is kept, else 0.  Draw counter = index >> 2, field = index & 3, kept iff
+    field >= lrintf(p * 65536); the seed is seed + *seed_offset (mod 2^64)."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    seed = (int(seed) + int(seed_offset or 0)) & 0xFFFFFFFFFFFFFFFF
+    first = rows[:, None] * np.uint64(C) + np.arange(0, C, 4, dtype=np.uint64)[None, :]         # index of each group of four: a multiple of 4
+    fields = dx_rand64_fields(seed, first >> np.uint64(2))
+    keep = np.stack([f >= thresh(p) for f in fields], axis=-1).reshape(len(rows), C)
+    return torch.from_numpy(keep.astype(np.float64)) * inv_keep(p)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# arithmetic: float64, plain fp32 torch, or an fp32 emulation of one summation tree (with or without fma contraction)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class Arith:
+    def __init__(self, dtype=torch.float64, tree=None, fma=True, fault=None):
+        self.dtype, self.tree, self.use_fma, self.fault = dtype, tree, fma, fault
+        self.trace = None               # a dict: every intermediate is recorded (the exact tier's representability check)
+
+    def t(self, x):
+        return None if x is None else torch.as_tensor(x).to(self.dtype)
+
+    def note(self, name, value, terms=None):
+        if self.trace is not None:
+            self.trace.setdefault(name, []).append((value, terms))
+        return value
+
+    def fma(self, a, b, c):
+        if self.dtype == torch.float64 or not self.use_fma:
+            return a * b + c
+        return (a.double() * b.double() + c.double()).float()
+
+    def rowsum(self, a, b=None, which=''):
+        """sum over the last axis of a (or of a * b) in this arithmetic's tree"""
+        if self.tree is None:
+            return (a if b is None else a * b).sum(-1)
+        lead, C = a.shape[:-1], a.shape[-1]
+
+        def lanes(x):
+            if self.tree == 'rowvec':
+                lpr = row_vec(C)[0]
+                return x.reshape(*lead, C // (lpr * 4), lpr, 4).transpose(-3, -2).reshape(*lead, lpr, C // lpr)
+            return x.reshape(*lead, 32, 4) if self.tree == 'pair32' else x.reshape(*lead, 16, 8)
+        va, vb = lanes(a), (None if b is None else lanes(b))
+        term = (lambda e: va[..., e]) if vb is None else (lambda e: va[..., e] * vb[..., e])
+        if self.tree == 'pair32':
+            if vb is None:
+                s = (va[..., 0] + va[..., 1]) + (va[..., 2] + va[..., 3])
+            else:
+                s = self.fma(va[..., 0], vb[..., 0], term(1)) + self.fma(va[..., 2], vb[..., 2], term(3))
+        else:
+            s = torch.zeros(va.shape[:-1], dtype=self.dtype)
+            for e in range(va.shape[-1]):
+                s = s + va[..., e] if vb is None else self.fma(va[..., e], vb[..., e], s)
+        L = s.shape[-1]
+        if self.fault == ('lane', which):
+            s = s.clone()
+            s[..., 3] = 0
+        idx = torch.arange(L)
+        offs = [L >> k for k in range(1, int(math.log2(L)) + 1)] if self.tree == 'rowvec' else [1 << k for k in range(int(math.log2(L)))]
+        for off in offs:
+            s = s + s[..., idx ^ off]
+        return s[..., 0]
+
+    def colsum(self, terms, base, shape, per_utterance):
+        """base + the sum of terms (B, N, C) over the rows (of each utterance, or of all), in ln_bwd_kernel's chain when emulating"""
+        B, N, C = shape
+        terms = terms.clone()
+        fault = self.fault if isinstance(self.fault, tuple) and self.fault[0] in ('row_dropped', 'block_dropped', 'wave16') else None
+        if fault and fault[0] == 'row_dropped':
+            terms[fault[1], fault[2]] = 0
+        if self.tree is None:
+            if fault and fault[0] == 'block_dropped':
+                rpb = bwd_form(B, N, C)[1]
+                terms[fault[1], fault[2] * rpb:(fault[2] + 1) * rpb] = 0
+            if fault and fault[0] == 'wave16':
+                waves, rpb = bwd_form(B, N, C)
+                n = torch.arange(N)
+                terms[:, ((n % rpb) // row_vec(C)[1]) % waves == 15] = 0
+            return base + (terms.sum(1) if per_utterance else terms.sum((0, 1)))
+        waves, rpb = bwd_form(B, N, C)
+        rpw = row_vec(C)[1]
+        G = waves * rpw
+        out = base.clone()
+        idx = torch.arange(rpw)
+        for blk in range(cdiv(N, rpb)):
+            rows = terms[:, blk * rpb:min(N, (blk + 1) * rpb)]
+            passes = cdiv(rows.shape[1], G)
+            pad = torch.zeros(B, passes * G, C, dtype=self.dtype)
+            pad[:, :rows.shape[1]] = rows
+            pad = pad.reshape(B, passes, waves, rpw, C)
+            s = torch.zeros(B, waves, rpw, C, dtype=self.dtype)
+            for k in range(passes):
+                s = s + pad[:, k]
+            off = 1
+            while off < rpw:
+                s = s + s[:, :, idx ^ off]
+                off <<= 1
+            r = s[:, :, 0]                                        # (B, waves, C)
+            if fault and fault[0] == 'wave16':
+                r = r.clone()
+                r[:, 15] = 0
+            t = torch.zeros(B, C, dtype=self.dtype)
+            for w in range(0, waves, 4):
+                t = t + ((r[:, w] + r[:, w + 1]) + (r[:, w + 2] + r[:, w + 3]))
+            for b in range(B):
+                if fault and fault[0] == 'block_dropped' and (b, blk) == tuple(fault[1:]):
+                    continue
+                if per_utterance:
+                    out[b] = out[b] + t[b]
+                else:
+                    out = out + t[b]
+        return out
+
+
+F64 = Arith()
+
+
+def emulation(tree, fma=True, fault=None):
+    return Arith(torch.float32, tree, fma, fault)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the family, restated once and evaluated in any arithmetic
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def valid_rows(c, rows, ignore_halo=False):
+    """bool (len(rows),): row n of utterance b is computed iff n < lens[b] + halo"""
+    rows = torch.as_tensor(rows, dtype=torch.long)
+    if c['lens'] is None:
+        return torch.ones(len(rows), dtype=torch.bool)
+    lim = torch.as_tensor(c['lens'], dtype=torch.long) + (0 if ignore_halo else c['halo'])
+    return (rows % c['N']) < lim[rows // c['N']]
+
+
+def all_rows(c):
+    return torch.arange(c['B'] * c['N'])
+
+
+def _film(c, ar, rows, beta_shift=0):
+    C = c['C']
+    b = torch.as_tensor(rows, dtype=torch.long) // c['N']
+    return ar.t(c['film'][:, :C])[b], ar.t(c['film'][:, C:2 * C])[(b + beta_shift) % c['B']]
+
+
+def make_z(c, rows, ar=F64):
+    """(z, padded) for the flat rows: z = drop_pre(a) + res on computed rows; on padded rows zeros where the kernel stores z (a
+    residual or a pre-dropout), else ``a`` as it was.  ``padded`` marks them."""
+    C = c['C']
+    rows = torch.as_tensor(rows, dtype=torch.long)
+    a = ar.t(c['a'].reshape(-1, C)[rows])
+    z = a
+    if c['p_pre']:
+        shift = 1 if ar.fault == 'pre_mask_row1' else 0
+        z = z * ar.t(keep_factors(c['seed_pre'], c['seed_offset'], (rows + shift).numpy(), C, c['p_pre']))
+    if c['res'] is not None:
+        z = z + ar.t(c['res'].reshape(-1, C)[rows])
+    valid = valid_rows(c, rows, ar.fault == 'no_halo')
+    stored = bool(c['p_pre']) or c['res'] is not None
+    z = torch.where(valid[:, None], z, torch.zeros_like(z) if stored else a)
+    return z, ~valid
+
+
+def ln_stage(c, rows, z, ar=F64):
+    """mean, rstd, y of the listed rows from their z (len(rows), C): the LayerNorm stage as ln_row_finish states it"""
+    C = c['C']
+    rows = torch.as_tensor(rows, dtype=torch.long)
+    valid = valid_rows(c, rows, ar.fault == 'no_halo')
+    z = torch.where(valid[:, None], ar.t(z), torch.zeros((), dtype=ar.dtype))
+    mu = ar.note('mean', ar.rowsum(z, which='mean') * (1.0 / C))
+    d = z - mu[:, None]
+    q = ar.rowsum(d, d, which='var')
+    var = q / (C - 1) if ar.fault == 'var_cm1' else q * (1.0 / C)
+    rs = 1.0 / torch.sqrt(var if ar.fault == 'no_eps' else var + ar.t(EPS))
+    t = ar.fma(d * rs[:, None], ar.t(c['w']), ar.t(c['b']))
+    if c['p_post']:
+        t = t * ar.t(keep_factors(c['seed_post'], c['seed_offset'], rows.numpy(), C, c['p_post']))
+    if c['film'] is not None:
+        gamma, beta = _film(c, ar, rows, 1 if ar.fault == 'film_next' else 0)
+        t = ar.fma(gamma, t, beta)
+    zero = torch.zeros((), dtype=ar.dtype)
+    return {'mean': torch.where(valid, mu, zero), 'rstd': torch.where(valid, rs, zero), 'y': torch.where(valid[:, None], t, zero)}
+
+
+def ln_backward(c, z, mean, rstd, ar=F64):
+    """dz, da, the five channel sums (on their bases) of the whole case, from the z / mean / rstd the kernel is handed"""
+    B, N, C = c['B'], c['N'], c['C']
+    rows = all_rows(c)
+    valid = valid_rows(c, rows, ar.fault == 'no_halo')
+    zero = torch.zeros((), dtype=ar.dtype)
+    mean, rstd = ar.t(mean).reshape(-1), ar.t(rstd).reshape(-1)
+    if ar.fault == 'neighbour_stats':
+        mean, rstd = torch.roll(mean, -1), torch.roll(rstd, -1)
+    z = torch.where(valid[:, None], ar.t(z).reshape(-1, C), zero)
+    dy = torch.where(valid[:, None], ar.t(c['dy']).reshape(-1, C), zero)
+    mu, rs = torch.where(valid, mean, zero)[:, None], torch.where(valid, rstd, zero)[:, None]
+    w, bias = ar.t(c['w']), ar.t(c['b'])
+    xh = ar.note('xh', (z - mu) * rs)
+    ln = ar.note('ln', ar.fma(xh, w, bias))
+    post = ar.t(keep_factors(c['seed_post'], c['seed_offset'], rows.numpy(), C, c['p_post'])) if c['p_post'] else None
+    d = dy
+    out = {}
+    shape = (B, N, C)
+    if c['film'] is not None:
+        t_fg = d * ln if post is None else d * ln * post
+        base = ar.t(c['base_dfilm'])
+        out['dfilm_gamma'] = ar.note('dfilm_gamma', ar.colsum(t_fg.reshape(shape), base[:, :C], shape, True), (t_fg, base[:, :C]))
+        out['dfilm_beta'] = ar.note('dfilm_beta', ar.colsum(d.reshape(shape), base[:, C:2 * C], shape, True), (d, base[:, C:2 * C]))
+        d = d * _film(c, ar, rows)[0]
+    if post is not None:
+        d = d * post
+    ar.note('d', d)
+    t_w = d * xh
+    out['dw'] = ar.note('dw', ar.colsum(t_w.reshape(shape), ar.t(c['base_dw']), shape, False), (t_w, ar.t(c['base_dw'])))
+    out['dbias'] = ar.note('dbias', ar.colsum(d.reshape(shape), ar.t(c['base_dbias']), shape, False), (d, ar.t(c['base_dbias'])))
+    g = ar.note('g', d * w)
+    s1 = ar.note('s1', ar.rowsum(g, which='s1') * (1.0 / C), (g, None))[:, None]
+    s2 = ar.note('s2', ar.rowsum(g, xh, which='s2') * (1.0 / C), (ar.note('g_xh', g * xh), None))[:, None]
+    ar.note('xh_s2', xh * s2)
+    dz = ar.note('dz', rs * ar.fma(-xh, s2, g - s1))
+    if c['relu_mask']:
+        dz = torch.where((z >= 0) if ar.fault == 'relu_ge' else (z > 0), dz, zero)
+    out['dz'] = dz.reshape(shape)
+    da = dz
+    if c['p_pre']:
+        shift = 1 if ar.fault == 'pre_mask_row1' else 0
+        da = dz * ar.t(keep_factors(c['seed_pre'], c['seed_offset'], (rows + shift).numpy(), C, c['p_pre']))
+    out['da'] = ar.note('da', da).reshape(shape)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# bounds
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def z_bound(c, rows):
+    """|z_dev - z| of the write-back: one rounding for the keep factor, one for the residual add; 0 where z is a or zero"""
+    C = c['C']
+    rows = torch.as_tensor(rows, dtype=torch.long)
+    a = c['a'].reshape(-1, C)[rows].double()
+    bound = torch.zeros_like(a)
+    t = a
+    if c['p_pre']:
+        t = a * keep_factors(c['seed_pre'], c['seed_offset'], rows.numpy(), C, c['p_pre'])
+        bound = U * t.abs()
+    if c['res'] is not None:
+        bound = bound + U * (t + c['res'].reshape(-1, C)[rows].double()).abs()
+    return torch.where(valid_rows(c, rows)[:, None], bound, torch.zeros_like(bound))
+
+
+def stage_bounds(c, rows, z, n, store16=None):
+    """bounds of mean, rstd, y for ln_stage(c, rows, z) evaluated in fp32 through a tree with n roundings"""
+    C = c['C']
+    rows = torch.as_tensor(rows, dtype=torch.long)
+    valid = valid_rows(c, rows)
+    z = torch.where(valid[:, None], cpu(z, torch.float64), torch.zeros((), dtype=torch.float64))
+    mu = z.mean(-1)
+    d = z - mu[:, None]
+    var = (d * d).mean(-1)
+    rs = 1.0 / torch.sqrt(var + EPS)
+    dmu = (n + 1) * U * z.abs().mean(-1)
+    rel_var = ((n + 4) * U * var + (dmu + U * d.abs().max(-1).values) ** 2) / (var + EPS) + 2 * U
+    rel_rs = 0.5 * rel_var + 4 * U
+    w, b = c['w'].double(), c['b'].double()
+    t = d * rs[:, None] * w + b
+    bt = w.abs() * rs[:, None] * (dmu[:, None] + d.abs() * (rel_rs[:, None] + 4 * U)) + 2 * U * t.abs() + U * b.abs()
+    if c['p_post']:
+        f = keep_factors(c['seed_post'], c['seed_offset'], rows.numpy(), C, c['p_post'])
+        t = t * f
+        bt = bt * f + U * t.abs()
+    if c['film'] is not None:
+        gamma, beta = _film(c, F64, rows)
+        bt = gamma.abs() * bt + U * (gamma * t).abs() + U * (gamma * t + beta).abs()
+        t = gamma * t + beta
+    if store16:
+        bt = bt + U_H[store16] * t.abs() + SUB_H[store16]
+    zero = torch.zeros((), dtype=torch.float64)
+    return {'mean': torch.where(valid, dmu + U * mu.abs(), zero), 'rstd': torch.where(valid, rs * rel_rs, zero),
+            'y': torch.where(valid[:, None], bt, zero)}
+
+
+def backward_bounds(c, z, mean, rstd, n, chains=None, store=True):
+    """bounds of ln_backward's outputs, for an fp32 evaluation through a row tree with n roundings and channel-sum chains ``chains``
+    = (all rows, per utterance); default: those of dx_ln_bwd at this shape"""
+    B, N, C = c['B'], c['N'], c['C']
+    rows = all_rows(c)
+    valid = valid_rows(c, rows)
+    zero = torch.zeros((), dtype=torch.float64)
+    z = torch.where(valid[:, None], cpu(z, torch.float64).reshape(-1, C), zero)
+    dy = torch.where(valid[:, None], c['dy'].double().reshape(-1, C), zero)
+    mu = torch.where(valid, cpu(mean, torch.float64).reshape(-1), zero)[:, None]
+    rs = torch.where(valid, cpu(rstd, torch.float64).reshape(-1), zero)[:, None]
+    w, bias = c['w'].double(), c['b'].double()
+    xh = (z - mu) * rs
+    post = keep_factors(c['seed_post'], c['seed_offset'], rows.numpy(), C, c['p_post']) if c['p_post'] else 1.0
+    chain_all, chain_b = chains or (bwd_chain(B, N, C, False), bwd_chain(B, N, C, True))
+    out = {}
+    d = dy
+    mags = lambda t: t.abs().reshape(B, N, C)
+    if c['film'] is not None:
+        base = c['base_dfilm'].double()
+        m_fg = mags(dy.abs() * ((xh * w).abs() + bias.abs()) * post)
+        out['dfilm_gamma'] = (chain_b + TERM_ROUNDINGS) * U * m_fg.sum(1) + chain_b * U * base[:, :C].abs()
+        out['dfilm_beta'] = (chain_b + TERM_ROUNDINGS) * U * mags(dy).sum(1) + chain_b * U * base[:, C:2 * C].abs()
+        d = d * _film(c, F64, rows)[0]
+    d = d * post
+    out['dw'] = (chain_all + TERM_ROUNDINGS) * U * mags(d * xh).sum((0, 1)) + chain_all * U * c['base_dw'].double().abs()
+    out['dbias'] = (chain_all + TERM_ROUNDINGS) * U * mags(d).sum((0, 1)) + chain_all * U * c['base_dbias'].double().abs()
+    g = d * w
+    s2 = (g * xh).mean(-1, keepdim=True)
+    dz = rs * (g - g.mean(-1, keepdim=True) - xh * s2)
+    bz = rs * U * (4 * g.abs() + (n + 4) * g.abs().mean(-1, keepdim=True)
+                   + xh.abs() * ((n + 8) * (g * xh).abs().mean(-1, keepdim=True) + 3 * s2.abs())) + 2 * U * dz.abs()
+    if c['relu_mask']:
+        bz = torch.where(z > 0, bz, zero)
+        dz = torch.where(z > 0, dz, zero)
+    ba = bz
+    da = dz
+    if c['p_pre']:
+        f = keep_factors(c['seed_pre'], c['seed_offset'], rows.numpy(), C, c['p_pre'])
+        da = dz * f
+        ba = bz * f + U * da.abs()
+    if c['io16'] and store:                            # (store False: the fp32 value before a 16-bit store, for between16)
+        bz, ba = bz + U_H[c['io16']] * dz.abs() + SUB_H[c['io16']], ba + U_H[c['io16']] * da.abs() + SUB_H[c['io16']]
+    out['dz'], out['da'] = bz.reshape(B, N, C), ba.reshape(B, N, C)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# comparison
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def worst_ratio(got, ref, bound):
+    """(largest |got - ref| / bound, its index).  A zero bound demands equality; NaN or a breach of a zero bound gives inf."""
+    got, ref = cpu(got, torch.float64), cpu(ref, torch.float64)
+    bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(ref)
+    err = (got - ref).abs()
+    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, math.inf)))
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    if r.numel() == 0:
+        return 0.0, ()
+    i = int(r.reshape(-1).argmax())
+    return float(r.reshape(-1)[i]), tuple(int(v) for v in np.unravel_index(i, tuple(r.shape))) if r.dim() else ()
+
+
+def between16(got16, ref, bound32, mode):
+    """elements of a 16-bit-stored result outside [RNE16(ref - bound32), RNE16(ref + bound32)].  Rounding is monotone, so the stored
+    rounding of any fp32 value within bound32 of ref lies inside; where both ends round to the same 16-bit number - most elements - the
+    device must hold exactly that number, so an fp32-level error shows wherever it moves a value across a 16-bit rounding boundary,
+    which the u_h |value| bound alone cannot see."""
+    ref = cpu(ref, torch.float64)
+    b = torch.as_tensor(bound32, dtype=torch.float64).expand_as(ref)
+    lo, hi = (ref - b).float().to(H16[mode]).double(), (ref + b).float().to(H16[mode]).double()
+    g = cpu(got16, torch.float64)
+    return int(((g < lo) | (g > hi) | torch.isnan(g)).sum())
+
+
+def bits_equal(a, b):
+    a, b = cpu(a).contiguous(), cpu(b).contiguous()
+    assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype, a.shape, b.shape)
+    view = {4: torch.int32, 2: torch.int16}[a.element_size()]
+    return bool(torch.equal(a.view(view), b.view(view)))
+
+
+def first_difference(a, b):
+    a, b = cpu(a, torch.float64), cpu(b, torch.float64)
+    i = ((a != b) | torch.isnan(a)).nonzero()
+    return 'equal' if len(i) == 0 else f'{len(i)} differ, first at {i[0].tolist()}: {float(a[tuple(i[0])])!r} vs {float(b[tuple(i[0])])!r}'
+
+
+def representable(t, dtype=torch.float32):
+    t = cpu(t, torch.float64)
+    return bool((t.to(dtype).double() == t).all())
+
+
+def order_free(terms, base=None):
+    """True when every partial sum of the terms (and the base), in any order, is an fp32 number: with 2^-k the common granularity,
+    sum |terms| 2^k < 2^24.  terms: (rows, C) summed over the rows (the worst case: all rows meet on one address)."""
+    t = cpu(terms, torch.float64).reshape(-1, terms.shape[-1])
+    allv = t if base is None else torch.cat([t, cpu(base, torch.float64).reshape(-1, terms.shape[-1])])
+    for k in range(0, 24):
+        if bool(((allv * 2.0 ** k) == (allv * 2.0 ** k).round()).all()):
+            return float((allv.abs().sum(0) * 2.0 ** k).max()) < 2.0 ** 24
+    return False
+
+
+def rne16(t, mode):
+    return cpu(t).to(H16[mode])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# inputs
+# ---------------------------------------------------------------------------------------------------------------------------------------
+KINDS = ('randn', 'offset', 'tiny', 'relu', 'outlier')
+BIG_LENS = [257, 256, 193, 192, 191, 64, 1, 0] * 8
+FF_LENS = [300, 252, 126, 127, 40, 1]
+SHAPES = {
+    'c128': dict(B=3, N=70, C=128, lens=[70, 65, 1]),                       # 4 waves, 64-row blocks + a 6-row tail
+    'c1024': dict(B=3, N=70, C=1024, lens=[70, 65, 1], halo=2),             # 32-row blocks
+    'c1024_bf16': dict(B=3, N=70, C=1024, lens=[70, 65, 1], halo=2, io16='bf16'),
+    'c1024_fp16': dict(B=3, N=70, C=1024, lens=[70, 65, 1], halo=2, io16='fp16'),
+    'big': dict(B=64, N=257, C=128, lens=BIG_LENS),                         # 16 waves: 192 + 65 rows
+}
+WRAP = dict(B=129, N=255)                                                    # 32 895 rows: the forward's second grid-stride pass
+
+
+def wrap_lens():
+    lens = ([255, 254, 128, 1, 200] * 26)[:WRAP['B']]
+    lens[-2:] = [250, 255]                                                   # the rows of the second pass are computed rows
+    return lens
+
+
+def wrap_rows():
+    """the rows of the wrap case that are restated: the first 64, from 32 700 to the end, and 64 random ones in between"""
+    total = WRAP['B'] * WRAP['N']
+    mid = torch.randint(64, 32700, (64,), generator=torch.Generator().manual_seed(3))
+    return torch.unique(torch.cat([torch.arange(64), mid, torch.arange(32700, total)]))
+
+
+def _base_case(B, N, C, lens, halo, io16, seed):
+    g = torch.Generator().manual_seed(1000 + seed)
+    return g, dict(B=B, N=N, C=C, lens=None if lens is None else list(lens), halo=halo, io16=io16, ld_film=2 * C + 4,
+                   seed_pre=0x1234_5678_9ABC_DEF0 + seed, seed_post=0x0FED_CBA9_8765_4321 + seed, seed_offset=77 + seed, relu_mask=0)
+
+
+OFFSET = 100.0
+OFFSET_SIGMA = {None: 0.01, 'fp16': 0.25, 'bf16': 2.0}      # a 16-bit type cannot hold sigma 0.01 at 100: its spacing there is 1/16 (fp16), 1/2 (bf16)
+
+
+def rounded_case(kind, B, N, C, lens, halo=0, io16=None, film=None, seed=0, with_dy=True):
+    """inputs of the rounded tier, named after the z the LayerNorm gets.  kind: 'randn'; 'offset' (mean 100, sigma about 0.01: the offset
+    rides in the residual, which no dropout touches, a = 0.01 randn under the pre-dropout; 16-bit rows: 100 + sigma randn with the sigma
+    the type can hold, OFFSET_SIGMA); 'tiny' (1e-4 randn); 'relu' (relu(randn), exact zeros, backward with relu_mask, no FiLM unless
+    asked for: the prenet's rows); 'outlier' (1 % of the elements x 300).  fp32 rows get a residual, p_pre = 0.1 and p_post = 0.2; 16-bit
+    rows and the ReLU'd rows are handed over as z (no residual, no pre-dropout), so that the z the kernel normalises is the z that is
+    stored.  kind_stats() says what each kind's z must look like; tests/test_ln_exact_cpu.py asserts it."""
+    g, c = _base_case(B, N, C, lens, halo, io16, seed)
+    film = (kind != 'relu') if film is None else film
+    r = lambda *s: torch.randn(*s, generator=g)
+    scale = {'randn': 1.0, 'offset': OFFSET_SIGMA[io16], 'tiny': 1e-4, 'relu': 1.0, 'outlier': 1.0}[kind]
+    a = r(B, N, C) * scale
+    if kind == 'offset' and io16:
+        a = a + OFFSET
+    if kind == 'relu':
+        a = a.clamp_min(0)
+    if kind == 'outlier':
+        a = torch.where(torch.rand(B, N, C, generator=g) < 0.01, a * 300, a)
+    plain = io16 is not None or kind == 'relu'
+    res = None if plain else 0.5 * scale * r(B, N, C) + (OFFSET if kind == 'offset' else 0.0)
+    c.update(kind=kind, a=a, res=res, p_pre=0.0 if plain else 0.1, p_post=0.2,
+             w=1 + 0.1 * r(C), b=0.1 * r(C), relu_mask=int(kind == 'relu'))
+    c['film'] = torch.cat([1 + 0.3 * r(B, C), 0.3 * r(B, C)], 1) if film else None
+    if with_dy:
+        c['dy'] = r(B, N, C)
+        c.update(base_dw=dyadic(g, (C,), 64, 16), base_dbias=dyadic(g, (C,), 64, 16), base_dfilm=dyadic(g, (B, 2 * C), 64, 16))
+    if io16:
+        for k in ('a', 'dy'):
+            if k in c:
+                c[k] = c[k].to(H16[io16])
+    return c
+
+
+def kind_stats(c):
+    """((lo, hi) of the row mean, (lo, hi) of the row standard deviation) that the z of this case's kind must show on every computed row"""
+    s = OFFSET_SIGMA[c['io16']]
+    return {'randn': ((-0.5, 0.5), (0.7, 1.5)), 'offset': ((OFFSET - 0.5 * s, OFFSET + 0.5 * s), (0.7 * s, 1.6 * s)),
+            'tiny': ((-5e-5, 5e-5), (0.7e-4, 1.5e-4)), 'relu': ((0.15, 0.65), (0.3, 0.85)), 'outlier': ((-25.0, 25.0), (0.8, 200.0))}[c['kind']]
+
+
+def dyadic(g, shape, span, den):
+    """integers in [-span, span] over den (a power of two)"""
+    return torch.randint(-span, span + 1, shape, generator=g).float() / den
+
+
+def pick(g, shape, values):
+    return torch.tensor(values, dtype=torch.float32)[torch.randint(0, len(values), shape, generator=g)]
+
+
+def exact_bwd_case(B, N, C, lens, halo=0, io16=None, film=True, p_pre=0.5, p_post=0.75, relu_mask=0, seed=0):
+    """the exact backward tier: integer z in [-4, 4] and dy in [-3, 3], planted integer mean in [-2, 2] and rstd in {0.5, 1, 2}, w and gamma in
+    {+-0.5, +-1, +-2}, dyadic b and beta, p in {0, 0.5, 0.75} (inv_keep 1, 2, 4): every product and every sum is an fp32 number in any order.
+    Padded rows of z, dy, mean, rstd hold NaN: nothing may read them."""
+    g, c = _base_case(B, N, C, lens, halo, io16, seed)
+    ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, generator=g).float()
+    pm = [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0]
+    c.update(kind='exact', z=ri(-4, 4, B, N, C), dy=ri(-3, 3, B, N, C), mean=ri(-2, 2, B, N), rstd=pick(g, (B, N), [0.5, 1.0, 2.0]),
+             w=pick(g, (C,), pm), b=dyadic(g, (C,), 16, 8), p_pre=p_pre, p_post=p_post, relu_mask=relu_mask, res=None,
+             film=torch.cat([pick(g, (B, C), pm), dyadic(g, (B, C), 16, 8)], 1) if film else None,
+             base_dw=dyadic(g, (C,), 64, 16), base_dbias=dyadic(g, (C,), 64, 16), base_dfilm=dyadic(g, (B, 2 * C), 64, 16))
+    c['a'] = c['z']
+    pad = ~valid_rows(c, all_rows(c)).reshape(B, N)
+    for k in ('z', 'dy', 'mean', 'rstd'):
+        c[k][pad] = float('nan')
+    if io16:
+        c['z'], c['dy'] = c['z'].to(H16[io16]), c['dy'].to(H16[io16])
+    return c
+
+
+def exact_fwd_case(B, N, C, lens, halo=0, p_pre=0.5, res=True, film=True, seed=0):
+    """exact forward facts: dyadic a and res (eighths) with p_pre in {0.5, 0.75} make z = drop(a) + res an fp32 number whose row sums are
+    exact; the last channel of every row is then set so that the row of z sums to a multiple of C (through res, or a itself), so the mean
+    is an integer computed without rounding."""
+    g, c = _base_case(B, N, C, lens, halo, None, seed)
+    a = torch.randint(-8, 9, (B, N, C), generator=g).float()
+    r = torch.randint(-8, 9, (B, N, C), generator=g).float() if res else None
+    c.update(kind='exact_fwd', a=a, res=r, p_pre=p_pre if res else 0.0, p_post=0.0, w=pick(g, (C,), [-2.0, -1.0, -0.5, 0.5, 1.0, 2.0]),
+             b=dyadic(g, (C,), 16, 8), film=torch.cat([pick(g, (B, C), [-2.0, -1.0, 0.5, 1.0]), dyadic(g, (B, C), 16, 8)], 1) if film else None)
+    z, _ = make_z(c, all_rows(c))
+    (r if res else a).reshape(-1, C)[:, -1] -= (z.sum(-1) % C).float()       # (the residual is not dropped out: the fix survives)
+    return c
+
+
+EXACT_BWD = {
+    'c128_w4': dict(B=3, N=70, C=128, lens=[70, 65, 1]),
+    'c128_w16': dict(B=64, N=257, C=128, lens=BIG_LENS),
+    'c128_16383': dict(B=1, N=16383, C=128, lens=[16380]),
+    'c128_16384': dict(B=1, N=16384, C=128, lens=[16380]),
+    'c1024_f32': dict(B=3, N=70, C=1024, lens=[70, 65, 1], halo=2, relu_mask=1),
+    'c1024_bf16': dict(B=3, N=70, C=1024, lens=[70, 65, 1], halo=2, relu_mask=1, io16='bf16'),
+    'c1024_fp16': dict(B=3, N=70, C=1024, lens=[70, 65, 1], halo=2, relu_mask=1, io16='fp16'),
+    'ff_62': dict(B=5, N=300, C=128, lens=FF_LENS[1:]),                      # 5 utterances: 62-token tiles
+    'ff_126': dict(B=35, N=300, C=128, lens=(FF_LENS * 6)[:35]),             # 35 utterances: 126-token tiles
+}
+EXACT_P = ((0.5, 0.75), (0.0, 0.0), (0.75, 0.5))
+
+
+def expected16(c, t):
+    """a float64 result as the kernel stores it in this case's row type"""
+    return cpu(t, torch.float32) if not c['io16'] else cpu(t, torch.float32).to(H16[c['io16']])
+
+
+def correctly_rounded_rstd(z):
+    """the fp32 chain var + eps, sqrt, 1 / x with every step correctly rounded, on rows whose mean and sum of squares are exact"""
+    z = cpu(z, torch.float64)
+    d = z - z.mean(-1, keepdim=True)
+    var = ((d * d).sum(-1) / z.shape[-1]).numpy().astype(np.float32)
+    return torch.from_numpy(np.float32(1.0) / np.sqrt(var + np.float32(1e-5)))
