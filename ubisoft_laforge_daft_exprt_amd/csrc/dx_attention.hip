@@ -12,6 +12,12 @@
 // no LDS round trip for P.  dK/dV kernel: a workgroup = 64 keys, 4 waves x 16 keys, looping over 64-query tiles; there the
 // scores are computed as S = Q K^T so that P / dS registers are the B operand of dV^T += dO^T P and dK^T += Q^T dS.
 // All accumulation is fp32; exp / log are the fp32 libm forms.
+//
+// Padded rows (len <= row < N of an utterance): the kernels LOAD them (a 64-row tile is staged whole, and a padded query of a partly valid
+// tile runs the loops on its own row) and keep them out of every result by selects: the forward masks a padded key's score to -inf
+// before the maximum, the backward sets its p to 0 after the exp, padded queries are stored as zeros, and dctx is zero on them by the
+// caller's contract.  So no output depends on what qkv holds there AS LONG AS IT IS FINITE (tests/test_attn_exact_gpu.py compares
+// bitwise against zeros there, values up to +-1e4).  NaN / Inf there are not supported: they reach the MFMAs as 0 * NaN (P V, dS K).
 #include "dx_common.h"
 #include <algorithm>
 #include <type_traits>
@@ -292,10 +298,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
     }
   }
   if (qrow < a.N) {
-    const float z = qrow < len ? 1.f : 0.f;
+    // a select, not a product with 0: a padded query of a partly valid tile ran the loop on its own row against lse = 0, and where that
+    // row's scores pass 88 its p is inf and its dq inf * 0 = NaN (tests/test_attn_exact_gpu.py: padded rows, 'underflow')
+    const bool valid = qrow < len;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
-      *reinterpret_cast<float4*>(out + dt * 16 + g * 4) = make_float4(dq[dt][0] * z, dq[dt][1] * z, dq[dt][2] * z, dq[dt][3] * z);
+      *reinterpret_cast<float4*>(out + dt * 16 + g * 4) =
+          make_float4(valid ? dq[dt][0] : 0.f, valid ? dq[dt][1] : 0.f, valid ? dq[dt][2] : 0.f, valid ? dq[dt][3] : 0.f);
   }
 }
 
@@ -607,10 +616,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split_kernel(const AttnBwd
     }
   }
   if (qrow < a.N) {
-    const float z = qrow < len ? 1.f : 0.f;
+    // a select, not a product with 0: a padded query of a partly valid tile ran the loop on its own row against lse = 0, and where that
+    // row's scores pass 88 its p is inf and its dq inf * 0 = NaN (tests/test_attn_exact_gpu.py: padded rows, 'underflow')
+    const bool valid = qrow < len;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
-      *reinterpret_cast<float4*>(out + dt * 16 + g * 4) = make_float4(dq[dt][0] * z, dq[dt][1] * z, dq[dt][2] * z, dq[dt][3] * z);
+      *reinterpret_cast<float4*>(out + dt * 16 + g * 4) =
+          make_float4(valid ? dq[dt][0] : 0.f, valid ? dq[dt][1] : 0.f, valid ? dq[dt][2] : 0.f, valid ? dq[dt][3] : 0.f);
   }
 }
 
@@ -1188,10 +1200,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_bf16_kernel(const AttnBwdA
     }
   }
   if (qrow < a.N) {
-    const float z = qrow < len ? QSCALE : 0.f;
+    const bool valid = qrow < len;                      // a select: see attn_bwd_dq_kernel
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
-      store4(out + dt * 16 + g * 4, dq[dt][0] * z, dq[dt][1] * z, dq[dt][2] * z, dq[dt][3] * z);
+      store4(out + dt * 16 + g * 4, valid ? dq[dt][0] * QSCALE : 0.f, valid ? dq[dt][1] * QSCALE : 0.f, valid ? dq[dt][2] * QSCALE : 0.f,
+             valid ? dq[dt][3] * QSCALE : 0.f);
   }
 }
 
