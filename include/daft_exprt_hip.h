@@ -655,6 +655,24 @@ int dx_wn_adamw(const void* table, int njobs, int blocks, double lr, double beta
 /* W of every weight-normed job from its stored v and g, through the step's own fold code (the same bits); plain jobs are skipped */
 int dx_wn_fold(const void* table, int njobs, int blocks, void* stream);
 
+/* ---- HiFi-GAN fine-tuning batches from a device-resident corpus (reference vocoder/dataset.py:118-148; csrc/dx_finetune_data.hip) ----
+ * The corpus: wav, every utterance's int16 samples (utterance u at wav + wav_off[u], wav_len[u] samples; every offset a multiple of 8
+ * and the buffer padded to one, so that 16-byte loads stay inside it), and mel, every utterance's predicted mel as (n_mels, mel_len[u])
+ * fp32 at mel + mel_off[u]; n_utt utterances.  One launch assembles B rows:
+ *   utterance of row b: utts[b], or order[order_pos + b] when utts is NULL (order holds n_order entries);
+ *   start frame of row b: starts_in[b], or, when starts_in is NULL, 0 for an utterance shorter than segment_size samples and otherwise
+ *     (uint64(r >> 32) * n) >> 32 with r = dx_rand64(seed, counter | (by_utt ? utterance : b)) and n = mel_len - fps: a value of
+ *     [0, mel_len - fps - 1], the range of the reference's randint;
+ *   y[b][i] = wav[start * hop_size + i] / 32768 (exact) and x[b][c][f] = mel[c][start + f], i < segment_size, f < fps; samples and frames
+ *     at or past the utterance's own length are 0 (torch's F.pad of a short utterance) and are never read.
+ * starts_out, utts_out (optional, int32 [B]) receive what the row used.  An utterance index outside [0, n_utt) gives a row of zeros.
+ * segment_size = fps * hop_size, hop_size % 8 == 0; wav and y 16-byte aligned.  Vector stores only, no atomics, no workspace: a row's
+ * bits depend on its own (utterance, start) alone. */
+int dx_ft_batch(const short* wav, const long* wav_off, const int* wav_len, const float* mel, const long* mel_off, const int* mel_len,
+                int n_utt, const int* utts, const int* order, long order_pos, long n_order, const int* starts_in, uint64_t seed,
+                uint64_t counter, int by_utt, float* x, float* y, int* starts_out, int* utts_out, int B, int segment_size, int hop_size,
+                int fps, int n_mels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

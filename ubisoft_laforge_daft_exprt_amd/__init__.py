@@ -19,3 +19,4 @@ from .discriminators import (DiscriminatorP, DiscriminatorS, HiFiGanDiscriminato
                              MultiScaleDiscriminator, discriminator_loss, feature_loss, generator_loss)
 from .vocoder_optim import NormedAdamW  # noqa: F401
 from .vocoder_finetune import HiFiGanFineTuner  # noqa: F401
+from .vocoder_data import HiFiGanFineTuneData  # noqa: F401

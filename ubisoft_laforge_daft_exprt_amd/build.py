@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libdaft_exprt_hip.so')
-SOURCES = ['dx_runtime.hip', 'dx_gemm.hip', 'dx_ffpair.hip', 'dx_attention.hip', 'dx_rows.hip', 'dx_upsample.hip', 'dx_loss.hip', 'dx_optim.hip', 'dx_pitch.hip', 'dx_vocoder.hip', 'dx_vocoder_bwd.hip', 'dx_mel.hip', 'dx_prosody.hip', 'dx_disc.hip', 'dx_disc_bwd.hip', 'dx_disc_wgrad.hip', 'dx_griffin_lim.hip', 'dx_vocoder_optim.hip']
+SOURCES = ['dx_runtime.hip', 'dx_gemm.hip', 'dx_ffpair.hip', 'dx_attention.hip', 'dx_rows.hip', 'dx_upsample.hip', 'dx_loss.hip', 'dx_optim.hip', 'dx_pitch.hip', 'dx_vocoder.hip', 'dx_vocoder_bwd.hip', 'dx_mel.hip', 'dx_prosody.hip', 'dx_disc.hip', 'dx_disc_bwd.hip', 'dx_disc_wgrad.hip', 'dx_griffin_lim.hip', 'dx_vocoder_optim.hip', 'dx_finetune_data.hip']
 F16_SOURCES = ['dx_gemm.hip', 'dx_ffpair.hip', 'dx_attention.hip', 'dx_rows.hip', 'dx_pitch.hip']    # compiled a second time with -DDX_F16 (fp16 operand mode)
 FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wno-unused-value', '-Wno-unused-result'] + os.environ.get('DX_EXTRA_HIPCC_FLAGS', '').split()
 

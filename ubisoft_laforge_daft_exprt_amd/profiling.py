@@ -272,6 +272,8 @@ def price(name, a, geom: Geometry):
         frames = geom.rows(a['B'], a['T_max'])
         flops = 2.0 * frames * 2 * (1024 * 2 * a['kmax'] + a['kmax'] * a['n_mels'])
         return 'mel_bwd<f32>', 'mfma', flops, frames * (2 * 256 * 4 + a['n_mels'] * 4)
+    if name == 'dx_ft_batch':                            # per row: int16 samples read, fp32 samples written, the mel crop read and written
+        return 'ft_batch', 'hbm', None, a['B'] * (a['segment_size'] * (2 + 4) + a['n_mels'] * a['fps'] * 2 * 4)
     if name in ('dx_mel_pack', 'dx_mel_bwd_pack'):
         return name[3:], 'hbm', None, a['n_mels'] * a['n_freq'] * 4 + (2 * 1024 + a['n_mels']) * a['kmax'] * 4
     if name == 'dx_symbol_prosody':                      # two frame rows in, int64 durations in, two symbol rows out

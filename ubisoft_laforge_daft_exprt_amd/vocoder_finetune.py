@@ -1,5 +1,5 @@
-"""The HiFi-GAN fine-tuning loop on gfx950 (reference vocoder/finetune_hifigan.py:119-319 without the data loader and TensorBoard):
-one call per step, checkpoints in the reference's layout.
+"""The HiFi-GAN fine-tuning loop on gfx950 (reference vocoder/finetune_hifigan.py:119-319 without TensorBoard): one call per step,
+``fit`` for the loop around it on the device-resident data of vocoder_data.py, checkpoints in the reference's layout.
 
 ``train_step`` runs the reference's order (lines 203-245): the generator forward once and the mel of ``y_g_hat``; the discriminator
 step on ``y_g_hat.detach()``; the generator step against the stepped discriminators.  Every gradient is this package's HIP; weight
@@ -10,14 +10,16 @@ spectral-normed layers keep torch's ``W / sigma`` backward and fold (sigma's gra
 Stated deviations from the reference: an optimiser state that does not fit raises ``ValueError`` (the reference starts fresh silently);
 ``disc_checkpoint=None`` raises (this package has no initialiser for the discriminators); ``step`` continues from the checkpoint's
 ``steps`` (the reference restarts its count at 0); ``epoch`` counts the ``end_epoch()`` calls, which is what the reference has written
-into its final checkpoint, and a restored tuner's learning rates are ``initial_lr * lr_decay ** epoch``.
+into its final checkpoint, and a restored tuner's learning rates are ``initial_lr * lr_decay ** epoch``; a checkpoint ``fit`` writes
+mid-pass therefore holds the completed passes, where the reference writes the 1-based pass in progress.
 
-Not built: graph capture of the step, bf16 operands, more than one GPU, writing the operand packs from the
-optimiser kernel, the data set and its loader, TensorBoard.
+Not built (DESIGN.md sections 19 and 20): graph capture of the step, bf16 operands, more than one GPU, writing the operand packs from
+the optimiser kernel, TensorBoard.
 """
 from __future__ import annotations
 
 import os
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -34,6 +36,14 @@ LOSS_NAMES = ('loss_disc_f', 'loss_disc_s', 'loss_gen_f', 'loss_gen_s', 'loss_fm
 class StepLosses(DeviceDict):
     """The seven losses of one step, one fp32 device vector until somebody looks (then ONE host transfer)."""
     KEYS = LOSS_NAMES
+
+
+class FitResult(NamedTuple):
+    """What ``HiFiGanFineTuner.fit`` did: the steps it ran, the last step's losses (None if it ran none; still on the device) and the
+    validation mel errors by step count."""
+    steps: int
+    losses: Optional[StepLosses]
+    validation: Dict[int, float]
 
 
 def _layers(prefix, module):
@@ -161,5 +171,37 @@ class HiFiGanFineTuner:
                         'optim_d': optim(self.optim_d.state_dict()), 'steps': self.step, 'epoch': self.epoch}, paths[1])
         return paths
 
+    def fit(self, data, training_steps, output_dir=None, validation_interval=1000, checkpoint_interval=1000, save_disc=False,
+            log=None) -> FitResult:
+        """Lines 196-319 around ``train_step``: until ``step`` reaches ``training_steps``, one step on ``data.batch(step)``
+        (vocoder_data.HiFiGanFineTuneData: a function of ``(seed, step)``, nothing crosses the host); ``end_epoch()`` when the step count
+        reaches a multiple of ``data.steps_per_epoch``; ``validate(data.val_batches())`` every ``validation_interval`` steps; with an
+        ``output_dir``, ``save_checkpoint`` every ``checkpoint_interval`` steps and at the end.  ``log(step, StepLosses)`` is called
+        after every step; the losses cross to the host only if it reads them.  A 0 interval turns its action off.
 
-__all__ = ['HiFiGanFineTuner', 'StepLosses', 'LOSS_NAMES']
+        ``epoch`` counts completed passes in every checkpoint written here: at a pass boundary ``end_epoch()`` comes first, and a
+        partial last pass is closed (the reference steps its schedulers after the ``break`` too) only AFTER the final checkpoint.  So
+        a new tuner made from the files of ``fit(k)`` and run to ``N`` with the same ``data`` is bitwise the tuner of ``fit(N)``.  A
+        checkpoint saved by hand after a ``fit`` that ended mid-pass already counts that pass, and does not resume exactly."""
+        per_pass = int(data.steps_per_epoch)
+        ran, losses, validation, saved = 0, None, {}, None
+        while self.step < training_steps:
+            losses = self.train_step(*data.batch(self.step)[:3])
+            ran += 1
+            if log is not None:
+                log(self.step, losses)
+            if self.step % per_pass == 0:
+                self.end_epoch()
+            if validation_interval and self.step % validation_interval == 0:
+                validation[self.step] = self.validate(data.val_batches())
+            if output_dir is not None and checkpoint_interval and self.step % checkpoint_interval == 0:
+                self.save_checkpoint(output_dir, save_disc)
+                saved = self.step
+        if output_dir is not None and saved != self.step:
+            self.save_checkpoint(output_dir, save_disc)
+        if ran and self.step % per_pass:
+            self.end_epoch()
+        return FitResult(ran, losses, validation)
+
+
+__all__ = ['HiFiGanFineTuner', 'StepLosses', 'FitResult', 'LOSS_NAMES']
