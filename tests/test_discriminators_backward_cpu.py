@@ -157,9 +157,11 @@ def test_guards_of_the_differentiable_entry_points():
 def test_a_backward_after_a_later_pass_raises():
     """The pass counter of the per-(B, T) plan: a state whose maps were overwritten is refused before anything is launched."""
     both = disc.HiFiGanDiscriminators(dh.state_dicts(), device='cpu')
-    plan = {'pass': 3}
+    plan = disc._Plan()
+    for _ in range(3):
+        plan.begin()
     with pytest.raises(RuntimeError, match='overwritten by a later pass'):
-        both._backward((plan, 2, 2, 64, [], []), torch.zeros(4))
+        both._backward(plan, 2, torch.zeros(4))
 
 
 def test_price_entries_of_the_backward():

@@ -14,8 +14,7 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 from tools.bench_vocoder import B, T_MAX  # noqa: E402
-from ubisoft_laforge_daft_exprt_amd._lib import lib  # noqa: E402
-from ubisoft_laforge_daft_exprt_amd.discriminators import _packed  # noqa: E402
+from ubisoft_laforge_daft_exprt_amd._lib import lib, packed as _packed  # noqa: E402
 
 DILATIONS = {3: (1, 2), 5: (2, 6), 7: (3, 12)}
 SCALE = {64: 64, 32: 256}

@@ -110,3 +110,22 @@ def lib() -> _Lib:
     if _LIB is None:
         _LIB = _Lib()
     return _LIB
+
+
+# What the audio modules (vocoder*.py, discriminators.py) share around a launch.
+def stream(device):
+    """-> the handle of torch's current stream on ``device``: what every entry point takes as ``stream``."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def packed(kind, w, dims, device):
+    """``dx_<kind>_pack`` of the contiguous fp32 device tensor ``w`` -> its operand pack, a uint8 device buffer of the size that
+    ``dx_<kind>_pack_size`` reports; ``dims``: the arguments the two entry points share."""
+    import torch
+    L = lib()
+    nbytes = torch.zeros(1, dtype=torch.long)
+    getattr(L, f'dx_{kind}_pack_size')(*dims, nbytes.data_ptr())
+    buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=device)
+    getattr(L, f'dx_{kind}_pack')(w.data_ptr(), buf.data_ptr(), *dims, stream(device))
+    return buf

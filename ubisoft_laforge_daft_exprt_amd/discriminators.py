@@ -7,6 +7,10 @@ reference ``do_*`` checkpoint.  ``forward(y, y_hat)`` returns ``(y_d_rs, y_d_gs,
 runs in csrc/dx_disc.hip (there is no PyTorch fallback and no CPU path), real and generated audio as one batch of 2B rows, one launch
 per layer.  The feature maps are permuted VIEWS of the kernels' channels-last buffers ((B, C, H, p) and (B, C, N)), not copies.
 
+Stated once (*One layer table*): ``layer_table`` holds a sub-discriminator's layers at one input length, and the forward, both
+backwards and the workspace query walk it; a pass lists its eight sub-discriminators once (``_Sub``), and the losses, both backwards and
+the MSD's pooled chain follow that list.  tests/test_discriminators_launches_cpu.py holds every library call to a recorded sequence.
+
 Weight folding, once and lazily (``refresh_weights()`` drops the folded copies; ``load_state_dict`` calls it):
   * weight norm (``weight_g`` / ``weight_v``): ``torch._weight_norm(v, g, 0)``;
   * spectral norm (the first MSD sub-discriminator: ``weight_orig`` / ``weight_u`` / ``weight_v``; told apart by ``weight_orig``):
@@ -29,12 +33,14 @@ synchronisation happens here).  ``HiFiGanDiscriminators.losses`` computes the si
 """
 from __future__ import annotations
 
+import functools
 import os
+from collections import namedtuple
 
 import torch
 from torch import nn
 
-from ._lib import lib
+from ._lib import lib, packed as _packed, stream as _stream
 
 LRELU_SLOPE = 0.1
 PERIODS = (2, 3, 5, 7, 11)
@@ -52,19 +58,29 @@ def conv_out(n, taps, stride, pad):
     return (n + 2 * pad - taps) // stride + 1
 
 
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+class Layer(namedtuple('Layer', 'name cin cout taps stride groups pad n_in n_out p')):
+    """One convolution of a sub-discriminator at one input length; ``name``: 'convs.<i>' or 'conv_post', the module's name in it.  Its
+    maps are channels-last, (rows, n, p, c): ``n_in`` positions of ``cin`` channels in, ``n_out`` of ``cout`` out, ``p`` columns per
+    position (the period; 1: no folding)."""
+
+    def strides(self, side):
+        """-> (batch stride, column stride, position stride) in elements of the layer's input ('in') or output ('out') map, as the
+        kernels take them: a kernel row is one column of one batch row."""
+        n, c = (self.n_in, self.cin) if side == 'in' else (self.n_out, self.cout)
+        return n * self.p * c, c, self.p * c
 
 
-def _packed(kind, w, dims, device):
-    """``dx_<kind>_pack`` of the contiguous fp32 device tensor ``w`` -> its operand pack, a uint8 device buffer of the size that
-    ``dx_<kind>_pack_size`` reports; ``dims``: the arguments the two entry points share."""
-    L = lib()
-    nbytes = torch.zeros(1, dtype=torch.long)
-    getattr(L, f'dx_{kind}_pack_size')(*dims, nbytes.data_ptr())
-    buf = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=device)
-    getattr(L, f'dx_{kind}_pack')(w.data_ptr(), buf.data_ptr(), *dims, _stream(device))
-    return buf
+@functools.lru_cache(maxsize=None)
+def layer_table(layers, T=1, p=1):
+    """The layers of one sub-discriminator (``MPD_LAYERS`` / ``MSD_LAYERS``, then ``POST``) on T samples folded by period p -> a tuple
+    of ``Layer``.  Host only; every walk over the layers (forward, both backwards, the workspace query) runs from this.  Only n_in and
+    n_out depend on T and p: where the names and shapes are all that is read, the defaults serve."""
+    table, n = [], -(-T // p)
+    for i, (cin, cout, taps, stride, groups, pad) in enumerate(layers + (POST,)):
+        name = f'convs.{i}' if i < len(layers) else 'conv_post'
+        table.append(Layer(name, cin, cout, taps, stride, groups, pad, n, conv_out(n, taps, stride, pad), p))
+        n = table[-1].n_out
+    return tuple(table)
 
 
 def _halves(t):
@@ -121,6 +137,13 @@ def fold_state_dict(state: dict) -> dict:
     return {n: (fold_weight(state, n).detach().contiguous(), state[n + '.bias'].float().detach().contiguous()) for n in layer_names(state)}
 
 
+def _below(named, prefix):
+    """The entries of ``named`` whose key starts with ``prefix``, keyed by the rest; None if ``named`` is None or holds none."""
+    if named is None:
+        return None
+    return {k[len(prefix):]: v for k, v in named.items() if k.startswith(prefix)} or None
+
+
 def _check_inputs(*xs):
     x = xs[0]
     for t in xs:
@@ -138,25 +161,45 @@ def _check_reflect(T, periods):
             raise ValueError(f'period {p}: the reflect padding ({p - T % p} samples) must be shorter than the signal ({T} samples)')
 
 
+def _require_gpu(device, what='the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels)'):
+    if device.type != 'cuda':
+        raise RuntimeError(what + '; there is no CPU path')
+
+
+def _require_frozen(modules, message, inputs=()):
+    """No parameter of ``modules`` (and none of ``inputs``) may require grad."""
+    if any(t.requires_grad for t in inputs) or any(q.requires_grad for m in modules for q in m.parameters()):
+        raise RuntimeError(message)
+
+
+def _check_run(module, *xs):
+    """The guards of the forward-only entry points."""
+    if torch.is_grad_enabled():
+        _require_frozen((module,), 'the discriminators are forward only: their backward is not built, and an input or parameter requires grad '
+                                   '(run under torch.no_grad() or detach the input)', xs)
+    _require_gpu(xs[0].device)
+
+
+def _check_forward(owner, y, y_hat):
+    """The guards of ``HiFiGanDiscriminators.losses``: forward only, as ``MultiPeriodDiscriminator.forward``."""
+    _check_run(owner.mpd, y, y_hat)
+
+
 def _check_differentiable(owner, y, y_hat):
     """The guards of the entry points that have a backward: only ``y_hat`` may require grad."""
     if y.requires_grad:
         raise RuntimeError('the discriminators\' backward goes to y_hat only: y must not require grad')
-    if any(q.requires_grad for m in (owner.mpd, owner.msd) for q in m.parameters()):
-        raise RuntimeError('the discriminators\' backward goes to y_hat only: their parameters are constants and must not require grad')
-    if y.device.type != 'cuda':
-        raise RuntimeError('the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels); there is no CPU path')
+    _require_frozen((owner.mpd, owner.msd), 'the discriminators\' backward goes to y_hat only: their parameters are constants and must not require grad')
+    _require_gpu(y.device)
 
 
-def _check_train(owner, y):
+def _check_train(owner, y, y_hat):
     """The guards of the discriminator step: the parameters stay frozen leaves (their gradients are returned, or added to ``.grad``)."""
     if owner.precision != 'f32':
         raise RuntimeError(f"HiFiGanDiscriminators: gradients exist for precision 'f32' only, got {owner.precision!r}")
-    if any(q.requires_grad for m in (owner.mpd, owner.msd) for q in m.parameters()):
-        raise RuntimeError('the discriminator step keeps the parameters frozen (requires_grad=False) and hands their gradients out itself: '
-                           'a parameter requires grad')
-    if y.device.type != 'cuda':
-        raise RuntimeError('the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels); there is no CPU path')
+    _require_frozen((owner.mpd, owner.msd), 'the discriminator step keeps the parameters frozen (requires_grad=False) and hands their gradients '
+                                            'out itself: a parameter requires grad')
+    _require_gpu(y.device)
 
 
 def _check_power_iterations(n):
@@ -193,14 +236,6 @@ def _norm_backward(conv, name, dw, db, out):
             out[name + '.weight_g'], out[name + '.weight_v'] = torch.autograd.grad(w, (g, v), dw.view_as(w))
 
 
-def _check_run(module, *xs):
-    if torch.is_grad_enabled() and (any(t.requires_grad for t in xs) or any(q.requires_grad for q in module.parameters())):
-        raise RuntimeError('the discriminators are forward only: their backward is not built, and an input or parameter requires grad '
-                           '(run under torch.no_grad() or detach the input)')
-    if xs[0].device.type != 'cuda':
-        raise RuntimeError('the HiFi-GAN discriminators run on the GPU (gfx950 HIP kernels); there is no CPU path')
-
-
 class _Arena:
     """Hands out the same buffers, in the same order, on every pass (``reset()`` starts a pass)."""
 
@@ -223,8 +258,16 @@ def _fresh(shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
+# One sub-discriminator of one pass over real + generated rows.  module: 'discriminators.<index>' of the 'mpd' / 'msd' (tag); set_id: 0
+# MPD, 1 MSD, the set of its loss rows: it reads slots 2 set_id (gen) and 2 set_id + 1 (fm) of the four generator-side upstream weights,
+# slot set_id of the two discriminator-side ones; level: its input x (2B, T_level) is the waveforms pooled that often; table: layer_table
+# of the module at T_level; score (2B, N, p); maps: the channels-last feature maps (2B, N_i, p, C_i) of convs.<i>
+_Sub = namedtuple('_Sub', 'module tag index set_id level x table score maps')
+
+
 class _SubDiscriminator(nn.Module):
     LAYERS = ()
+    period = 1
 
     def _init_layers(self, conv_cls, two_d, precision):
         if precision not in PRECISIONS:
@@ -233,36 +276,36 @@ class _SubDiscriminator(nn.Module):
         tail = (1,) if two_d else ()
         self.convs = nn.ModuleList([conv_cls((cout, cin // g, k) + tail) for cin, cout, k, _, g, _ in self.LAYERS])
         self.conv_post = conv_cls((POST[1], POST[0], POST[2]) + tail)
+        self._drop_weights()
+
+    def _drop_weights(self, folded=None):
+        """Everything derived from the weights: the forward's packs, the backward's, and the folded pairs handed in from outside."""
         self._packs = None
         self._dgrad = None
-        self._folded = None
+        self._folded = folded
 
     def refresh_weights(self, folded=None):
         """Drop the folded, packed device weights: the next forward folds the current parameters again.  ``folded``: {layer: (W, bias)}
         that the caller vouches to BE the fold of the current parameters (vocoder_optim.NormedAdamW.folded(): the optimiser kernel
         writes W as it steps g and v); the next packs are built from these tensors instead of folding with torch.  They are dropped
         again by any ``load_state_dict``, ``.to()`` or plain ``refresh_weights()``."""
-        self._packs = None
-        self._dgrad = None
         if folded is not None:
-            names = [f'convs.{i}' for i in range(len(self.convs))] + ['conv_post']
+            names = [ly.name for ly in layer_table(self.LAYERS)]
             if sorted(folded) != sorted(names):
                 raise ValueError(f'refresh_weights: folded must hold exactly the layers {names}, got {sorted(folded)}')
             for n in names:
-                w, v = folded[n][0], (self.conv_post if n == 'conv_post' else self.convs[int(n[len('convs.'):])]).weight_v
+                w, v = folded[n][0], self.get_submodule(n).weight_v
                 if w.numel() != v.numel() or w.device != v.device or w.dtype != torch.float32 or not w.is_contiguous():
                     raise ValueError(f'refresh_weights: the folded weight of {n} must be contiguous fp32 with weight_v\'s {v.numel()} elements on {v.device}')
-        self._folded = folded
+        self._drop_weights(folded)
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
-        self.refresh_weights()
+        self._drop_weights()
         return out
 
     def _apply(self, fn, *args, **kwargs):
-        self._packs = None                      # .to() / .cuda(): the packs follow the parameters
-        self._dgrad = None
-        self._folded = None
+        self._drop_weights()                    # .to() / .cuda(): the packs follow the parameters
         return super()._apply(fn, *args, **kwargs)
 
     def folded(self) -> dict:
@@ -273,140 +316,117 @@ class _SubDiscriminator(nn.Module):
         return {n: (w.reshape(w.shape[0], w.shape[1], w.shape[2]).contiguous(), b) for n, (w, b) in out.items()}
 
     def _device_weights(self):
+        """{layer: (weight, bias)}: the folded pair of the first and the last layer, the operand pack of every layer between."""
         if self._packs is None:
-            bf16 = PRECISIONS[self.precision]
-            F = self.folded()
-            dev = self.conv_post.bias.device
-            P = {'convs.0': F['convs.0'], 'conv_post': F['conv_post']}
-            for i, (cin, cout, k, _, g, _) in enumerate(self.LAYERS[1:], 1):
-                w, b = F[f'convs.{i}']
-                P[f'convs.{i}'] = (_packed('disc', w, (cout, cin // g, k, bf16), dev), b)
+            bf16, dev, P = PRECISIONS[self.precision], self.conv_post.bias.device, self.folded()
+            for ly in layer_table(self.LAYERS)[1:-1]:
+                w, b = P[ly.name]
+                P[ly.name] = (_packed('disc', w, (ly.cout, ly.cin // ly.groups, ly.taps, bf16), dev), b)
             self._packs = P
         return self._packs
 
     def _dgrad_weights(self):
-        """The transposed, per-stride-phase packs of dx_disc_conv_dgrad, built on the first backward only."""
+        """{layer: the transposed, per-stride-phase pack of dx_disc_conv_dgrad}, built on the first backward only."""
         if self._dgrad is None:
-            bf16 = PRECISIONS[self.precision]
-            F = self.folded()
-            dev = self.conv_post.bias.device
-            P = {}
-            for i, (cin, cout, k, s, g, _) in enumerate(self.LAYERS[1:], 1):
-                P[i] = _packed('disc_dgrad', F[f'convs.{i}'][0], (cin, cout, g, k, s, bf16), dev)
-            self._dgrad = P
+            bf16, dev, F = PRECISIONS[self.precision], self.conv_post.bias.device, self.folded()
+            self._dgrad = {ly.name: _packed('disc_dgrad', F[ly.name][0], (ly.cin, ly.cout, ly.groups, ly.taps, ly.stride, bf16), dev)
+                           for ly in layer_table(self.LAYERS)[1:-1]}
         return self._dgrad
 
-    def _run_bwd(self, score, fmaps, B, T, p, gw, i_gen, i_fm, dz, dy, accumulate):
-        """The chain of one sub-discriminator from its scores down to the waveform: score (2B, N, p) and the channels-last maps of a
-        forward pass over real + generated rows; gw the four upstream gradients (device); dz two buffers for the pre-activation
-        gradients; dy (B, T) receives (accumulate: is added) the gradient of the generated rows.  One launch per layer."""
-        L, st, bf16 = lib(), _stream(score.device), PRECISIONS[self.precision]
-        P, D = self._device_weights(), self._dgrad_weights()
-        gen, fm = gw.data_ptr() + 4 * i_gen, gw.data_ptr() + 4 * i_fm
-        N, C = score.shape[1], POST[0]
-        last = fmaps[-1]
-        (sr, sg), (r, g) = _halves(score), _halves(last)
-        cur, nxt = dz
-        L.dx_disc_post_bwd(sr, sg, N * p, 1, p, P['conv_post'][0].data_ptr(), cur.data_ptr(), r, g, N * p * C, C, p * C, gen, fm,
-                           2.0 / (score.numel() // 2), 2.0 / (last.numel() // 2), B * p, p, N, C, POST[2], 1, st)
-        for i in range(len(self.LAYERS) - 1, 0, -1):
-            cin, cout, k, s, grp, pad = self.LAYERS[i]
-            below = fmaps[i - 1]
-            n_in, n_out = below.shape[1], fmaps[i].shape[1]
-            r, g = _halves(below)
-            L.dx_disc_conv_dgrad(cur.data_ptr(), n_out * p * cout, cout, p * cout, D[i].data_ptr(), nxt.data_ptr(), r, g, n_in * p * cin, cin,
-                                 p * cin, fm, 2.0 / (below.numel() // 2), B * p, p, n_in, cin, cout, grp, k, s, pad, 1, bf16, st)
-            cur, nxt = nxt, cur
-        _, cout, k, s, _, pad = self.LAYERS[0]
-        L.dx_disc_first_bwd(cur.data_ptr(), P['convs.0'][0].data_ptr(), dy.data_ptr(), dy.shape[1], T, B, p, cout, k, s, pad,
-                            int(accumulate), st)
+    def forward(self, x):
+        """x (B, 1, T) -> (scores (B, n), [feature maps: 6 of (B, C, H, p), or 8 of (B, C, N)])."""
+        _check_inputs(x)
+        _check_reflect(x.shape[2], (self.period,))
+        _check_run(self, x)
+        return self._views(*self._run(x.reshape(x.shape[0], -1).contiguous(), _fresh))
 
-    def _wgrad_workspace(self, R, T, p):
-        """-> bytes of the largest workspace the weight-gradient kernels of this sub-discriminator ask for on R rows of T samples."""
-        L, nb = lib(), torch.zeros(1, dtype=torch.long)
-        _, cout, k, s, _, pad = self.LAYERS[0]
-        L.dx_disc_first_wgrad_size(R, T, p, cout, k, s, pad, nb.data_ptr())
-        need = int(nb.item())
-        N = conv_out(-(-T // p), k, s, pad)
-        for cin, cout, k, s, g, pad in self.LAYERS[1:]:
-            L.dx_disc_wgrad_size(R * p, N, cin, cout, g, k, s, pad, nb.data_ptr(), None)
-            need = max(need, int(nb.item()))
-            N = conv_out(N, k, s, pad)
-        L.dx_disc_post_wgrad_size(R * p, N, POST[0], POST[2], nb.data_ptr())
-        return max(need, int(nb.item()))
-
-    def _run_wgrad(self, x2, score, fmaps, B, p, gw, dz, ws, zero):
-        """The discriminator step of one sub-discriminator (csrc/dx_disc_wgrad.hip): x2 (2B, T) its input, score (2B, N, p) and the
-        channels-last maps of a pass, real rows first; gw -> ONE device float, the upstream gradient of its discriminator loss; dz two
-        buffers for the pre-activation gradients of all 2B rows; ws the workspace; zero -> a device zero (dx_disc_conv_dgrad's
-        feature-matching weight) -> {layer: (dW (Cout, Cin / groups, taps), db)} of the folded pairs.  Top down, each layer's weight
-        gradient launched before its data gradient, so the two dz buffers suffice."""
-        L, st, dev = lib(), _stream(score.device), score.device
-        P, D = self._device_weights(), self._dgrad_weights()
-        N, C, R = score.shape[1], POST[0], 2 * B
-        last = fmaps[-1]
-        cur, nxt = dz
-        out = {}
-        dW, db = _fresh((POST[1], C, POST[2]), dev), _fresh((POST[1],), dev)
-        L.dx_disc_post_wgrad(score.data_ptr(), N * p, 1, p, P['conv_post'][0].data_ptr(), last.data_ptr(), cur.data_ptr(), N * p * C, C, p * C, gw,
-                             2.0 / (score.numel() // 2), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), R * p, B * p, p, N, C, POST[2], st)
-        out['conv_post'] = (dW, db)
-        for i in range(len(self.LAYERS) - 1, 0, -1):
-            cin, cout, k, s, grp, pad = self.LAYERS[i]
-            below = fmaps[i - 1]
-            n_in, n_out = below.shape[1], fmaps[i].shape[1]
-            dW, db = _fresh((cout, cin // grp, k), dev), _fresh((cout,), dev)
-            L.dx_disc_wgrad(below.data_ptr(), n_in * p * cin, cin, p * cin, cur.data_ptr(), n_out * p * cout, cout, p * cout, dW.data_ptr(),
-                            db.data_ptr(), ws.data_ptr(), ws.numel(), R * p, p, n_in, cin, cout, grp, k, s, pad, st)
-            out[f'convs.{i}'] = (dW, db)
-            L.dx_disc_conv_dgrad(cur.data_ptr(), n_out * p * cout, cout, p * cout, D[i].data_ptr(), nxt.data_ptr(), below.data_ptr(),
-                                 below.data_ptr(), n_in * p * cin, cin, p * cin, zero, 0.0, R * p, p, n_in, cin, cout, grp, k, s, pad, 1, 0, st)
-            cur, nxt = nxt, cur
-        _, cout, k, s, _, pad = self.LAYERS[0]
-        dW, db = _fresh((cout, 1, k), dev), _fresh((cout,), dev)
-        L.dx_disc_first_wgrad(x2.data_ptr(), x2.shape[1], x2.shape[1], cur.data_ptr(), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), R, p,
-                              cout, k, s, pad, st)
-        out['convs.0'] = (dW, db)
-        return out
-
-    def _run(self, x2, p, alloc):
-        """x2 (R, T) fp32 contiguous on the device, period p (1: no folding) -> (scores (R, N, p), [channels-last feature maps
-        (R, N_i, p, C_i)]): one launch per layer."""
+    def _run(self, x2, alloc):
+        """x2 (R, T) fp32 contiguous on the device -> (scores (R, N, p), [channels-last feature maps (R, N_i, p, C_i)]): one launch per
+        layer."""
         L, st, bf16 = lib(), _stream(x2.device), PRECISIONS[self.precision]
         P = self._device_weights()
-        R, T = x2.shape
-        dev = x2.device
-        cin, cout, k, s, _, pad = self.LAYERS[0]
-        N = conv_out(-(-T // p), k, s, pad)
-        w, b = P['convs.0']
-        cur = alloc((R, N, p, cout), dev)
-        L.dx_disc_first(x2.data_ptr(), T, T, w.data_ptr(), b.data_ptr(), cur.data_ptr(), R, p, cout, k, s, pad, st)
-        fmaps = [cur]
-        for i, (cin, cout, k, s, g, pad) in enumerate(self.LAYERS[1:], 1):
-            w, b = P[f'convs.{i}']
-            nout = conv_out(N, k, s, pad)
-            out = alloc((R, nout, p, cout), dev)
-            L.dx_disc_conv(cur.data_ptr(), N * p * cin, cin, p * cin, w.data_ptr(), b.data_ptr(), out.data_ptr(), nout * p * cout, cout,
-                           p * cout, R * p, p, N, cin, cout, g, k, s, pad, 1, bf16, st)
-            fmaps.append(out)
-            cur, N = out, nout
-        w, b = P['conv_post']
-        score = alloc((R, N, p), dev)
-        C = POST[0]
-        L.dx_disc_post(cur.data_ptr(), N * p * C, C, p * C, w.data_ptr(), b.data_ptr(), score.data_ptr(), N * p, 1, p, R * p, p, N, C, POST[2], st)
-        return score, fmaps
+        (R, T), p, dev = x2.shape, self.period, x2.device
+        first, *hidden, post = layer_table(self.LAYERS, T, p)
+        w, b = P[first.name]
+        cur = alloc((R, first.n_out, p, first.cout), dev)
+        L.dx_disc_first(x2.data_ptr(), T, T, w.data_ptr(), b.data_ptr(), cur.data_ptr(), R, p, first.cout, first.taps, first.stride, first.pad, st)
+        maps = [cur]
+        for ly in hidden:
+            w, b = P[ly.name]
+            out = alloc((R, ly.n_out, p, ly.cout), dev)
+            L.dx_disc_conv(cur.data_ptr(), *ly.strides('in'), w.data_ptr(), b.data_ptr(), out.data_ptr(), *ly.strides('out'), R * p, p, ly.n_in,
+                           ly.cin, ly.cout, ly.groups, ly.taps, ly.stride, ly.pad, 1, bf16, st)
+            maps.append(out)
+            cur = out
+        w, b = P[post.name]
+        score = alloc((R, post.n_out, p), dev)
+        L.dx_disc_post(cur.data_ptr(), *post.strides('in'), w.data_ptr(), b.data_ptr(), score.data_ptr(), *post.strides('out'), R * p, p,
+                       post.n_in, post.cin, post.taps, st)
+        return score, maps
 
+    def _run_bwd(self, sub, gw, dz, dy, accumulate):
+        """The chain of one sub-discriminator of a pass from its scores down to its input: gw the four upstream gradients (device); dz
+        two buffers for the pre-activation gradients; dy (B, T_level) receives (accumulate: is added) the gradient of the generated
+        rows.  One launch per layer."""
+        L, st, bf16 = lib(), _stream(sub.score.device), PRECISIONS[self.precision]
+        P, D = self._device_weights(), self._dgrad_weights()
+        gen, fm = gw.data_ptr() + 4 * (2 * sub.set_id), gw.data_ptr() + 4 * (2 * sub.set_id + 1)
+        B, p = dy.shape[0], self.period
+        first, *hidden, post = sub.table
+        last = sub.maps[-1]
+        (sr, sg), (r, g) = _halves(sub.score), _halves(last)
+        cur, nxt = dz
+        L.dx_disc_post_bwd(sr, sg, *post.strides('out'), P[post.name][0].data_ptr(), cur.data_ptr(), r, g, *post.strides('in'), gen, fm,
+                           2.0 / (sub.score.numel() // 2), 2.0 / (last.numel() // 2), B * p, p, post.n_in, post.cin, post.taps, 1, st)
+        for ly, below in zip(reversed(hidden), reversed(sub.maps[:-1])):
+            r, g = _halves(below)
+            L.dx_disc_conv_dgrad(cur.data_ptr(), *ly.strides('out'), D[ly.name].data_ptr(), nxt.data_ptr(), r, g, *ly.strides('in'), fm,
+                                 2.0 / (below.numel() // 2), B * p, p, ly.n_in, ly.cin, ly.cout, ly.groups, ly.taps, ly.stride, ly.pad, 1, bf16, st)
+            cur, nxt = nxt, cur
+        L.dx_disc_first_bwd(cur.data_ptr(), P[first.name][0].data_ptr(), dy.data_ptr(), dy.shape[1], dy.shape[1], B, p, first.cout, first.taps,
+                            first.stride, first.pad, int(accumulate), st)
 
-def _views_p(score, fmaps):
-    """channels-last buffers -> the reference's (x (R, N p), [fmap (R, C, H, p)])."""
-    R = score.shape[0]
-    return score.view(R, -1), [f.permute(0, 3, 1, 2) for f in fmaps] + [score.unsqueeze(1)]
+    def _wgrad_workspace(self, sub):
+        """-> bytes of the largest workspace the weight-gradient kernels ask for on this sub-discriminator of a pass."""
+        L, nb, p, (R, T) = lib(), torch.zeros(1, dtype=torch.long), self.period, sub.x.shape
+        first, *hidden, post = sub.table
+        L.dx_disc_first_wgrad_size(R, T, p, first.cout, first.taps, first.stride, first.pad, nb.data_ptr())
+        need = int(nb.item())
+        for ly in hidden:
+            L.dx_disc_wgrad_size(R * p, ly.n_in, ly.cin, ly.cout, ly.groups, ly.taps, ly.stride, ly.pad, nb.data_ptr(), None)
+            need = max(need, int(nb.item()))
+        L.dx_disc_post_wgrad_size(R * p, post.n_in, post.cin, post.taps, nb.data_ptr())
+        return max(need, int(nb.item()))
 
-
-def _views_s(score, fmaps):
-    """channels-last buffers -> the reference's (x (R, N), [fmap (R, C, N)])."""
-    R = score.shape[0]
-    return score.view(R, -1), [f.squeeze(2).permute(0, 2, 1) for f in fmaps] + [score.view(R, 1, -1)]
+    def _run_wgrad(self, sub, gw, dz, ws, zero):
+        """The discriminator step of one sub-discriminator of a pass (csrc/dx_disc_wgrad.hip), real rows first; gw -> ONE device float,
+        the upstream gradient of its discriminator loss; dz two buffers for the pre-activation gradients of all 2B rows; ws the
+        workspace; zero -> a device zero (dx_disc_conv_dgrad's feature-matching weight) -> {layer: (dW (Cout, Cin / groups, taps), db)}
+        of the folded pairs.  Top down, each layer's weight gradient launched before its data gradient, so the two dz buffers suffice."""
+        L, st, dev = lib(), _stream(sub.score.device), sub.score.device
+        P, D = self._device_weights(), self._dgrad_weights()
+        (R, T), p = sub.x.shape, self.period
+        first, *hidden, post = sub.table
+        cur, nxt = dz
+        out = {}
+        dW, db = _fresh((post.cout, post.cin, post.taps), dev), _fresh((post.cout,), dev)
+        L.dx_disc_post_wgrad(sub.score.data_ptr(), *post.strides('out'), P[post.name][0].data_ptr(), sub.maps[-1].data_ptr(), cur.data_ptr(),
+                             *post.strides('in'), gw, 2.0 / (sub.score.numel() // 2), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
+                             R * p, R // 2 * p, p, post.n_in, post.cin, post.taps, st)
+        out[post.name] = (dW, db)
+        for ly, below in zip(reversed(hidden), reversed(sub.maps[:-1])):
+            dW, db = _fresh((ly.cout, ly.cin // ly.groups, ly.taps), dev), _fresh((ly.cout,), dev)
+            L.dx_disc_wgrad(below.data_ptr(), *ly.strides('in'), cur.data_ptr(), *ly.strides('out'), dW.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                            ws.numel(), R * p, p, ly.n_in, ly.cin, ly.cout, ly.groups, ly.taps, ly.stride, ly.pad, st)
+            out[ly.name] = (dW, db)
+            L.dx_disc_conv_dgrad(cur.data_ptr(), *ly.strides('out'), D[ly.name].data_ptr(), nxt.data_ptr(), below.data_ptr(), below.data_ptr(),
+                                 *ly.strides('in'), zero, 0.0, R * p, p, ly.n_in, ly.cin, ly.cout, ly.groups, ly.taps, ly.stride, ly.pad, 1, 0, st)
+            cur, nxt = nxt, cur
+        dW, db = _fresh((first.cout, 1, first.taps), dev), _fresh((first.cout,), dev)
+        L.dx_disc_first_wgrad(sub.x.data_ptr(), T, T, cur.data_ptr(), dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), R, p,
+                              first.cout, first.taps, first.stride, first.pad, st)
+        out[first.name] = (dW, db)
+        return out
 
 
 class DiscriminatorP(_SubDiscriminator):
@@ -418,12 +438,10 @@ class DiscriminatorP(_SubDiscriminator):
         self.period = int(period)
         self._init_layers(_WNConv, True, precision)
 
-    def forward(self, x):
-        """x (B, 1, T) -> (scores (B, n), [6 feature maps (B, C, H, p)])."""
-        _check_inputs(x)
-        _check_reflect(x.shape[2], (self.period,))
-        _check_run(self, x)
-        return _views_p(*self._run(x.reshape(x.shape[0], -1).contiguous(), self.period, _fresh))
+    @staticmethod
+    def _views(score, fmaps):
+        """channels-last buffers -> the reference's (x (R, N p), [fmap (R, C, H, p)])."""
+        return score.view(score.shape[0], -1), [f.permute(0, 3, 1, 2) for f in fmaps] + [score.unsqueeze(1)]
 
 
 class DiscriminatorS(_SubDiscriminator):
@@ -435,21 +453,20 @@ class DiscriminatorS(_SubDiscriminator):
         self.use_spectral_norm = bool(use_spectral_norm)
         self._init_layers(_SNConv if use_spectral_norm else _WNConv, False, precision)
 
-    def forward(self, x):
-        """x (B, 1, T) -> (scores (B, n), [8 feature maps (B, C, N)])."""
-        _check_inputs(x)
-        _check_run(self, x)
-        return _views_s(*self._run(x.reshape(x.shape[0], -1).contiguous(), 1, _fresh))
+    @staticmethod
+    def _views(score, fmaps):
+        """channels-last buffers -> the reference's (x (R, N), [fmap (R, C, N)])."""
+        return score.view(score.shape[0], -1), [f.squeeze(2).permute(0, 2, 1) for f in fmaps] + [score.view(score.shape[0], 1, -1)]
 
 
 class _MultiDiscriminator(nn.Module):
+    POOLED = False              # each sub-discriminator after the first reads the AvgPool1d(4, 2, padding=2) of the one before
+
     def refresh_weights(self, folded=None):
         """``folded``: {'discriminators.<i>.<layer>': (W, bias)}, see _SubDiscriminator.refresh_weights; a sub-discriminator none of whose
         layers is named (the spectral-normed one) folds its own parameters as before."""
         for i, d in enumerate(self.discriminators):
-            prefix = f'discriminators.{i}.'
-            own = None if folded is None else {k[len(prefix):]: v for k, v in folded.items() if k.startswith(prefix)}
-            d.refresh_weights(own or None)
+            d.refresh_weights(_below(folded, f'discriminators.{i}.'))
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
@@ -459,20 +476,31 @@ class _MultiDiscriminator(nn.Module):
     def forward(self, y, y_hat):
         """y, y_hat (B, 1, T) fp32 on the device -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs) as the reference returns them."""
         _check_inputs(y, y_hat)
-        self._check_shape(y.shape[2])
+        _check_reflect(y.shape[2], [d.period for d in self.discriminators])
         _check_run(self, y, y_hat)
         B = y.shape[0]
         x2 = torch.cat([y.detach().reshape(B, -1), y_hat.detach().reshape(B, -1)], 0)
         y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
-        for score, fmaps in (self._views(*raw) for raw in self._run(x2, _fresh)):
+        for d, (_, _, raw_score, raw_maps) in zip(self.discriminators, self._run(x2, _fresh)):
+            score, fmaps = d._views(raw_score, raw_maps)
             y_d_rs.append(score[:B])
             y_d_gs.append(score[B:])
             fmap_rs.append([f[:B] for f in fmaps])
             fmap_gs.append([f[B:] for f in fmaps])
         return y_d_rs, y_d_gs, fmap_rs, fmap_gs
 
-    def _check_shape(self, T):
-        pass
+    def _run(self, x2, alloc):
+        """-> per sub-discriminator (the level of its input: how often x2 was pooled, its (R, T_level) input, scores, feature maps), the
+        last two as the kernels' channels-last buffers."""
+        out, level = [], 0
+        for i, d in enumerate(self.discriminators):
+            if i and self.POOLED:
+                R, T = x2.shape
+                pooled = alloc((R, T // 2 + 1), x2.device)
+                lib().dx_disc_pool(x2.data_ptr(), pooled.data_ptr(), R, T, _stream(x2.device))
+                x2, level = pooled, level + 1
+            out.append((level, x2) + d._run(x2, alloc))
+        return out
 
 
 class MultiPeriodDiscriminator(_MultiDiscriminator):
@@ -482,41 +510,17 @@ class MultiPeriodDiscriminator(_MultiDiscriminator):
         super().__init__()
         self.discriminators = nn.ModuleList([DiscriminatorP(p, precision) for p in PERIODS])
 
-    def _check_shape(self, T):
-        _check_reflect(T, PERIODS)
-
-    _views = staticmethod(_views_p)
-
-    def _run(self, x2, alloc):
-        """-> per sub-discriminator (scores, feature maps) as the kernels' channels-last buffers."""
-        return [d._run(x2, d.period, alloc) for d in self.discriminators]
-
 
 class MultiScaleDiscriminator(_MultiDiscriminator):
     """Three scale sub-discriminators, the first spectral-normed, the others fed through AvgPool1d(4, 2, padding=2)
     (discriminators.py:127-156): 26 launches for both inputs."""
+    POOLED = True
 
     def __init__(self, precision='f32'):
         super().__init__()
         self.discriminators = nn.ModuleList([DiscriminatorS(True, precision), DiscriminatorS(False, precision),
                                              DiscriminatorS(False, precision)])
         self.meanpools = nn.ModuleList([nn.Module(), nn.Module()])      # the reference's two AvgPool1d: no parameters
-
-    _views = staticmethod(_views_s)
-
-    def _run(self, x2, alloc, inputs=None):
-        """``inputs``: a list that receives the (R, T_i) input of each sub-discriminator (the waveforms, then the two pooled buffers)."""
-        out = []
-        for i, d in enumerate(self.discriminators):
-            if i:
-                R, T = x2.shape
-                pooled = alloc((R, T // 2 + 1), x2.device)
-                lib().dx_disc_pool(x2.data_ptr(), pooled.data_ptr(), R, T, _stream(x2.device))
-                x2 = pooled
-            if inputs is not None:
-                inputs.append(x2)
-            out.append(d._run(x2, 1, alloc))
-        return out
 
 
 # ---- losses -----------------------------------------------------------------------------------------------------------------------
@@ -535,26 +539,25 @@ def _dense_pair(r, g):
     return r, g
 
 
-def _loss_rows(pairs, kind, set_id, keep):
+def _loss_rows(pairs, kind, set_id):
+    """-> [(r, g, code)]: each pair as dense blocks, and its code in dx_disc_losses' table."""
     rows = []
     for r, g in pairs:
         r, g = _dense_pair(r, g)
         if r.numel() == 0:
             raise ValueError('a loss over an empty tensor')
-        keep += [r, g]
-        rows.append([r.data_ptr(), g.data_ptr(), r.numel(), kind + 2 * set_id])
+        rows.append((r, g, kind + 2 * set_id))
     return rows
 
 
 class _LossPlan:
-    """The device table of dx_disc_losses for a fixed list of tensors, and its workspace."""
+    """The device table of dx_disc_losses for a fixed list of tensors (``_loss_rows``; kept alive here), and its workspace."""
 
     def __init__(self, rows, n_sets, device):
-        if device.type != 'cuda':
-            raise RuntimeError('the GAN losses run on the GPU (csrc/dx_disc.hip); there is no CPU path')
-        self.n, self.n_sets = len(rows), n_sets
-        self.max_count, self.total = max(r[2] for r in rows), sum(r[2] for r in rows)
-        self.table = torch.tensor(rows, dtype=torch.int64).to(device)
+        _require_gpu(device, 'the GAN losses run on the GPU (csrc/dx_disc.hip)')
+        self.rows, self.n, self.n_sets = rows, len(rows), n_sets
+        self.max_count, self.total = max(r.numel() for r, _, _ in rows), sum(r.numel() for r, _, _ in rows)
+        self.table = torch.tensor([[r.data_ptr(), g.data_ptr(), r.numel(), code] for r, g, code in rows], dtype=torch.int64).to(device)
         nfl = torch.zeros(1, dtype=torch.long)
         lib().dx_disc_losses_workspace(self.max_count, self.n, nfl.data_ptr())
         self.partial = torch.empty(int(nfl.item()), dtype=torch.float32, device=device)
@@ -577,8 +580,7 @@ def discriminator_loss(disc_real_outputs, disc_generated_outputs):
     """-> (loss, r_losses, g_losses) as discriminators.py:163-174; the list entries are 0-d device tensors, not floats."""
     pairs = list(zip(disc_real_outputs, disc_generated_outputs))
     _check_loss_inputs([t for p in pairs for t in p])
-    keep = []
-    out = _LossPlan(_loss_rows(pairs, 0, 0, keep), 1, pairs[0][0].device).run()
+    out = _LossPlan(_loss_rows(pairs, 0, 0), 1, pairs[0][0].device).run()
     return out[0], [out[3 + 3 * i] for i in range(len(pairs))], [out[3 + 3 * i + 1] for i in range(len(pairs))]
 
 
@@ -586,8 +588,7 @@ def generator_loss(disc_outputs):
     """-> (loss, gen_losses) as discriminators.py:177-185."""
     outs = list(disc_outputs)
     _check_loss_inputs(outs)
-    keep = []
-    out = _LossPlan(_loss_rows([(t, t) for t in outs], 0, 0, keep), 1, outs[0].device).run()
+    out = _LossPlan(_loss_rows([(t, t) for t in outs], 0, 0), 1, outs[0].device).run()
     return out[1], [out[3 + 3 * i + 2] for i in range(len(outs))]
 
 
@@ -595,8 +596,7 @@ def feature_loss(fmap_r, fmap_g):
     """-> 2 x the sum over all feature maps of mean |r - g| (discriminators.py:188-194)."""
     pairs = [(rl, gl) for dr, dg in zip(fmap_r, fmap_g) for rl, gl in zip(dr, dg)]
     _check_loss_inputs([t for p in pairs for t in p])
-    keep = []
-    return _LossPlan(_loss_rows(pairs, 1, 0, keep), 1, pairs[0][0].device).run()[2]
+    return _LossPlan(_loss_rows(pairs, 1, 0), 1, pairs[0][0].device).run()[2]
 
 
 def _checkpoint(checkpoint) -> dict:
@@ -605,6 +605,44 @@ def _checkpoint(checkpoint) -> dict:
     if not isinstance(checkpoint, dict) or 'mpd' not in checkpoint or 'msd' not in checkpoint:
         raise TypeError("a discriminator checkpoint is a dict with 'mpd' and 'msd' state dicts (the reference's do_* files)")
     return checkpoint
+
+
+class _Plan:
+    """What ``HiFiGanDiscriminators`` keeps per (B, T, device): the activation arenas of the two discriminators, the latest pass over
+    them, the loss table, the workspaces of the two backwards (made on first use) and the upstream weights uploaded so far."""
+
+    def __init__(self):
+        self.arenas = {'mpd': _Arena(), 'msd': _Arena()}
+        self.passes, self.subs = 0, []           # the passes begun so far; the sub-discriminators of the latest one
+        self.loss = None                         # _LossPlan over the arenas' buffers
+        self.bwd = None                          # (dz pair, [gradient buffer of each pooled input])
+        self.train = None                        # (dz pair, workspace, device zero)
+        self.uploaded = {}
+
+    def begin(self):
+        """Starts a pass: the arenas hand out their buffers from the first again."""
+        self.passes += 1
+        for arena in self.arenas.values():
+            arena.reset()
+
+    def check_current(self, stamp):
+        if self.passes != stamp:
+            raise RuntimeError('the discriminators\' feature maps of this pass were overwritten by a later pass at the same (B, T): '
+                               'call backward() before the next losses() / generator_losses() / generator_loss_grad() at that shape')
+
+    def upstream(self, weights, n, device):
+        """``weights``: n floats or an fp32 tensor of n on ``device`` -> an fp32 device tensor of n, read by the kernels.  Floats are
+        uploaded once per plan: a captured graph must not copy from host memory."""
+        held = torch.is_tensor(weights)
+        key = None if held else tuple(float(w) for w in weights)
+        ok = (weights.shape == (n,) and weights.dtype == torch.float32 and weights.device == device) if held else len(key) == n
+        if not ok:
+            raise ValueError(f'weights: {"two" if n == 2 else "four"} floats or an fp32 tensor of {n} on the inputs\' device')
+        if held:
+            return weights.detach().contiguous()
+        if key not in self.uploaded:
+            self.uploaded[key] = torch.tensor(key, dtype=torch.float32).to(device)
+        return self.uploaded[key]
 
 
 class HiFiGanDiscriminators:
@@ -624,83 +662,89 @@ class HiFiGanDiscriminators:
         state = _checkpoint(checkpoint)
         self.precision = precision
         self.device = torch.device(device)
-        self.mpd = MultiPeriodDiscriminator(precision)
-        self.msd = MultiScaleDiscriminator(precision)
-        self.mpd.load_state_dict(state['mpd'], strict=True)
-        self.msd.load_state_dict(state['msd'], strict=True)
-        self.mpd.to(self.device).eval()
-        self.msd.to(self.device).eval()
+        self.mpd, self.msd = MultiPeriodDiscriminator(precision), MultiScaleDiscriminator(precision)
+        for tag, module in self.named():
+            module.load_state_dict(state[tag], strict=True)
+            module.to(self.device).eval()
         self._plans = {}
 
-    def _pass(self, y, y_hat, differentiable=False, train=False):
+    def named(self):
+        """-> (('mpd', the MPD), ('msd', the MSD)): the tags under which both discriminators' layers, folded weights and gradients are
+        keyed, '<tag>.discriminators.<i>.<layer>', and the order of a pass."""
+        return ('mpd', self.mpd), ('msd', self.msd)
+
+    def refresh_weights(self, folded=None):
+        """``refresh_weights`` of both discriminators; ``folded``: {'<tag>.discriminators.<i>.<layer>': (W, bias)}, as
+        vocoder_optim.NormedAdamW.folded() names the layers it was given under these tags."""
+        for tag, module in self.named():
+            module.refresh_weights(_below(folded, tag + '.'))
+
+    def _plan(self, y, y_hat, check):
+        """The guards of an entry point (``check``: one of the three above) -> the plan of the inputs' shape."""
         _check_inputs(y, y_hat)
         _check_reflect(y.shape[2], PERIODS)
-        if train:
-            _check_train(self, y)
-        elif differentiable:
-            _check_differentiable(self, y, y_hat)
-        else:
-            _check_run(self.mpd, y, y_hat)
-        B, _, T = y.shape
-        key = (B, T, y.device)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = {'f': _Arena(), 's': _Arena(), 'loss': None, 'pass': 0, 'bwd': None, 'gw': {}}
-        plan['pass'] += 1
+        check(self, y, y_hat)
+        key = (y.shape[0], y.shape[2], y.device)
+        if key not in self._plans:
+            self._plans[key] = _Plan()
+        return self._plans[key]
+
+    def _pass(self, plan, y, y_hat):
+        """One forward of both discriminators into the plan's arenas -> the stamp of the pass."""
+        B = y.shape[0]
+        plan.begin()
         x2 = torch.cat([y.detach().reshape(B, -1), y_hat.detach().reshape(B, -1)], 0)
-        plan['f'].reset()
-        plan['s'].reset()
-        mpd = self.mpd._run(x2, plan['f'])
-        plan['inputs'] = [x2] * len(PERIODS)         # the (2B, T_i) input of every sub-discriminator, for the first layers' weight gradients
-        msd = self.msd._run(x2, plan['s'], plan['inputs'])
-        return plan, B, mpd, msd
+        plan.subs = []
+        for set_id, (tag, module) in enumerate(self.named()):
+            for i, (d, (level, x, score, maps)) in enumerate(zip(module.discriminators, module._run(x2, plan.arenas[tag]))):
+                plan.subs.append(_Sub(d, tag, i, set_id, level, x, layer_table(d.LAYERS, x.shape[1], d.period), score, maps))
+        return plan.passes
 
     def losses(self, y, y_hat) -> dict:
-        plan, B, mpd, msd = self._pass(y, y_hat)
-        return self._losses(plan, B, mpd, msd, y.device)
+        plan = self._plan(y, y_hat, _check_forward)
+        self._pass(plan, y, y_hat)
+        return self._losses(plan)
 
-    def _losses(self, plan, B, mpd, msd, device):
-        if plan['loss'] is None:
-            rows, keep = [], []
-            for s, outs in enumerate((mpd, msd)):
-                rows += _loss_rows([(sc[:B], sc[B:]) for sc, _ in outs], 0, s, keep)
-                rows += _loss_rows([(f[:B], f[B:]) for sc, fm in outs for f in fm + [sc]], 1, s, keep)
-            plan['loss'] = _LossPlan(rows, 2, device)
-        out = plan['loss'].run()
+    def _losses(self, plan):
+        if plan.loss is None:
+            B = plan.subs[0].x.shape[0] // 2
+            rows = []
+            for set_id in range(2):
+                own = [sub for sub in plan.subs if sub.set_id == set_id]
+                rows += _loss_rows([(sub.score[:B], sub.score[B:]) for sub in own], 0, set_id)
+                rows += _loss_rows([(f[:B], f[B:]) for sub in own for f in sub.maps + [sub.score]], 1, set_id)
+            plan.loss = _LossPlan(rows, 2, plan.subs[0].x.device)
+        out = plan.loss.run()
         return {name: out[i] for i, name in enumerate(LOSS_NAMES)}
 
     # ---- backward to the generated waveform (csrc/dx_disc_bwd.hip) -------------------------------------------------------------------
     def _forward_kept(self, y, y_hat):
-        """One pass whose feature maps stay in the plan for a backward -> (state, the four generator-side losses)."""
-        plan, B, mpd, msd = self._pass(y, y_hat, differentiable=True)
-        six = self._losses(plan, B, mpd, msd, y.device)
-        state = (plan, plan['pass'], B, y.shape[2], mpd, msd)
-        return state, {name: six[name] for name in GEN_LOSS_NAMES}
+        """One pass whose feature maps stay in the plan for a backward -> (plan, the pass's stamp, the four generator-side losses)."""
+        plan = self._plan(y, y_hat, _check_differentiable)
+        stamp = self._pass(plan, y, y_hat)
+        six = self._losses(plan)
+        return plan, stamp, {name: six[name] for name in GEN_LOSS_NAMES}
 
-    def _backward(self, state, gw):
-        """gw: fp32 device tensor of 4, the upstream gradients in GEN_LOSS_NAMES order -> dy_hat (B, 1, T)."""
-        plan, stamp, B, T, mpd, msd = state
-        if plan['pass'] != stamp:
-            raise RuntimeError('the discriminators\' feature maps of this pass were overwritten by a later pass at the same (B, T): '
-                               'call backward() before the next losses() / generator_losses() / generator_loss_grad() at that shape')
-        dev = gw.device
-        if plan['bwd'] is None:
-            biggest = max(f.numel() // 2 for _, fm in mpd + msd for f in fm)
-            plan['bwd'] = {'dz': (_fresh((biggest,), dev), _fresh((biggest,), dev)),
-                           'pooled': [_fresh((B, msd[i][1][0].shape[1]), dev) for i in (1, 2)]}
-        dz, pooled = plan['bwd']['dz'], plan['bwd']['pooled']
-        dy = _fresh((B, T), dev)
-        for i, (d, (score, fmaps)) in enumerate(zip(self.mpd.discriminators, mpd)):
-            d._run_bwd(score, fmaps, B, T, d.period, gw, 0, 1, dz, dy, i > 0)
-        subs = self.msd.discriminators
-        subs[0]._run_bwd(*msd[0], B, T, 1, gw, 2, 3, dz, dy, True)
-        T1, T2 = pooled[0].shape[1], pooled[1].shape[1]
-        subs[1]._run_bwd(*msd[1], B, T1, 1, gw, 2, 3, dz, pooled[0], False)
-        subs[2]._run_bwd(*msd[2], B, T2, 1, gw, 2, 3, dz, pooled[1], False)
+    def _backward(self, plan, stamp, gw):
+        """gw: fp32 device tensor of 4, the upstream gradients in GEN_LOSS_NAMES order -> dy_hat (B, 1, T).  Every sub-discriminator's
+        chain ends in the gradient of its own input; the pooled inputs' gradients are then folded back, last level first."""
+        plan.check_current(stamp)
+        dev, subs = gw.device, plan.subs
+        B, T = subs[0].x.shape[0] // 2, subs[0].x.shape[1]
+        if plan.bwd is None:
+            biggest = max(f.numel() // 2 for sub in subs for f in sub.maps)
+            lengths = {sub.level: sub.x.shape[1] for sub in subs}
+            plan.bwd = (_fresh((biggest,), dev), _fresh((biggest,), dev)), [_fresh((B, lengths[k]), dev) for k in range(1, len(lengths))]
+        dz, pooled = plan.bwd
+        dx = [_fresh((B, T), dev)] + pooled              # per level: the gradient of that input's generated rows
+        written = set()
+        for sub in subs:
+            sub.module._run_bwd(sub, gw, dz, dx[sub.level], sub.level in written)
+            written.add(sub.level)
         L, st = lib(), _stream(dev)
-        L.dx_disc_pool_bwd(pooled[1].data_ptr(), pooled[0].data_ptr(), B, T1, 1, st)
-        L.dx_disc_pool_bwd(pooled[0].data_ptr(), dy.data_ptr(), B, T, 1, st)
-        return dy.view(B, 1, T)
+        for level in range(len(dx) - 1, 0, -1):
+            L.dx_disc_pool_bwd(dx[level].data_ptr(), dx[level - 1].data_ptr(), B, dx[level - 1].shape[1], 1, st)
+        return dx[0].view(B, 1, T)
 
     def generator_losses(self, y, y_hat) -> dict:
         """-> {loss_gen_f, loss_fm_f, loss_gen_s, loss_fm_s}: the bits of ``losses()``, differentiable with respect to ``y_hat`` (only).
@@ -712,20 +756,8 @@ class HiFiGanDiscriminators:
         """-> ({the four generator-side losses}, d sum_i weights[i] loss_i / d y_hat (B, 1, T)), without autograd.  ``weights``: four
         floats or an fp32 device tensor of 4, in the order loss_gen_f, loss_fm_f, loss_gen_s, loss_fm_s."""
         with torch.no_grad():
-            state, four = self._forward_kept(y, y_hat)
-            plan = state[0]
-            if torch.is_tensor(weights):
-                if weights.shape != (4,) or weights.dtype != torch.float32 or weights.device != y.device:
-                    raise ValueError('weights: four floats or an fp32 tensor of 4 on the inputs\' device')
-                gw = weights.detach().contiguous()
-            else:
-                key = tuple(float(w) for w in weights)
-                if len(key) != 4:
-                    raise ValueError('weights: four floats or an fp32 tensor of 4 on the inputs\' device')
-                gw = plan['gw'].get(key)
-                if gw is None:                       # uploaded once per plan: a captured graph must not copy from host memory
-                    gw = plan['gw'][key] = torch.tensor(key, dtype=torch.float32).to(y.device)
-            return four, self._backward(state, gw)
+            plan, stamp, four = self._forward_kept(y, y_hat)
+            return four, self._backward(plan, stamp, plan.upstream(weights, 4, y.device))
 
     # ---- the discriminator step: loss_disc to every parameter (csrc/dx_disc_wgrad.hip; DESIGN §18) ---------------------------------
     def _spectral_layers(self):
@@ -751,49 +783,32 @@ class HiFiGanDiscriminators:
         bits either way."""
         n = _check_power_iterations(power_iterations)
         with torch.no_grad():
-            _check_inputs(y, y_hat)
-            _check_reflect(y.shape[2], PERIODS)
-            _check_train(self, y)
-            dev, key = y.device, None
-            if torch.is_tensor(weights):
-                if weights.shape != (2,) or weights.dtype != torch.float32 or weights.device != dev:
-                    raise ValueError('weights: two floats or an fp32 tensor of 2 on the inputs\' device')
-                gw = weights.detach().contiguous()
-            else:
-                key = tuple(float(w) for w in weights)
-                if len(key) != 2:
-                    raise ValueError('weights: two floats or an fp32 tensor of 2 on the inputs\' device')
+            plan, dev = self._plan(y, y_hat, _check_train), y.device
+            gw = plan.upstream(weights, 2, dev)
             if n:
                 for c in self._spectral_layers():
                     power_iterate(c.weight_orig, c.weight_u, c.weight_v, n)
                 for d in self.msd.discriminators:
                     if d.use_spectral_norm:
                         d.refresh_weights()
-            plan, B, mpd, msd = self._pass(y, y_hat, train=True)
-            six = self._losses(plan, B, mpd, msd, y.device)
-            if key is not None:
-                gw = plan['gw'].get(key)
-                if gw is None:                       # uploaded once per plan, as generator_loss_grad's
-                    gw = plan['gw'][key] = torch.tensor(key, dtype=torch.float32).to(dev)
-            subs = list(zip(self.mpd.discriminators, mpd, [d.period for d in self.mpd.discriminators], [0] * len(mpd))) + \
-                list(zip(self.msd.discriminators, msd, [1] * len(msd), [1] * len(msd)))
-            inputs = plan['inputs']
-            if plan.get('train') is None:
-                biggest = max(f.numel() for _, fm in mpd + msd for f in fm)
-                need = max(d._wgrad_workspace(2 * B, x.shape[1], p) for (d, _, p, _), x in zip(subs, inputs))
-                plan['train'] = {'dz': (_fresh((biggest,), dev), _fresh((biggest,), dev)), 'zero': torch.zeros(1, dtype=torch.float32, device=dev),
-                                 'ws': torch.empty(need, dtype=torch.uint8, device=dev)}
-            tr = plan['train']
-            grads = {'mpd': {}, 'msd': {}}
-            for j, ((d, (score, fmaps), p, which), x) in enumerate(zip(subs, inputs)):
-                pairs = d._run_wgrad(x, score, fmaps, B, p, gw.data_ptr() + 4 * which, tr['dz'], tr['ws'], tr['zero'].data_ptr())
-                i = j if which == 0 else j - len(mpd)
+            self._pass(plan, y, y_hat)
+            six = self._losses(plan)
+            subs = plan.subs
+            if plan.train is None:
+                biggest = max(f.numel() for sub in subs for f in sub.maps)
+                need = max(sub.module._wgrad_workspace(sub) for sub in subs)
+                plan.train = ((_fresh((biggest,), dev), _fresh((biggest,), dev)), torch.empty(need, dtype=torch.uint8, device=dev),
+                              torch.zeros(1, dtype=torch.float32, device=dev))
+            dz, ws, zero = plan.train
+            grads = {tag: {} for tag, _ in self.named()}
+            for sub in subs:
+                pairs = sub.module._run_wgrad(sub, gw.data_ptr() + 4 * sub.set_id, dz, ws, zero.data_ptr())
                 for name, (dw, db) in pairs.items():
-                    conv = d.conv_post if name == 'conv_post' else d.convs[int(name[len('convs.'):])]
+                    conv, key = sub.module.get_submodule(name), f'discriminators.{sub.index}.{name}'
                     if folded and not isinstance(conv, _SNConv):
-                        grads['msd' if which else 'mpd'][f'discriminators.{i}.{name}'] = (dw, db)
+                        grads[sub.tag][key] = (dw, db)
                     else:
-                        _norm_backward(conv, f'discriminators.{i}.{name}', dw, db, grads['msd' if which else 'mpd'])
+                        _norm_backward(conv, key, dw, db, grads[sub.tag])
             return {'loss_disc_f': six['loss_disc_f'], 'loss_disc_s': six['loss_disc_s']}, grads
 
     def discriminator_backward(self, y, y_hat, weights=(1.0, 1.0), power_iterations=1):
@@ -802,7 +817,7 @@ class HiFiGanDiscriminators:
         ``optim_d.zero_grad(); D.discriminator_backward(y, y_hat); optim_d.step(); D.mpd.refresh_weights(); D.msd.refresh_weights()``."""
         two, grads = self.discriminator_loss_grad(y, y_hat, weights, power_iterations)
         with torch.no_grad():
-            for tag, module in (('mpd', self.mpd), ('msd', self.msd)):
+            for tag, module in self.named():
                 for key, q in module.named_parameters():
                     g = grads[tag][key]
                     if q.grad is None:
@@ -815,8 +830,8 @@ class HiFiGanDiscriminators:
 class _GeneratorLosses(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y_hat, owner, y):
-        state, four = owner._forward_kept(y, y_hat)
-        ctx.owner, ctx.state = owner, state
+        ctx.plan, ctx.stamp, four = owner._forward_kept(y, y_hat)
+        ctx.owner = owner
         return tuple(four[name].clone() for name in GEN_LOSS_NAMES)
 
     @staticmethod
@@ -824,7 +839,7 @@ class _GeneratorLosses(torch.autograd.Function):
     def backward(ctx, *grads):
         ref = next(g for g in grads if g is not None)
         gw = torch.stack([torch.zeros_like(ref) if g is None else g for g in grads]).float().reshape(4).contiguous()
-        return ctx.owner._backward(ctx.state, gw), None, None
+        return ctx.owner._backward(ctx.plan, ctx.stamp, gw), None, None
 
 
 __all__ = ['DiscriminatorP', 'DiscriminatorS', 'MultiPeriodDiscriminator', 'MultiScaleDiscriminator', 'HiFiGanDiscriminators',

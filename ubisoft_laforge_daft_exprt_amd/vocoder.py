@@ -20,8 +20,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ._lib import lib
-from .discriminators import _packed
+from ._lib import lib, packed as _packed, stream as _stream
 
 NEG_SLOPE = 0.1     # leaky-ReLU slope before every convolution (applied inside the kernels)
 HOP = 256           # waveform samples per mel frame: the product of the four upsampling factors
@@ -620,7 +619,3 @@ def load_hifigan_vocoder(checkpoint_path=None, device=None, precision='f32'):
     if device is None:
         device = 'cuda'
     return HiFiGanVocoder(checkpoint_path=checkpoint_path, config=DEFAULT_CONFIG, device=device, precision=precision)
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream

@@ -84,7 +84,8 @@ class HiFiGanFineTuner:
         betas = (adam_b1, adam_b2)
         D = self.discriminators
         self.optim_g = NormedAdamW(_layers('', self.generator), learning_rate, betas, leaves=True)
-        self.optim_d = NormedAdamW(_layers('msd.', D.msd) + _layers('mpd.', D.mpd), learning_rate, betas)     # MSD first, as line 134
+        msd_first = [layer for tag, module in reversed(D.named()) for layer in _layers(tag + '.', module)]         # as line 134
+        self.optim_d = NormedAdamW(msd_first, learning_rate, betas)
         self.step, self.epoch = 0, 0
         if not reset_optimizers and 'optim_g' in ckpt and 'optim_d' in ckpt:
             self.optim_g.load_state_dict(ckpt['optim_g'])
@@ -97,15 +98,12 @@ class HiFiGanFineTuner:
 
     def _refresh_discriminators(self):
         """The discriminators' packs from the optimiser's W (the spectral-normed sub-discriminator folds its own parameters)."""
-        F = self.optim_d.folded()
-        D = self.discriminators
-        D.msd.refresh_weights({k[len('msd.'):]: v for k, v in F.items() if k.startswith('msd.')})
-        D.mpd.refresh_weights({k[len('mpd.'):]: v for k, v in F.items() if k.startswith('mpd.')})
+        self.discriminators.refresh_weights(self.optim_d.folded())
 
     def discriminator_gradients(self, y, y_hat):
         """-> ({loss_disc_f, loss_disc_s}, the gradients as ``optim_d.step`` takes them) of ``discriminator_loss_grad(folded=True)``."""
         two, grads = self.discriminators.discriminator_loss_grad(y, y_hat, power_iterations=self.power_iterations, folded=True)
-        return two, {f'{tag}.{k}': g for tag in ('msd', 'mpd') for k, g in grads[tag].items()}
+        return two, {f'{tag}.{k}': g for tag in grads for k, g in grads[tag].items()}
 
     def generator_gradients(self):
         """-> the gradients as ``optim_g.step`` takes them, read off the folded leaves and the biases after ``backward()``."""

@@ -15,14 +15,10 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import lib
+from ._lib import lib, stream as _stream
 
 # {address of a device job table: (elements of its weight-normed jobs, elements of its plain jobs)}: what profiling.price needs
 TABLE_LOG = {}
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _check_param(name, p):

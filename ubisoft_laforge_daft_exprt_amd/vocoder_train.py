@@ -25,9 +25,8 @@ import json
 
 import torch
 
-from ._lib import lib
-from .discriminators import _packed
-from .vocoder import HOP, HiFiGanVocoder, _issue, _stream, check_config, generator_launches, pad_folded_weights
+from ._lib import lib, packed as _packed, stream as _stream
+from .vocoder import HOP, HiFiGanVocoder, _issue, check_config, generator_launches, pad_folded_weights
 
 
 # ---- host-built operands of the data gradients --------------------------------------------------------------------------------------
