@@ -490,6 +490,29 @@ def test_graph_buckets_replay_exact_shapes(dx):
     assert len(synth.graphs) == 1, list(synth.graphs)
 
 
+def test_graph_cache_evicts_the_least_used_bucket(dx):
+    """``max_graphs=2`` and three T buckets X, Y, Z (B = 1, L = 12; T_max 33, 93, 150: buckets 64, 128, 192) called X, Y, X, Z, Y: a full
+    cache drops the bucket with the fewest hits (Y with 1, not X with 2, when Z arrives; then Z, and Y is captured anew with hits 1).  The
+    expected contents follow from the rule ``del cache[min(cache, key=hits)]`` before an insert and ``hits += 1`` per graphed call; every
+    graphed result is bitwise the eager one."""
+    from ubisoft_laforge_daft_exprt_amd.inference import GraphedSynthesizer
+    from ubisoft_laforge_daft_exprt_amd.synth import synthetic_inference_batch
+    hp = helpers.golden_hparams(stats={'spk 0': {'pitch': {'mean': 5.0, 'std': 0.25}}, 'spk 1': {'pitch': {'mean': 4.6, 'std': 0.3}}})
+    synth = GraphedSynthesizer(build_model(dx, hp).eval(), hp, max_graphs=2)
+    inputs, prosody, spk, accent = synthetic_inference_batch(batch_size=1, sym_len_range=(12, 12), seed=21)
+    X, Y, Z = (1, 16, 64, 'f32'), (1, 16, 128, 'f32'), (1, 16, 192, 'f32')
+    calls = ((0.4, 33, {X: 1}), (1.0, 93, {X: 1, Y: 1}), (0.4, 33, {X: 2, Y: 1}), (1.6, 150, {X: 2, Z: 1}), (1.0, 93, {X: 2, Y: 1}))
+    for scale, T, cached in calls:
+        mv = lambda t: t.clone().to(DEV)
+        dev = lambda: ((mv(inputs[0]), mv(inputs[1] * scale)) + tuple(mv(t) for t in inputs[2:]), 'add', {k: mv(v) for k, v in prosody.items()},
+                       mv(spk), mv(accent))
+        _, (mel_e, len_e), w_e = synth(*dev(), use_graph=False)
+        _, (mel_g, len_g), w_g = synth(*dev(), use_graph=True)
+        assert mel_g.shape[2] == T and len_g.tolist() == [T]
+        assert torch.equal(mel_e, mel_g) and torch.equal(w_e, w_g) and torch.equal(len_e, len_g)
+        assert {k: e.hits for k, e in synth.graphs.items()} == cached, (scale, list(synth.graphs))
+
+
 @pytest.mark.parametrize('use_graph', [False, True])
 def test_batched_accent_encoder_equals_per_recording_runs(dx, use_graph):
     """scripts/synthesize.py:420-448 runs the accent encoder once per reference recording (B = 1, no padding) and averages.  The batched form

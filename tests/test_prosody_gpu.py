@@ -227,7 +227,7 @@ def test_speech_synthesizer_end_to_end(g, parts, transform, use_graph):
     assert second['mel'].shape[2] != first['mel'].shape[2] and second['mel'].shape[2] <= 64
     assert len(synth.synth.graphs) == (1 if use_graph else 0)
     if use_graph:
-        assert next(iter(synth.synth.graphs.values()))['hits'] == 2
+        assert next(iter(synth.synth.graphs.values())).hits == 2
     a = _case_args(case)
     without = synth(a[0], transform, a[1], a[2], a[3], pcm16=False, use_graph=use_graph)
     assert without['pcm'] is None and torch.equal(without['audio'], first['audio'])

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from ._lib import lib
+from .graphs import Entry, GraphCache, capture
 from .mel import DEFAULTS, HOP, N_FFT, mel_filter_bank
 
 N_BINS = N_FFT // 2 + 1
@@ -129,7 +130,7 @@ class GriffinLim:
         self.bank = pack_filter_bank(self.filter_bank)           # raises for a bank the kernel cannot take
         self.device = torch.device(device)
         self._ops = None
-        self._graphs = {}                                        # (B, T, iterations) -> captured chain and its static buffers
+        self._graphs = GraphCache(self.MAX_GRAPHS, 'oldest')     # (B, T, iterations) -> captured chain and its static buffers
         self.captures = 0
 
     # -- operands ----------------------------------------------------------------------------------------------------------------
@@ -222,23 +223,19 @@ class GriffinLim:
         key = (B, T, iterations, str(dev))
         g = self._graphs.get(key)
         if g is None:
-            g = dict(xa=torch.zeros(B, S, dtype=torch.float32, device=dev), xb=torch.zeros(B, S, dtype=torch.float32, device=dev),
-                     mag=torch.zeros(B, T, N_BINS, dtype=torch.float32, device=dev), frames=torch.zeros(B, dtype=torch.int32, device=dev))
-            self._chain(g['xa'], g['xb'], g['mag'], T * N_BINS, g['frames'], B, T, 1, dev)   # eager warm-up: configures the kernel
+            xa, xb = torch.zeros(B, S, dtype=torch.float32, device=dev), torch.zeros(B, S, dtype=torch.float32, device=dev)
+            mag_s, frames_s = torch.zeros(B, T, N_BINS, dtype=torch.float32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
+            chain = lambda n: self._chain(xa, xb, mag_s, T * N_BINS, frames_s, B, T, n, dev)
+            chain(1)                                                      # eager warm-up on the current stream: configures the kernel
             torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                g['out'] = self._chain(g['xa'], g['xb'], g['mag'], T * N_BINS, g['frames'], B, T, iterations, dev)
-            g['graph'] = graph
+            graph, out = capture(lambda: chain(iterations))
             self.captures += 1
-            if len(self._graphs) >= self.MAX_GRAPHS:
-                self._graphs.pop(next(iter(self._graphs)))
-            self._graphs[key] = g
-        g['xa'].copy_(init)
-        g['mag'].copy_(mag)
-        g['frames'].copy_(frames)
-        g['graph'].replay()
-        return g['out'].clone(), sample_lengths
+            g = self._graphs[key] = Entry([graph], xa=xa, xb=xb, mag=mag_s, frames=frames_s, out=out)
+        g.xa.copy_(init)
+        g.mag.copy_(mag)
+        g.frames.copy_(frames)
+        g.graphs[0].replay()
+        return g.out.clone(), sample_lengths
 
     def peak_normalize(self, x):
         """x (B, S) fp32 on the device -> x / max|x| per row (griffin_lim.py:196).  An all-zero row stays zero; the reference would

@@ -25,20 +25,32 @@ import torch
 from . import ops
 from .durations import get_int_durations
 from .functional import Lengths
+from .graphs import Entry, GraphCache, capture, warm_up
 
 L_STEP, T_STEP = 16, 64
+PADDED = ('symbols', 'dur', 'dur_int', 'energy', 'pitch')     # ``run``'s static buffers of the bucket's L; every other one has its exact shape
 
 
 def _up(n, step):
     return (int(n) + step - 1) // step * step
 
 
+def _stage(static, live, padded):
+    """The live tensors into a graph's static buffers.  The ``padded`` ones are longer on the last axis: zeroed, live rows in front."""
+    for k, v in live.items():
+        if k in padded:
+            static[k].zero_()
+            static[k][..., :v.shape[-1]].copy_(v)
+        else:
+            static[k].copy_(v)
+
+
 class GraphedSynthesizer:
     def __init__(self, model, hparams, max_graphs=32):
         self.model = model.eval()
         self.hparams = hparams
-        self.graphs = {}
-        self.accent_graphs = {}
+        self.graphs = GraphCache(max_graphs, 'least_used')            # per bucket: one graph, its ``static`` inputs, its ``outs``
+        self.accent_graphs = GraphCache(max_graphs, 'least_used')     # ... and its ``out``
         self.max_graphs = max_graphs
 
     # -- host side: exactly the reference's pre-processing, model.py:1068-1087 --------------------------------------------
@@ -73,11 +85,6 @@ class GraphedSynthesizer:
         mel = m.frame_decoder(x, film['frame_decoder'], out_lens)
         return mel, weights
 
-    @staticmethod
-    def _evict(cache, limit):
-        if len(cache) >= limit:
-            del cache[min(cache, key=lambda k: cache[k]['hits'])]
-
     def __call__(self, inputs, pitch_transform, external_prosody, external_embeddings, external_accent_emb, use_graph=True):
         """Same arguments as ``DaftExprt.inference``; returns the same triple."""
         return self.run(self.prepare(inputs, pitch_transform, external_prosody), external_embeddings, external_accent_emb, use_graph)
@@ -101,37 +108,23 @@ class GraphedSynthesizer:
                 key = (B, Lb, Tb, self.model.runtime.precision)
                 entry = self.graphs.get(key)
                 if entry is None:
-                    static = {k: (torch.zeros(B, Lb, dtype=v.dtype, device=dev) if k in ('symbols', 'dur', 'dur_int', 'energy', 'pitch') else v.clone())
-                              for k, v in live.items()}
+                    static = {k: (torch.zeros(B, Lb, dtype=v.dtype, device=dev) if k in PADDED else v.clone()) for k, v in live.items()}
+                    _stage(static, live, PADDED)
                     static['in_exist'] = torch.full((B,), L, dtype=torch.int32, device=dev)      # rows that EXIST on each axis: re-read by
                     static['out_exist'] = torch.full((B,), T, dtype=torch.int32, device=dev)    # every replay (set per call below)
-                    for k in ('symbols', 'dur', 'dur_int', 'energy', 'pitch'):
-                        static[k][:, :L].copy_(live[k])
                     # host-side shape metadata of the BUCKET (lengths as Python ints only size tensors here)
-                    meta = dict(in_host=[Lb] * B, out_host=[Tb] * B, n_frames=Tb)
-                    stream = torch.cuda.Stream()
-                    stream.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(stream):                       # warm-up: packs weights, sets kernel attributes
-                        self._device_forward({**static, **meta})
-                    torch.cuda.current_stream().wait_stream(stream)
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                        outs = self._device_forward({**static, **meta})
-                    self._evict(self.graphs, self.max_graphs)
-                    entry = dict(graph=graph, static=static, outs=outs, hits=0)
-                    self.graphs[key] = entry
-                entry['hits'] += 1
-                static, outs = entry['static'], entry['outs']
+                    forward = lambda: self._device_forward({**static, 'in_host': [Lb] * B, 'out_host': [Tb] * B, 'n_frames': Tb})
+                    warm_up(forward)                                      # packs weights, sets kernel attributes
+                    graph, outs = capture(forward)
+                    entry = self.graphs[key] = Entry([graph], static=static, outs=outs)
+                entry.hits += 1
+                static, outs = entry.static, entry.outs
                 ops.repack_all(self.model.runtime)        # weights changed since capture (load_state_dict, an optimiser step)? one
                                                           # launch rewrites the SAME pack buffers the captured kernels read
-                for k in ('symbols', 'dur', 'dur_int', 'energy', 'pitch'):
-                    static[k].zero_()
-                    static[k][:, :L].copy_(live[k])
-                for k in ('in_lens', 'in_lens_i32', 'out_lens', 'out_lens_i32', 'spk_embs', 'accent_emb'):
-                    static[k].copy_(live[k])
+                _stage(static, live, PADDED)
                 static['in_exist'].fill_(L)
                 static['out_exist'].fill_(T)
-                entry['graph'].replay()
+                entry.graphs[0].replay()
                 mel, weights = outs[0][:, :, :T].clone(), outs[1][:, :L, :T].clone()
         encoder_preds = [prep['dur'], prep['dur_int'], prep['energy'], prep['pitch'], prep['in_lens']]
         return encoder_preds, [mel, out_lens], weights
@@ -156,34 +149,21 @@ class GraphedSynthesizer:
                 return run(frames_energy.contiguous(), frames_pitch.contiguous(), mel_specs.contiguous(), lengths, i32, host)
             Tb = _up(T, T_STEP)
             key = (R, Tb, self.model.runtime.precision)
+            live = dict(e=frames_energy, p=frames_pitch, mel=mel_specs, lens=lengths, i32=i32)
             entry = self.accent_graphs.get(key)
             if entry is None:
                 static = dict(e=torch.zeros(R, Tb, device=dev), p=torch.zeros(R, Tb, device=dev), mel=torch.zeros(R, n_mel, Tb, device=dev),
                               lens=lengths.clone(), i32=i32.clone())
-                args = lambda: (static['e'], static['p'], static['mel'], static['lens'], static['i32'], [Tb] * R)
-                stream = torch.cuda.Stream()
-                stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(stream):
-                    run(*args())
-                torch.cuda.current_stream().wait_stream(stream)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                    out = run(*args())
-                self._evict(self.accent_graphs, self.max_graphs)
-                entry = dict(graph=graph, static=static, out=out, hits=0)
-                self.accent_graphs[key] = entry
-            entry['hits'] += 1
-            static = entry['static']
+                _stage(static, live, ('e', 'p', 'mel'))
+                forward = lambda: run(static['e'], static['p'], static['mel'], static['lens'], static['i32'], [Tb] * R)
+                warm_up(forward)
+                graph, out = capture(forward)
+                entry = self.accent_graphs[key] = Entry([graph], static=static, out=out)
+            entry.hits += 1
             ops.repack_all(self.model.runtime)
-            for k, v in (('e', frames_energy), ('p', frames_pitch)):
-                static[k].zero_()
-                static[k][:, :T].copy_(v)
-            static['mel'].zero_()
-            static['mel'][:, :, :T].copy_(mel_specs)
-            static['lens'].copy_(lengths)
-            static['i32'].copy_(i32)
-            entry['graph'].replay()
-            return entry['out'].clone()
+            _stage(entry.static, live, ('e', 'p', 'mel'))
+            entry.graphs[0].replay()
+            return entry.out.clone()
 
     def accent_embedding(self, frames_energy, frames_pitch, mel_specs, lengths, use_graph=True):
         """The averaged accent embedding (1, 128) of scripts/synthesize.py:446-448."""

@@ -62,6 +62,7 @@ import torch
 from . import ops
 from .ddp import GradientReducer
 from .functional import Lengths
+from .graphs import Entry, GraphCache, capture, warm_up
 from .loss import LossTerms
 from .hparams import loss_scale_config
 from .optim import FusedAdam, LossScaler, update_learning_rate
@@ -110,11 +111,6 @@ PHASE_NAMES = ('A: forward, loss, backward of decoder / upsampler / phoneme enco
                'D: backward of prenet layer 0')
 
 
-class _StepGraphs:
-    """The captured graphs (one per backward phase) of one padded batch shape with their static inputs and outputs."""
-    __slots__ = ('graphs', 'inputs', 'loss', 'terms_dev', 'hits')
-
-
 class Trainer:
     def __init__(self, model, criterion, hparams, conditioner=None, process_group=None, bucket_mb=16.0, grad_sink=True,
                  use_graphs=True, max_graphs=16, cuts='auto', bucket=None):
@@ -148,8 +144,8 @@ class Trainer:
         scale_cfg = loss_scale_config(hparams)
         self._fp16_loss_scale = scale_cfg['loss_scale']
         self.scaler = LossScaler(scale_cfg, self.device) if scale_cfg['dynamic'] and model.runtime.precision == 'fp16' else None
-        self.graphs = {}
-        self.val_graphs = {}
+        self.graphs = GraphCache(self.max_graphs, 'least_used')      # per padded shape: one graph per backward phase, static ``inputs``,
+        self.val_graphs = GraphCache(self.max_graphs, 'oldest')      # captured ``loss`` and ``terms_dev``
         self._conditioner_generation = getattr(conditioner, 'generation', None)
         self.adv_weight = torch.zeros((), dtype=torch.float32, device=self.device)    # read by the captured loss
         self.val_adv_weight = torch.zeros((), dtype=torch.float32, device=self.device)   # validation: iteration = 0 (train.py:198)
@@ -281,29 +277,21 @@ class Trainer:
     def _capture(self, parsed, key):
         """One graph per backward phase for this padded shape.  One eager step on a side stream first (kernel attributes, weight
         packs, allocator), with the optimiser NOT applied: the captured step then sees the same state a replay will."""
-        g = _StepGraphs()
         static = self._static_inputs(parsed)
-        rt = self.model.runtime
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            _, _, rest = self._phases(static, self.adv_weight, lambda gid: None)
-            for run in rest:
+        phase_a = lambda: self._phases(static, self.adv_weight, lambda gid: None)
+
+        def whole_step():
+            for run in phase_a()[2]:
                 run()
-        torch.cuda.current_stream().wait_stream(side)
-        g.graphs = [torch.cuda.CUDAGraph() for _ in range(self.cut_levels + 1)]
-        # thread_local: CUDA calls of OTHER threads (the RCCL watchdog polling its events, a pinned-memory loader) must not abort the capture
-        with torch.cuda.graph(g.graphs[0], capture_error_mode='thread_local'):
-            rt.seed_offset.add_(1)                            # a new dropout stream per replay (the seeds in the launches are frozen)
-            g.loss, terms, rest = self._phases(static, self.adv_weight, lambda gid: None)
-        g.terms_dev = [t._device_terms for t in terms]        # static device tensors: wrapped anew after every replay
-        for graph, run in zip(g.graphs[1:], rest):
-            with torch.cuda.graph(graph, pool=g.graphs[0].pool(), capture_error_mode='thread_local'):
-                run()
-        g.inputs, g.hits = static, 0
-        if len(self.graphs) >= self.max_graphs:               # evict the least used shape (its pool is freed with it)
-            del self.graphs[min(self.graphs, key=lambda q: self.graphs[q].hits)]
-        self.graphs[key] = g
+
+        def first():
+            self.model.runtime.seed_offset.add_(1)            # a new dropout stream per replay (the seeds in the launches are frozen)
+            return phase_a()
+        warm_up(whole_step)
+        head, (loss, terms, rest) = capture(first)
+        later = [capture(run, pool=head.pool())[0] for run in rest]      # phases B-D
+        g = Entry([head] + later, inputs=static, loss=loss, terms_dev=[t._device_terms for t in terms])   # static device tensors: wrapped
+        self.graphs[key] = g                                  # anew after every replay; a full cache drops its least used shape first
         return g
 
     def _check_conditioner(self):
@@ -427,21 +415,12 @@ class Trainer:
         return out + (kept,) if keep_outputs else out
 
     def _capture_val(self, parsed, key):
-        g = _StepGraphs()
         static = self._static_inputs(parsed)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._val_forward(*static[0])                        # warm-up outside the capture
-        torch.cuda.current_stream().wait_stream(side)
-        g.graphs = [torch.cuda.CUDAGraph()]
-        with torch.cuda.graph(g.graphs[0], capture_error_mode='thread_local'):
-            g.loss, indiv = self._val_forward(*static[0])
-        g.terms_dev = [indiv._device_terms]
-        g.inputs, g.hits = static, 0
-        if len(self.val_graphs) >= self.max_graphs:
-            self.val_graphs.pop(next(iter(self.val_graphs)))
-        self.val_graphs[key] = g
+        forward = lambda: self._val_forward(*static[0])
+        warm_up(forward)
+        graph, (loss, indiv) = capture(forward)
+        g = Entry([graph], inputs=static, loss=loss, terms_dev=[indiv._device_terms])
+        self.val_graphs[key] = g                              # a full cache drops its oldest shape first
         return g
 
     def note_loss(self, value: float):

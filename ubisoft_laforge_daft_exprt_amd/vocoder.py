@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from ._lib import lib, packed as _packed, stream as _stream
+from .graphs import capture
 
 NEG_SLOPE = 0.1     # leaky-ReLU slope before every convolution (applied inside the kernels)
 HOP = 256           # waveform samples per mel frame: the product of the four upsampling factors
@@ -602,11 +603,8 @@ class VocoderStream:
             if self.graph is not None:
                 self.graph.replay()
             elif self.use_graph and self.done == 1:       # chunk 0 ran eagerly (first audio as early as possible, and the warm-up)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                    self._launch()
-                self.graph, self.captures = graph, self.captures + 1
-                graph.replay()
+                self.graph, self.captures = capture(self._launch)[0], self.captures + 1
+                self.graph.replay()
             else:
                 self._launch()
         valid = self.valid[self.done]
