@@ -30,10 +30,6 @@ extern "C" {
 /* ---- runtime ----------------------------------------------------------------------------------------------------- */
 int dx_version(void);
 const char* dx_last_error(void);
-/* HIP-event bracketing of one kernel family (0 conv GEMM, 1 weight-grad GEMM, 2 attention fwd, 3 attention bwd,
- * 4 upsampler fwd, 5 LayerNorm rows); used by bench.py to time the dominant kernel inside the timed region. */
-int dx_prof_enable(int kind, int capacity);
-int dx_prof_collect(int kind, int* launches, double* total_ms);
 
 /* ---- host-side integer durations: DaftExprt.get_int_durations, model.py:950-973 -> duration_to_integer, extract_features.py:69-125 ----
  * HOST pointers, no GPU work.  dur: (B, L) seconds, already thresholded (values < filter_length / sampling_rate / 2 set to 0);
@@ -102,8 +98,43 @@ typedef struct DxWgradJob {
   const int* rows_exist;      /* optional, as in dx_conv_wgrad (after `reserved`: the earlier fields keep their offsets) */
 } DxWgradJob;
 int dx_conv_wgrad_batched(const void* jobs, int njobs, int taps, int dy_bf16, int x_bf16, void* stream);
-/* grad (Cout, Cin, taps) (+)= G[taps][Cout][Cin]   (re-layout helper; dx_conv_wgrad itself now writes the parameter layout) */
-int dx_unpack_wgrad(const float* G, float* grad, int Cout, int Cin, int taps, int accumulate, void* stream);
+/* ---- launch plans: which kernel a dispatcher picks for a shape, at which tile width and grid ---------------------------------------
+ * Host code only: no device pointer, no stream, no HIP call (they answer on a machine without a GPU).  Each dispatcher above and below
+ * calls its plan function and switches on the record, so a rule is stated once; profiling.py and the tests ask here too.  All five fill
+ * one record of DX_PLAN_INTS ints (fields a family does not use are 0).  The arguments are the dispatcher's own, the scalars the
+ * decision depends on; dx_ln_plan: backward != 0 plans dx_ln_bwd.  The _f16 twins answer alike and reject operand mode 2. */
+#define DX_PLAN_INTS 14
+#define DX_PLAN_KERNEL 0         /* one of the DX_K_* ids below */
+#define DX_PLAN_TOK 1            /* tokens (conv, feed-forward pair) or rows (LayerNorm) one workgroup owns per pass */
+#define DX_PLAN_GRID_X 2         /* the launch dimensions: grid x, y, z and threads per workgroup */
+#define DX_PLAN_GRID_Y 3
+#define DX_PLAN_GRID_Z 4
+#define DX_PLAN_THREADS 5
+#define DX_PLAN_SPLIT 6          /* weight gradients: split-K (== grid z) */
+#define DX_PLAN_CHUNK 7          /* weight gradients: tokens per K chunk */
+#define DX_PLAN_ROUNDS 8         /* batched weight gradient: rounds of workgroups */
+#define DX_PLAN_SWEEP 9          /* dx_ln_fwd: rows one pass of the grid covers */
+#define DX_PLAN_PASSES 10        /* dx_ln_fwd: passes of its grid-stride loop */
+#define DX_PLAN_COUTP 11         /* dx_conv_gemm: the pack's padded dimensions (dims[0], dims[1] of dx_pack_dims for that mode) */
+#define DX_PLAN_CINP 12
+#define DX_PLAN_SWIZZLE 13       /* deep-K conv: the XCD swizzle width the grid was rounded for (0: none) */
+#define DX_K_CONV_GEMM_F32 1     /* conv_gemm_kernel<float>: tiled, 64 or 128 tokens */
+#define DX_K_CONV_GEMM_H16 2     /* conv_gemm_kernel<16-bit> */
+#define DX_K_CONV_GEMM_SPLIT 3   /* conv_gemm_kernel<split bf16> */
+#define DX_K_CONV_WS 4           /* conv_ws_kernel: weight-stationary, CinP == 128 */
+#define DX_K_CONV_DK 5           /* conv_dk_kernel: deep-K, CinP >= 256 */
+#define DX_K_WGRAD_F32 6         /* wgrad_kernel (also the 16-bit modes' fallback for dimensions that are no multiple of 8) */
+#define DX_K_WGRAD_SPLIT 7       /* wgrad_split_kernel */
+#define DX_K_WGRAD_H16 8         /* wgrad_bf16_kernel, 64 input channels per workgroup (256 threads) */
+#define DX_K_WGRAD_H16_WIDE 9    /* wgrad_bf16_kernel, 128 input channels per workgroup (512 threads); every batched launch */
+#define DX_K_FF_PAIR 10          /* ff_pair_kernel: 126- or 62-token tiles */
+#define DX_K_LN_FWD 11           /* ln_fwd_kernel */
+#define DX_K_LN_BWD 12           /* ln_bwd_kernel: THREADS / 64 waves, TOK rows per block */
+int dx_conv_gemm_plan(int B, int N, int Cin, int Cout, int taps, int bf16, int ldx, int* plan);
+int dx_conv_wgrad_plan(int B, int N, int Cin, int Cout, int taps, int bf16, int ldx, int ldy, int dy_bf16, int x_bf16, int* plan);
+int dx_conv_wgrad_batched_plan(const void* jobs, int njobs, int taps, int dy_bf16, int x_bf16, int* plan);
+int dx_ff_pair_plan(int B, int N, int* plan);
+int dx_ln_plan(int B, int N, int C, int backward, int* plan);
 /* Fused conv feed-forward pair (model.py:206-217 PositionWiseConvFF.forward: conv k3 128->F, ReLU, conv k3 F->128) and the
  * input-gradient chain of the same pair, bf16 MFMA operands, ONE launch; the F-wide hidden tensor is consumed from LDS.
  *   Y[b,n,:] (+)= bias_b + conv3(Wb, Hm)[b,n,:],   Hm = mid(bias_a + conv3(Wa, X)),  H <- Hm (bf16, kept for the weight gradients)

@@ -1,4 +1,4 @@
-"""Float64 references, per-element bounds and launch-path predicates for the GEMM family (csrc/dx_gemm.hip, csrc/dx_ffpair.hip).
+"""Float64 references, per-element bounds and the library's launch plans for the GEMM family (csrc/dx_gemm.hip, csrc/dx_ffpair.hip).
 
 The reference of every checked element is float64 arithmetic on exactly the operands the device multiplies: weights rounded as the
 pack rounds them (``w.to(h16)``, RNE), f32-stored activations rounded where the kernel converts them, 16-bit-stored activations as
@@ -212,7 +212,7 @@ def pick_lens(B, N, tile, rotate=0, open_halo=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the host-side launch plan, restated (dx_pack_dims, dx_conv_gemm, launch_conv, dx_conv_wgrad, ff_pair_launch)
+# the host-side launch plan: the library's own answer (the dx_*_plan entry points, include/daft_exprt_hip.h), restated nowhere
 # ---------------------------------------------------------------------------------------------------------------------------
 def _cdiv(a, b):
     return -(-a // b)
@@ -222,56 +222,52 @@ def _roundup(a, b):
     return _cdiv(a, b) * b
 
 
-def pack_dims(Cout, Cin, half):
-    bk = 64 if half else 32
-    return [_roundup(Cout, TILE), _roundup(Cin, bk), _roundup(Cin, TILE), _roundup(Cout, bk)]
+OPERAND_MODE = {'f32': 0, 'bf16': 1, 'fp16': 1, 'bf16x3': 2}
+# how the tables of test_gemm_exact_gpu.py name a plan's kernel (Plan.kernel: the header's DX_K_* names)
+PATH = {'conv_gemm_f32': 'f32_{tok}', 'conv_gemm_h16': 'h16_{tok}', 'conv_gemm_split': 'split_{tok}', 'conv_ws': 'ws', 'conv_dk': 'dk',
+        'wgrad_f32': 'f32', 'wgrad_split': 'split', 'wgrad_h16': 'narrow', 'wgrad_h16_wide': 'wide'}
 
 
-def conv_path(mode, B, N, Cin, Cout, taps, ldx=None):
-    """The kernel dx_conv_gemm launches for this shape: 'f32_64' / 'f32_128' / 'h16_64' / 'h16_128' (tiled, tokens per tile), 'ws'
-    (weight-stationary) or 'dk' (deep-K)."""
-    ldx = Cin if ldx is None else ldx
-    half = mode != 'f32'
-    CoutP, CinP = pack_dims(Cout, Cin, half)[:2]
-    if half and CinP >= 256 and Cin % 64 == 0 and B * N * ldx < 2 ** 31:
-        return 'dk'
-    if half and CinP == 128 and B * _cdiv(N, 128) >= 64:
-        return 'ws'
-    small_below = 1024 if (not half or taps == 1) else 0
-    small = B * _cdiv(N, TILE) * (CoutP // TILE) < small_below
-    return ('h16_' if half else 'f32_') + ('64' if small else '128')
+def _plan(entry, mode, *args):
+    from ubisoft_laforge_daft_exprt_amd import _lib
+    return _lib.plan(entry + ('_f16' if mode == 'fp16' else ''), *args)
+
+
+def path(plan):
+    return PATH[plan.kernel].format(tok=plan.tok)
+
+
+def conv_plan(mode, B, N, Cin, Cout, taps, ldx=None):
+    """what dx_conv_gemm launches for this shape (``.coutp`` / ``.cinp``: the pack's padded dimensions)"""
+    return _plan('dx_conv_gemm_plan', mode, B, N, Cin, Cout, taps, OPERAND_MODE[mode], Cin if ldx is None else ldx)
+
+
+def wgrad_plan(mode, B, N, Cin, Cout, taps, dy16=False, x16=False, ldx=None, ldy=None):
+    """what dx_conv_wgrad launches (``.chunk``: tokens per K chunk)"""
+    return _plan('dx_conv_wgrad_plan', mode, B, N, Cin, Cout, taps, OPERAND_MODE[mode], Cin if ldx is None else ldx, Cout if ldy is None else ldy,
+                 int(dy16), int(x16))
+
+
+def wgrad_batched_plan(mode, taps, jobs, dy16=False, x16=False):
+    """what dx_conv_wgrad_batched launches for jobs of these (B, N, Cin, Cout) (``.rounds``: rounds of workgroups)"""
+    import ctypes
+    recs = b''.join(struct.pack('<5Q8iQ', 0, 0, 0, 0, 0, Cout, Cin, B, N, Cin, Cout, -1, 0, 0) for B, N, Cin, Cout in jobs)     # DxWgradJob, pointers null
+    buf = ctypes.create_string_buffer(recs)
+    return _plan('dx_conv_wgrad_batched_plan', mode, ctypes.addressof(buf), len(jobs), taps, int(dy16), int(x16))
+
+
+def ff_pair_plan(B, N, mode='bf16'):
+    """what the fused feed-forward pair launches (``.tok``: output tokens per workgroup)"""
+    return _plan('dx_ff_pair_plan', mode, B, N)
 
 
 LIVE_TILE_ROWS = 1024        # DK_MAX_B: batch rows the weight-stationary / deep-K kernels number live token tiles for
 
 
 def plain_tile_order(B):
-    """True when the weight-stationary / deep-K kernels fall back to the plain (b, tile) order and per-row limits read from memory"""
+    """True when the weight-stationary / deep-K kernels fall back to the plain (b, tile) order and per-row limits read from memory.
+    Decided inside the kernels (``a.B <= DK_MAX_B`` in conv_ws_kernel / conv_dk_kernel), not by host code: no plan reports it."""
     return B > LIVE_TILE_ROWS
-
-
-def wgrad_chunk(taps, dy16, x16):
-    """tokens per chunk of the 16-bit weight-gradient kernel (wb_bk)"""
-    return 128 if (taps == 1 or (dy16 and x16)) else 64
-
-
-def wgrad_path(mode, Cin, Cout, ldx=None, ldy=None):
-    """'f32' (32-token chunks; also the 16-bit modes' fallback when a dimension is not a multiple of 8), 'narrow' or 'wide'."""
-    ldx, ldy = Cin if ldx is None else ldx, Cout if ldy is None else ldy
-    if mode == 'f32' or not (Cin % 8 == 0 and ldx % 8 == 0 and Cout % 8 == 0 and ldy % 8 == 0):
-        return 'f32'
-    return 'wide' if Cin % 128 == 0 and _cdiv(Cout, TILE) * _cdiv(Cin, 64) >= 64 else 'narrow'
-
-
-def wgrad_batch_rounds(shapes):
-    """rounds of workgroups dx_conv_wgrad_batched runs for jobs of these (Cin, Cout)"""
-    tile_jobs = sum(_cdiv(co, TILE) * (ci // 128) for ci, co in shapes)
-    return max(1, (tile_jobs * 4 + 128) // 256)
-
-
-def ff_pair_tile(B, N):
-    """output tokens per workgroup of the fused feed-forward pair"""
-    return 126 if B * _cdiv(N, 126) >= 96 else 62
 
 
 PACK_MAX = 60                # descriptors per launch of dx_pack_weights_host

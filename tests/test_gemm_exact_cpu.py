@@ -243,20 +243,23 @@ def test_exclusion_cap_and_region_cover():
 
 
 def test_launch_plan_predicates():
-    """the shapes of test_gemm_exact_gpu.py land on the paths their table claims"""
-    assert gx.conv_path('f32', 3, 129, 80, 136, 3) == 'f32_64' and gx.conv_path('f32', 5, 1, 192, 128, 1) == 'f32_64'
-    assert gx.conv_path('f32', 64, 200, 64, 1024, 3) == 'f32_128' and gx.conv_path('f32', 64, 200, 64, 1024, 1) == 'f32_128'
-    assert gx.conv_path('bf16', 4, 37, 192, 384, 1) == 'h16_64' and gx.conv_path('fp16', 3, 150, 128, 384, 1) == 'h16_64'
+    """the shapes of test_gemm_exact_gpu.py land on the paths their table claims: asked of the library's own dispatch rule"""
+    conv = lambda *a, **k: gx.path(gx.conv_plan(*a, **k))
+    wgrad = lambda mode, Cin, Cout: gx.path(gx.wgrad_plan(mode, 2, 130, Cin, Cout, 1))
+    chunk = lambda taps, dy16, x16: gx.wgrad_plan('bf16', 2, 130, 128, 136, taps, dy16, x16).chunk
+    assert conv('f32', 3, 129, 80, 136, 3) == 'f32_64' and conv('f32', 5, 1, 192, 128, 1) == 'f32_64'
+    assert conv('f32', 64, 200, 64, 1024, 3) == 'f32_128' and conv('f32', 64, 200, 64, 1024, 1) == 'f32_128'
+    assert conv('bf16', 4, 37, 192, 384, 1) == 'h16_64' and conv('fp16', 3, 150, 128, 384, 1) == 'h16_64'
     for shape in ((3, 150, 128, 1024, 3), (2, 130, 80, 136, 3), (4, 130, 288, 128, 3), (64, 200, 192, 1024, 1)):
-        assert gx.conv_path('bf16', *shape) == 'h16_128', shape
-    assert gx.pack_dims(128, 288, 1)[1] == 320
-    assert gx.conv_path('bf16', 13, 640, 80, 136, 3) == 'ws' and gx.conv_path('bf16', 13, 640, 128, 384, 1) == 'ws'
-    assert gx.conv_path('bf16', 12, 640, 128, 384, 1) == 'h16_64'                      # 60 token tiles: below the threshold
-    assert gx.conv_path('bf16', 4, 300, 256, 128, 3) == 'dk' and gx.conv_path('bf16', 4, 300, 320, 80, 1) == 'dk'
-    assert gx.conv_path('bf16', 1100, 130, 256, 128, 3) == 'dk' and gx.conv_path('bf16', 1100, 130, 128, 256, 1) == 'ws'
+        assert conv('bf16', *shape) == 'h16_128', shape
+    assert gx.conv_plan('bf16', 1, 1, 288, 128, 1).cinp == 320
+    assert conv('bf16', 13, 640, 80, 136, 3) == 'ws' and conv('bf16', 13, 640, 128, 384, 1) == 'ws'
+    assert conv('bf16', 12, 640, 128, 384, 1) == 'h16_64'                      # 60 token tiles: below the threshold
+    assert conv('bf16', 4, 300, 256, 128, 3) == 'dk' and conv('bf16', 4, 300, 320, 80, 1) == 'dk'
+    assert conv('bf16', 1100, 130, 256, 128, 3) == 'dk' and conv('bf16', 1100, 130, 128, 256, 1) == 'ws'
     assert gx.plain_tile_order(1100) and not gx.plain_tile_order(1024)
-    assert gx.wgrad_path('f32', 80, 136) == 'f32' and gx.wgrad_path('bf16', 192, 4) == 'f32'
-    assert gx.wgrad_path('bf16', 128, 384) == 'narrow' and gx.wgrad_path('bf16', 256, 136) == 'narrow'
-    assert gx.wgrad_path('fp16', 1024, 512) == 'wide'
-    assert gx.wgrad_chunk(3, True, False) == 64 and gx.wgrad_chunk(3, True, True) == 128 and gx.wgrad_chunk(1, False, False) == 128
-    assert gx.ff_pair_tile(4, 127) == 62 and gx.ff_pair_tile(32, 379) == 126 and gx.ff_pair_tile(23, 379) == 62
+    assert wgrad('f32', 80, 136) == 'f32' and wgrad('bf16', 192, 4) == 'f32'
+    assert wgrad('bf16', 128, 384) == 'narrow' and wgrad('bf16', 256, 136) == 'narrow'
+    assert wgrad('fp16', 1024, 512) == 'wide'
+    assert chunk(3, True, False) == 64 and chunk(3, True, True) == 128 and chunk(1, False, False) == 128
+    assert gx.ff_pair_plan(4, 127).tok == 62 and gx.ff_pair_plan(32, 379).tok == 126 and gx.ff_pair_plan(23, 379).tok == 62

@@ -87,7 +87,7 @@ def conv_case(ops, mode, path, B, N, Cin, Cout, taps, transpose):
         for x16 in ([False, True] if h16 else [False]):
             xin = x32.to(h16) if x16 else x32
             tag = f'{path} {mode} x16={x16} T={transpose}'
-            assert gx.conv_path(mode, B, N, Cin, Cout, taps) == path and gx.plain_tile_order(B) == (B == 1100)
+            assert gx.path(gx.conv_plan(mode, B, N, Cin, Cout, taps)) == path and gx.plain_tile_order(B) == (B == 1100)
             acc, S = gx.conv64(gx.operand64(xin, mode), w64, bias)
             kw = dict(transpose=transpose)
 
@@ -135,7 +135,7 @@ def conv_case(ops, mode, path, B, N, Cin, Cout, taps, transpose):
             # x = a column slice of a wider tensor: ldx > Cin
             wide = wide32.to(h16) if x16 else wide32
             xs = wide[:, :, 32:32 + Cin]
-            assert gx.conv_path(mode, B, N, Cin, Cout, taps, ldx=Cin + 64) == path
+            assert gx.path(gx.conv_plan(mode, B, N, Cin, Cout, taps, ldx=Cin + 64)) == path
             acc_s, S_s = gx.conv64(gx.operand64(xs, mode), w64, bias)
             y = ops.conv_gemm(xs, pack, bias, **kw)
             worst = max(worst, gx.check(y, acc_s, S_s, q=q, what=f'{tag} strided x').assert_ok())
@@ -174,7 +174,7 @@ def test_one_changed_operand_is_seen_in_the_device_result(ops, mode):
     B, N, Cin, Cout = 2, 130, 1024, 128
     ops.set_precision(mode)
     try:
-        assert gx.conv_path(mode, B, N, Cin, Cout, 3) == ('f32_64' if mode == 'f32' else 'dk')
+        assert gx.path(gx.conv_plan(mode, B, N, Cin, Cout, 3)) == ('f32_64' if mode == 'f32' else 'dk')
         w = randn(Cout, Cin, 3, seed=1, scale=1.0 / math.sqrt(3 * Cin))
         pack = ops.PackedWeight(w)
         x = randn(B, N, Cin, seed=3)
@@ -209,7 +209,7 @@ def wgrad_case(ops, mode, path, B, N, Cin, Cout, taps):
     worst = 0.0
     ops.set_precision(mode)
     try:
-        assert 'wgrad_' + gx.wgrad_path(mode, Cin, Cout) == path
+        assert 'wgrad_' + gx.path(gx.wgrad_plan(mode, B, N, Cin, Cout, taps)) == path
         on16 = h16 is not None and path != 'wgrad_f32'          # the fallback takes fp32-stored operands only ...
         opmode = mode if on16 else 'f32'                        # ... and multiplies them unrounded
         w = randn(*((Cout, Cin) + ((3,) if taps == 3 else ())), seed=1, scale=0.05)
@@ -218,7 +218,8 @@ def wgrad_case(ops, mode, path, B, N, Cin, Cout, taps):
         g0 = randn(*w.shape, seed=4)
         n_ax = torch.arange(N, device=DEV)[None, :, None]
         for dy16, x16 in ([(a, b) for a in (False, True) for b in (False, True)] if on16 else [(False, False)]):
-            chunk = gx.wgrad_chunk(taps, dy16, x16) if path != 'wgrad_f32' else 32
+            chunk = gx.wgrad_plan(mode, B, N, Cin, Cout, taps, dy16, x16).chunk
+            assert path != 'wgrad_f32' or chunk == 32
             ll = gx.pick_lens(B, N, chunk, int(dy16) + 2 * int(x16))
             lens = i32(ll)
             re = i32([max(1, n - 3) if b % 2 == 0 else min(N, n + 5) for b, n in enumerate(ll)])
@@ -261,7 +262,7 @@ def test_wgrad_batched_launch(ops, mode, taps, dy16, x16):
     ops.set_precision(mode)
     try:
         geo = [(2, 100, 128, 128), (3, 77, 128, 384), (2, 130, 256, 128), (1, 65, 128, 1024)]
-        chunk = gx.wgrad_chunk(taps, dy16, x16)
+        chunk = gx.wgrad_plan(mode, *geo[0], taps, dy16, x16).chunk
         jobs = []
         rt.defer_wgrad = True
         for i in range(34):
@@ -284,7 +285,7 @@ def test_wgrad_batched_launch(ops, mode, taps, dy16, x16):
         per_launch = ops.WGRAD_BATCH[taps]
         order = sorted(jobs, key=lambda j: -j[0])                            # flush_wgrads launches the largest B * N first
         if taps == 1:                                                        # (the k = 3 launches take 8 layers: one round)
-            assert gx.wgrad_batch_rounds([(j[1], j[2]) for j in order[:per_launch]]) > 1
+            assert gx.wgrad_batched_plan(mode, taps, [(1, j[0], j[1], j[2]) for j in order[:per_launch]], dy16, x16).rounds > 1      # (B * N as one row)
         assert ops.flush_wgrads(rt) == -(-34 // per_launch) and not rt.wgrad_queue
         worst = 0.0
         for i, (_, Cin, Cout, dyin, xin, start, gw, gb, pack, re) in enumerate(jobs):
@@ -319,7 +320,7 @@ def test_ff_pair_forward_and_backward(ops, tok, B, N, lens_l, Fc, mode):
     q = BAR[path]
     ops.set_precision(mode)
     try:
-        assert gx.ff_pair_tile(B, N) == tok
+        assert gx.ff_pair_plan(B, N, mode).tok == tok
         lens = i32(lens_l)
         full = i32([N] * B)
         w1, b1 = randn(Fc, 128, 3, seed=1, scale=1 / math.sqrt(384)), randn(Fc, seed=2, scale=0.1)
@@ -390,7 +391,8 @@ def test_pack_routes_write_the_images_of_a_fresh_pack(ops, mode):
     fresh = []
     for pk in packs:
         img = pk._image(mode)
-        assert img.dims == gx.pack_dims(pk.cout, pk.cin, half)
+        fwd, bwd = gx.conv_plan(mode, 1, 1, pk.cin, pk.cout, 1), gx.conv_plan(mode, 1, 1, pk.cout, pk.cin, 1)      # the input-gradient conv swaps the channels
+        assert img.dims == [fwd.coutp, fwd.cinp, bwd.coutp, bwd.cinp]
         f, b = torch.empty_like(img.fwd), torch.empty_like(img.bwd)
         poison(f), poison(b)
         ops._fn('dx_pack_weights', mode)(pk.weight.data_ptr(), f.data_ptr(), b.data_ptr(), pk.cout, pk.cin, pk.taps, half, ops._stream())

@@ -79,11 +79,12 @@ def test_every_kind_of_input_is_what_its_name_says(shape):
 
 
 def test_launch_rules_restated():
-    assert lx.bwd_form(64, 257, 128) == (16, 192) and lx.bwd_form(1, 16383, 128) == (4, 64) and lx.bwd_form(1, 16384, 128) == (16, 192)
-    assert lx.bwd_form(64, 257, 1024) == (4, 32)
+    """asked of the library's own plans (dx_ln_plan, dx_ff_pair_plan): a changed threshold in csrc/ fails here"""
+    assert lx.bwd_waves_rows(64, 257, 128) == (16, 192) and lx.bwd_waves_rows(1, 16383, 128) == (4, 64) and lx.bwd_waves_rows(1, 16384, 128) == (16, 192)
+    assert lx.bwd_waves_rows(64, 257, 1024) == (4, 32)
     for C in (128, 1024):
-        assert lx.fwd_rows_per_sweep(40000, C) == 32768 and lx.fwd_passes(32768, C) == 1 and lx.fwd_passes(lx.WRAP['B'] * lx.WRAP['N'], C) == 2
-    assert lx.ff_tile(5, 300) == 62 and lx.ff_tile(35, 300) == 126
+        assert lx.ln_plan(1, 40000, C).sweep == 32768 and lx.ln_plan(1, 32768, C).passes == 1 and lx.ln_plan(lx.WRAP['B'], lx.WRAP['N'], C).passes == 2
+    assert lx.ff_pair_tok(5, 300) == 62 and lx.ff_pair_tok(35, 300) == 126
     assert lx.thresh(0.1) == 6554 and lx.thresh(0.5) == 32768 and lx.inv_keep(0.75) == 4.0
 
 
@@ -187,7 +188,7 @@ def test_skipped_second_grid_stride_pass_leaves_the_sentinel():
     """the forward's wrap case restates a row subset: rows from 32 700 on are in it, so rows a skipped second pass leaves unwritten are seen"""
     rows = lx.wrap_rows()
     total = lx.WRAP['B'] * lx.WRAP['N']
-    assert lx.fwd_passes(total, 128) == 2 and int((rows >= lx.fwd_rows_per_sweep(total, 128)).sum()) == total - 32768 and len(rows) <= 400
+    assert lx.ln_plan(lx.WRAP['B'], lx.WRAP['N'], 128).passes == 2 and int((rows >= lx.ln_plan(lx.WRAP['B'], lx.WRAP['N'], 128).sweep).sum()) == total - 32768 and len(rows) <= 400
     c = lx.rounded_case('randn', C=128, lens=lx.wrap_lens(), with_dy=False, **lx.WRAP)
     z, _ = lx.make_z(c, rows)
     ref, bound = lx.ln_stage(c, rows, z), lx.stage_bounds(c, rows, z, 11)

@@ -197,7 +197,7 @@ LN_BWD_EXACT = ['c128_w4', 'c128_w16', 'c1024_f32', 'c1024_bf16', 'c1024_fp16']
 @pytest.mark.parametrize('name', LN_BWD_EXACT)
 def test_exact_backward_tier_is_bitwise(lib, name, p_pre, p_post):
     kw = lx.EXACT_BWD[name]
-    assert lx.bwd_form(kw['B'], kw['N'], kw['C']) == ((16, 192) if name == 'c128_w16' else (4, 32 if kw['C'] == 1024 else 64))
+    assert lx.bwd_waves_rows(kw['B'], kw['N'], kw['C']) == ((16, 192) if name == 'c128_w16' else (4, 32 if kw['C'] == 1024 else 64))
     for film in (True, False):
         c = lx.exact_bwd_case(p_pre=p_pre, p_post=p_post, film=film, **kw)
         ref = lx.ln_backward(c, c['z'], c['mean'], c['rstd'])
@@ -213,7 +213,7 @@ def test_16383_rows_take_four_waves_16384_sixteen_and_the_shared_rows_agree(lib)
     outs = {}
     for name, form in (('c128_16383', (4, 64)), ('c128_16384', (16, 192))):
         kw = lx.EXACT_BWD[name]
-        assert lx.bwd_form(kw['B'], kw['N'], kw['C']) == form
+        assert lx.bwd_waves_rows(kw['B'], kw['N'], kw['C']) == form
         c = lx.exact_bwd_case(**kw)
         out = run_bwd(lib, c, c['z'], c['mean'], c['rstd'], shadow=True)
         assert_exact_backward(c, out, lx.ln_backward(c, c['z'], c['mean'], c['rstd']), name)
@@ -245,7 +245,7 @@ def ff_setup(ops, c, build, zero_first=False):
 
 def ff_live(c):
     """(B, N) bool: rows in a token tile that starts below min(len + 1, N): the tiles the pair computes (skip_halo = 1)"""
-    tok = lx.ff_tile(c['B'], c['N'])
+    tok = lx.ff_pair_tok(c['B'], c['N'])
     lim = (torch.tensor(c['lens']) + 1).clamp(max=c['N'])
     return (torch.arange(c['N'])[None, :] // tok) < ((lim + tok - 1) // tok)[:, None]
 
@@ -256,7 +256,7 @@ FF = [('bf16', 'ff_62'), ('fp16', 'ff_62'), ('bf16', 'ff_126'), ('fp16', 'ff_126
 def ff_case(name, p_pre, film=False, seed=0):
     c = lx.exact_bwd_case(p_pre=p_pre, p_post=0.0, film=film, seed=seed, **lx.EXACT_BWD[name])
     c['ld_film'] = 256 + 4
-    assert lx.ff_tile(c['B'], c['N']) == (62 if name == 'ff_62' else 126)
+    assert lx.ff_pair_tok(c['B'], c['N']) == (62 if name == 'ff_62' else 126)
     return c
 
 
@@ -410,7 +410,7 @@ def test_rounded_tier_forward_and_backward(lib, shape, kind):
     n = lx.TREE_N[('rowvec', C)]
     rows = lx.all_rows(c)
     valid = valid_mask(c)
-    assert lx.bwd_form(B, N, C) == ((16, 192) if shape == 'big' else (4, 32 if C == 1024 else 64)) and lx.fwd_passes(B * N, C) == 1
+    assert lx.bwd_waves_rows(B, N, C) == ((16, 192) if shape == 'big' else (4, 32 if C == 1024 else 64)) and lx.ln_plan(B, N, C).passes == 1
     out = run_fwd(lib, c, shadow=C == 128)
     z64, _ = lx.make_z(c, rows)
     r = {}
@@ -447,7 +447,7 @@ def test_rounded_tier_forward_and_backward(lib, shape, kind):
 def test_forward_grid_stride_second_pass(lib, C, io16):
     B, N = lx.WRAP['B'], lx.WRAP['N']
     total = B * N
-    assert lx.fwd_rows_per_sweep(total, C) == 32768 < total and lx.fwd_passes(total, C) == 2      # row_grid's cap: a second pass
+    assert lx.ln_plan(B, N, C).sweep == 32768 < total and lx.ln_plan(B, N, C).passes == 2      # row_grid's cap: a second pass
     c = lx.rounded_case('randn', C=C, lens=lx.wrap_lens(), io16=io16, with_dy=False, **lx.WRAP)
     out = run_fwd(lib, c)
     rows = lx.wrap_rows()
@@ -514,7 +514,7 @@ def test_pair_forward_layernorm_epilogue(lib, ops, build, name, with_qkv):
     c = lx.rounded_case('randn', B, N, 128, lens, with_dy=False)
     c['p_post'] = 0.0
     c['ld_film'] = 260
-    assert lx.ff_tile(B, N) == (62 if name == 'ff_62' else 126)
+    assert lx.ff_pair_tok(B, N) == (62 if name == 'ff_62' else 126)
     g = torch.Generator().manual_seed(8)
     r_ = lambda *s: torch.randn(*s, generator=g)
     valid = valid_mask(c)

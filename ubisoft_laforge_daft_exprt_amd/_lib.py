@@ -112,6 +112,34 @@ def lib() -> _Lib:
     return _LIB
 
 
+# Launch plans: the record every ``dx_*_plan`` entry point fills, by the names the header gives its fields and kernel ids.
+_PLAN = None
+
+
+def _plan_layout():
+    """-> (the Plan namedtuple: DX_PLAN_* in record order, lower case; {DX_K_* value: its name, lower case})"""
+    global _PLAN
+    if _PLAN is None:
+        import collections
+        defs = {k: int(v) for k, v in re.findall(r'#define (DX_(?:PLAN|K)_\w+) (\d+)', open(HEADER).read())}
+        n = defs.pop('DX_PLAN_INTS')
+        fields = sorted((v, k[len('DX_PLAN_'):].lower()) for k, v in defs.items() if k.startswith('DX_PLAN_'))
+        assert [v for v, _ in fields] == list(range(n)), 'DX_PLAN_* must number the record 0 .. DX_PLAN_INTS - 1'
+        _PLAN = (collections.namedtuple('Plan', [f for _, f in fields]),
+                 {v: k[len('DX_K_'):].lower() for k, v in defs.items() if k.startswith('DX_K_')})
+    return _PLAN
+
+
+def plan(entry, *args):
+    """What the dispatcher behind ``entry`` ('dx_conv_gemm_plan', 'dx_ln_plan', ... or an ``_f16`` twin) would launch for these scalars:
+    Plan(kernel='conv_dk', tok=128, grid_x=..., ...).  Host code only: works without a GPU."""
+    Plan, kernels = _plan_layout()
+    buf = (ctypes.c_int * len(Plan._fields))()
+    getattr(lib(), entry)(*args, ctypes.addressof(buf))
+    p = Plan(*buf)
+    return p._replace(kernel=kernels[p.kernel])
+
+
 # What the audio modules (vocoder*.py, discriminators.py) share around a launch.
 def stream(device):
     """-> the handle of torch's current stream on ``device``: what every entry point takes as ``stream``."""

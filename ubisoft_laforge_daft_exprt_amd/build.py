@@ -9,6 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libdaft_exprt_hip.so')
+HEADER = os.path.join(os.path.dirname(PKG), 'include', 'daft_exprt_hip.h')
 SOURCES = ['dx_runtime.hip', 'dx_gemm.hip', 'dx_ffpair.hip', 'dx_attention.hip', 'dx_rows.hip', 'dx_upsample.hip', 'dx_loss.hip', 'dx_optim.hip', 'dx_pitch.hip', 'dx_vocoder.hip', 'dx_vocoder_bwd.hip', 'dx_mel.hip', 'dx_prosody.hip', 'dx_disc.hip', 'dx_disc_bwd.hip', 'dx_disc_wgrad.hip', 'dx_griffin_lim.hip', 'dx_vocoder_optim.hip', 'dx_finetune_data.hip']
 F16_SOURCES = ['dx_gemm.hip', 'dx_ffpair.hip', 'dx_attention.hip', 'dx_rows.hip', 'dx_pitch.hip']    # compiled a second time with -DDX_F16 (fp16 operand mode)
 FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wno-unused-value', '-Wno-unused-result'] + os.environ.get('DX_EXTRA_HIPCC_FLAGS', '').split()
@@ -22,8 +23,9 @@ def _stale(target, deps):
 
 
 def _deps(src):
-    """An object depends on its source and on every header in csrc/: listed, not kept by hand, so a new header cannot be forgotten."""
-    return [os.path.join(CSRC, src)] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h'))
+    """An object depends on its source, on every header in csrc/ (listed, not kept by hand, so a new header cannot be forgotten) and on
+    the public header, which dx_common.h includes."""
+    return [os.path.join(CSRC, src), HEADER] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h'))
 
 
 def _compile(job):

@@ -1393,7 +1393,6 @@ int dx_attention_fwd(const void* qkvv, int ld, const int* lens, void* ctxv, int 
   AttnArgs a{qkv, ld, lens, ctx, ldc, lse, B, N, H, D, seed, (uint32_t)lrintf(p_drop * 65536.f), 1.f / (1.f - p_drop), seed_offset, order, 0};
   a.xcd_map = (H * B) % 8 == 0;
   hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_ATTN_FWD, s);
   const dim3 grid(dx_cdiv(N, 64), H, B);
   if (bf16 && qkv_bf16 && ctx_bf16) hipLaunchKernelGGL((attn_fwd_bf16_kernel<dx_h16, dx_h16>), grid, dim3(256), 0, s, a);
   else if (bf16 && qkv_bf16) hipLaunchKernelGGL((attn_fwd_bf16_kernel<dx_h16, float>), grid, dim3(256), 0, s, a);
@@ -1401,7 +1400,6 @@ int dx_attention_fwd(const void* qkvv, int ld, const int* lens, void* ctxv, int 
   else if (bf16) hipLaunchKernelGGL((attn_fwd_bf16_kernel<float, float>), grid, dim3(256), 0, s, a);
   else if (split) { if constexpr (kSplitBuild) hipLaunchKernelGGL(attn_fwd_split_kernel, grid, dim3(256), 0, s, a); }
   else hipLaunchKernelGGL(attn_fwd_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), 0, s, a);
-  dx_prof_end(DX_PROF_ATTN_FWD, s);
   DX_LAUNCH_CHECK("dx_attention_fwd");
   return DX_OK;
 }
@@ -1428,9 +1426,7 @@ int dx_attention_proj_ln_fwd(const void* qkv, int ld, const int* lens, void* ctx
   k.y = y; k.y_h = (dx_h16*)y_bf16_copy; k.mean = mean; k.rstd = rstd;
   k.seed_pre = seed_pre; k.thresh_pre = (uint32_t)lrintf(p_pre * 65536.f); k.inv_keep_pre = 1.f / (1.f - p_pre);
   hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_ATTN_FWD, s);
   hipLaunchKernelGGL(attn_proj_ln_fwd_kernel, dim3(8 * dx_cdiv(N, 64) * dx_cdiv(B, 8)), dim3(512), 0, s, k);
-  dx_prof_end(DX_PROF_ATTN_FWD, s);
   DX_LAUNCH_CHECK("dx_attention_proj_ln_fwd");
   return DX_OK;
 }
@@ -1455,7 +1451,6 @@ int dx_attention_bwd(const void* qkvv, int ld, const void* ctxv, const void* dct
     hipLaunchKernelGGL(attn_delta_kernel, dim3((int)std::min<long>((items + 3) / 4, 8192)), dim3(256), 0, s, dctx, ctx, ldc, delta, B, N, H);
   AttnBwdArgs a{qkv, ld, dctx, ldc, lse, delta, lens, dqkv, ldg, B, N, H, D, seed, (uint32_t)lrintf(p_drop * 65536.f), 1.f / (1.f - p_drop), ctx, delta, seed_offset, order, 0};
   a.xcd_map = (H * B) % 8 == 0;
-  dx_prof_begin(DX_PROF_ATTN_BWD, s);
   if (bf16) {
     const dim3 grid(dx_cdiv(N, 64), H, B);
 #define DX_ATTN_BWD(QT_, OT_)                                                                          \
@@ -1485,7 +1480,6 @@ int dx_attention_bwd(const void* qkvv, int ld, const void* ctxv, const void* dct
     hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), 0, s, a);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(dx_cdiv(N, 64), H, B), dim3(256), 0, s, a);
   }
-  dx_prof_end(DX_PROF_ATTN_BWD, s);
   DX_LAUNCH_CHECK("dx_attention_bwd");
   return DX_OK;
 }

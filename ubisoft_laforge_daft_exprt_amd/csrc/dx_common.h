@@ -12,8 +12,6 @@
 extern "C" {
 #endif
 void dx_set_error(const char* fmt, ...);
-void dx_prof_begin(int kernel_id, hipStream_t s);
-void dx_prof_end(int kernel_id, hipStream_t s);
 #ifdef __cplusplus
 }
 #endif
@@ -35,10 +33,6 @@ void dx_prof_end(int kernel_id, hipStream_t s);
     }                                                                 \
   } while (0)
 
-// kernel families that can be bracketed by HIP events (bench.py roofline leg)
-enum { DX_PROF_CONV_GEMM = 0, DX_PROF_WGRAD_GEMM = 1, DX_PROF_ATTN_FWD = 2, DX_PROF_ATTN_BWD = 3,
-       DX_PROF_UPSAMPLE = 4, DX_PROF_ROWS = 5, DX_PROF_NKINDS = 6 };
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // The 16-bit operand / storage type of the reduced-precision paths.  dx_gemm.hip, dx_ffpair.hip, dx_attention.hip and dx_rows.hip are
 // compiled TWICE: as they stand (bf16: BASELINE.json config 2) and with -DDX_F16 (IEEE fp16: config 5), where every exported name
@@ -52,12 +46,18 @@ typedef _Float16 dx_h16;
 typedef __bf16 dx_h16;
 #define DX_MFMA_H16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16((A), (B), (C), 0, 0, 0)
 #endif
+#include "../../include/daft_exprt_hip.h"   // after the renames: the prototypes, DxWgradJob, the launch-plan record (DX_PLAN_*, DX_K_*)
 typedef dx_h16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef dx_h16 bf16x4 __attribute__((ext_vector_type(4)));
 
 static inline int dx_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int dx_roundup(int a, int b) { return dx_cdiv(a, b) * b; }
 static inline bool dx_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the six fields every launch plan has (include/daft_exprt_hip.h); the family's own fields start at zero
+static inline void dx_plan_set(int* p, int kernel, int tok, int gx, int gy, int gz, int threads) {
+  for (int i = 0; i < DX_PLAN_INTS; ++i) p[i] = 0;
+  p[DX_PLAN_KERNEL] = kernel; p[DX_PLAN_TOK] = tok; p[DX_PLAN_GRID_X] = gx; p[DX_PLAN_GRID_Y] = gy; p[DX_PLAN_GRID_Z] = gz; p[DX_PLAN_THREADS] = threads;
+}
 
 #ifdef __HIPCC__
 // ---- split-bf16 operands (C ABI operand mode 2, bf16 build) ---------------------------------------------------------------------

@@ -866,6 +866,18 @@ extern "C" void dx_ff_pair_set_stamps(unsigned long long* p) { g_ffpair_stamps =
 
 extern "C" {
 
+// The launch plan of every entry point of the pair (record: include/daft_exprt_hip.h).
+// Tile width by shape: 126-token tiles with one workgroup per CU (NJ = 8) where they fill the chip (frame axis: ~250 live tiles at C2);
+// 62-token tiles with two per CU (NJ = 4) for short batches (symbol axis: 48 utterances of <= 120 symbols are 48 tiles of 126 but 96 of
+// 62: twice the CUs, half the serial slice loop per workgroup).  Forward and backward see the same (B, N) and therefore make the same
+// choice (the sign words are laid out per tile).
+int dx_ff_pair_plan(int B, int N, int* plan) {
+  DX_REQUIRE(plan && B > 0 && N > 0, "dx_ff_pair_plan: bad arguments");
+  const int tok = B * dx_cdiv(N, FP<8>::TOK) >= 96 ? FP<8>::TOK : FP<4>::TOK;
+  dx_plan_set(plan, DX_K_FF_PAIR, tok, B * dx_cdiv(N, tok), 1, 1, 512);
+  return DX_OK;
+}
+
 // One launch for conv(k=3, 128 -> F) -> mid -> conv(k=3, F -> 128) on channels-last bf16 activations (see the header of this file).
 // Wa / Wb: fragment-major bf16 packs written by dx_pack_weights (forward pair: conv1.fwd / conv2.fwd; input-gradient pair:
 // conv2.bwd / conv1.bwd).  H [B][N][F] bf16 receives the mid activation; Y [B][N][128] fp32 the result (+= if accumulate).
@@ -937,24 +949,20 @@ static int ff_pair_launch(const void* X, int ldx, const void* Wa, const void* Wb
     hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_pair_kernel<false, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * FP<4>::IMG);
     configured = true;
   }
-  // tile width: 62-token tiles with two workgroups per CU (NJ = 4) or 126-token tiles with one (NJ = 8)
   a.hmask = hmask;
-  // Tile width by shape: 126-token tiles where they fill the chip (frame axis: ~250 live tiles at C2); 62-token tiles for short batches
-  // (symbol axis: 48 utterances of <= 120 symbols are 48 tiles of 126 but 96 of 62: twice the CUs, half the serial slice loop per workgroup).
-  // Forward and backward see the same (B, N) and therefore make the same choice (the sign words are laid out per tile).
-  const int nj = B * dx_cdiv(N, FP<8>::TOK) >= 96 ? 8 : 4;
+  int plan[DX_PLAN_INTS];
+  if (int rc = dx_ff_pair_plan(B, N, plan)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_CONV_GEMM, s);
-  if (nj == 8) {
-    if (aux && hmask) hipLaunchKernelGGL((ff_pair_kernel<true, false, 8, true>), dim3(B * dx_cdiv(N, FP<8>::TOK)), dim3(512), lds8, s, a);
-    else if (aux) hipLaunchKernelGGL((ff_pair_kernel<true, false, 8>), dim3(B * dx_cdiv(N, FP<8>::TOK)), dim3(512), lds8, s, a);
-    else hipLaunchKernelGGL((ff_pair_kernel<false, true, 8>), dim3(B * dx_cdiv(N, FP<8>::TOK)), dim3(512), 3 * FP<8>::IMG, s, a);
+  const dim3 grid(plan[DX_PLAN_GRID_X]), block(plan[DX_PLAN_THREADS]);
+  if (plan[DX_PLAN_TOK] == FP<8>::TOK) {
+    if (aux && hmask) hipLaunchKernelGGL((ff_pair_kernel<true, false, 8, true>), grid, block, lds8, s, a);
+    else if (aux) hipLaunchKernelGGL((ff_pair_kernel<true, false, 8>), grid, block, lds8, s, a);
+    else hipLaunchKernelGGL((ff_pair_kernel<false, true, 8>), grid, block, 3 * FP<8>::IMG, s, a);
   } else {
-    if (aux && hmask) hipLaunchKernelGGL((ff_pair_kernel<true, false, 4, true>), dim3(B * dx_cdiv(N, FP<4>::TOK)), dim3(512), lds4, s, a);
-    else if (aux) hipLaunchKernelGGL((ff_pair_kernel<true, false, 4>), dim3(B * dx_cdiv(N, FP<4>::TOK)), dim3(512), lds4, s, a);
-    else hipLaunchKernelGGL((ff_pair_kernel<false, true, 4>), dim3(B * dx_cdiv(N, FP<4>::TOK)), dim3(512), 3 * FP<4>::IMG, s, a);
+    if (aux && hmask) hipLaunchKernelGGL((ff_pair_kernel<true, false, 4, true>), grid, block, lds4, s, a);
+    else if (aux) hipLaunchKernelGGL((ff_pair_kernel<true, false, 4>), grid, block, lds4, s, a);
+    else hipLaunchKernelGGL((ff_pair_kernel<false, true, 4>), grid, block, 3 * FP<4>::IMG, s, a);
   }
-  dx_prof_end(DX_PROF_CONV_GEMM, s);
   DX_LAUNCH_CHECK("dx_ff_pair");
   return DX_OK;
 }

@@ -675,19 +675,21 @@ __global__ __launch_bounds__(512, 2) void conv_ws_kernel(const ConvGemmArgs a, i
 #undef DX_WS_LOAD
 }
 
+constexpr size_t conv_ws_smem(int taps) {
+  return (size_t)(2 * taps * TILE) * 128 + std::max<size_t>((size_t)2 * (128 + taps - 1) * 128, (size_t)128 * 288);
+}
+
+// plan: the record of dx_conv_gemm_plan (grid x = the persistent workgroups per channel tile)
 template <int TAPS, bool XH>
-void launch_conv_ws(const ConvGemmArgs& a, hipStream_t s) {
-  const size_t smem = (size_t)(2 * TAPS * TILE) * 128 + std::max<size_t>((size_t)2 * (128 + TAPS - 1) * 128, (size_t)128 * 288);
+void launch_conv_ws(const ConvGemmArgs& a, hipStream_t s, const int* plan) {
+  const size_t smem = conv_ws_smem(TAPS);
   static bool configured = false;
   if (!configured) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_ws_kernel<TAPS, XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     configured = true;
   }
-  const int co_tiles = a.CoutP / TILE;
-  const int total = a.B * dx_cdiv(a.N, 128);
-  const int per_cu = smem * 2 <= 160 * 1024 ? 2 : 1;       // TAPS=1 fits twice per CU
-  const int wgs = std::max(1, std::min(total, (256 * per_cu) / co_tiles));
-  hipLaunchKernelGGL((conv_ws_kernel<TAPS, XH>), dim3(wgs, co_tiles), dim3(512), smem, s, a, wgs);
+  hipLaunchKernelGGL((conv_ws_kernel<TAPS, XH>), dim3(plan[DX_PLAN_GRID_X], plan[DX_PLAN_GRID_Y]), dim3(plan[DX_PLAN_THREADS]), smem, s, a,
+                     plan[DX_PLAN_GRID_X]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1051,18 +1053,16 @@ __global__ __launch_bounds__(512) void conv_dk_kernel(const ConvGemmArgs a) {
 }
 
 template <int TAPS, bool XH>
-void launch_conv_dk(const ConvGemmArgs& a, hipStream_t s) {
+void launch_conv_dk(const ConvGemmArgs& a, hipStream_t s, const int* plan) {
   const size_t smem = std::max<size_t>((size_t)2 * (128 + TAPS - 1) * 128, (size_t)128 * 528);
   static bool configured = false;
   if (!configured) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dk_kernel<TAPS, XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     configured = true;
   }
-  dim3 grid(a.B * dx_cdiv(a.N, 128), a.CoutP / TILE);
   ConvGemmArgs b = a;
-  b.xcd_swizzle = (grid.y > 1 && (grid.y <= 4 || grid.y % 4 == 0)) ? 4 : 0;
-  if (b.xcd_swizzle) grid.x = dx_roundup(grid.x, 8);
-  hipLaunchKernelGGL((conv_dk_kernel<TAPS, XH>), grid, dim3(512), smem, s, b);
+  b.xcd_swizzle = plan[DX_PLAN_SWIZZLE];
+  hipLaunchKernelGGL((conv_dk_kernel<TAPS, XH>), dim3(plan[DX_PLAN_GRID_X], plan[DX_PLAN_GRID_Y]), dim3(plan[DX_PLAN_THREADS]), smem, s, b);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2101,17 +2101,6 @@ __global__ __launch_bounds__(256) void pack_weights_flat_bf16_kernel(const PackB
   pack_block_bf16(a.d[lo], wb - a.prefix[lo], threadIdx.x & 63);
 }
 
-// grad[co][ci][tap] (+)= G[tap][co][ci]
-__global__ void unpack_wgrad_kernel(const float* __restrict__ G, float* __restrict__ grad, int Cout, int Cin, int taps, int accumulate) {
-  const size_t n = (size_t)Cout * Cin * taps;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int tap = (int)(i % taps);
-    const size_t cc = i / taps;
-    const float v = G[(size_t)tap * Cout * Cin + cc];
-    grad[i] = accumulate ? grad[i] + v : v;
-  }
-}
-
 // column sums: out[c] += sum_rows X[row][c]   (bias gradients); X fp32 or bf16
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, int ldx, float* __restrict__ out,
@@ -2134,29 +2123,23 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, in
 }
 
 template <typename T, int TAPS, int TOK, bool XH>
-void launch_conv_inst(const ConvGemmArgs& a, hipStream_t s) {
+void launch_conv_inst(const ConvGemmArgs& a, hipStream_t s, const int* plan) {
   const size_t smem = (size_t)(TAPS * TILE + TOK + TAPS - 1) * 128;
   static bool configured = false;
   if (!configured) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, TAPS, TOK, XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     configured = true;
   }
-  dim3 grid(a.B * dx_cdiv(a.N, TOK), a.CoutP / TILE);
-  hipLaunchKernelGGL((conv_gemm_kernel<T, TAPS, TOK, XH>), grid, dim3(256), smem, s, a);
+  hipLaunchKernelGGL((conv_gemm_kernel<T, TAPS, TOK, XH>), dim3(plan[DX_PLAN_GRID_X], plan[DX_PLAN_GRID_Y]), dim3(plan[DX_PLAN_THREADS]), smem, s, a);
 }
 
 template <typename T, int TAPS>
-int launch_conv(const ConvGemmArgs& a, hipStream_t s) {
-  // narrow outputs (Cout <= 128: conv2, out-proj, mel projection ...) launch few workgroups: in exact-f32 mode (MFMA-paced)
-  // 64-token tiles fill the chip better (measured 405 -> 354 us on the FF conv2); in bf16 mode the 128-token tile stays ahead
-  // (62 vs 79 us) because the weight tile is re-staged half as often.
-  // (bf16, k = 1, few workgroups - the phoneme-level Linear layers: 64-token tiles measured 9.6 -> 7.7 us; bf16 k = 3 stays at 128)
-  constexpr long small_below = (sizeof(T) == 4 || TAPS == 1) ? 1024 : 0;
-  const bool small = (long)a.B * dx_cdiv(a.N, TILE) * (a.CoutP / TILE) < small_below;
+int launch_conv(const ConvGemmArgs& a, hipStream_t s, const int* plan) {
+  const bool small = plan[DX_PLAN_TOK] == 64;
   if constexpr (sizeof(T) == 2) {
-    if (a.x_bf16) { if (small) launch_conv_inst<T, TAPS, 64, true>(a, s); else launch_conv_inst<T, TAPS, 128, true>(a, s); return DX_OK; }
+    if (a.x_bf16) { if (small) launch_conv_inst<T, TAPS, 64, true>(a, s, plan); else launch_conv_inst<T, TAPS, 128, true>(a, s, plan); return DX_OK; }
   }
-  if (small) launch_conv_inst<T, TAPS, 64, false>(a, s); else launch_conv_inst<T, TAPS, 128, false>(a, s);
+  if (small) launch_conv_inst<T, TAPS, 64, false>(a, s, plan); else launch_conv_inst<T, TAPS, 128, false>(a, s, plan);
   return DX_OK;
 }
 
@@ -2231,6 +2214,38 @@ int dx_pack_weights_host(const void* descs, int n, int bf16, void* stream) {
   return DX_OK;
 }
 
+// The launch plan of dx_conv_gemm (record: include/daft_exprt_hip.h).  Every rule of the dispatch is written here and nowhere else.
+int dx_conv_gemm_plan(int B, int N, int Cin, int Cout, int taps, int bf16, int ldx, int* plan) {
+  DX_REQUIRE(plan, "dx_conv_gemm_plan: null pointer");
+  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_conv_gemm: bad operand mode %d", bf16);
+  DX_REQUIRE(B > 0 && N > 0 && Cin > 0 && Cout > 0 && taps > 0, "dx_conv_gemm: bad dims B=%d N=%d Cin=%d Cout=%d", B, N, Cin, Cout);
+  int d[4];
+  dx_pack_dims(Cout, Cin, bf16 == 1, d);     // the split mode reads the f32 pack
+  const int co_tiles = d[0] / TILE, tiles128 = B * dx_cdiv(N, 128);
+  constexpr int ws_min_tiles = 64;
+  constexpr int dk_min_cin = 256;
+  if (bf16 == 1 && d[1] >= dk_min_cin && (Cin % 64) == 0 && (long)B * N * ldx < (1L << 31)) {
+    // deep-K layers: weights straight from the fragment-major pack into registers, live tiles numbered first
+    const int swizzle = (co_tiles > 1 && (co_tiles <= 4 || co_tiles % 4 == 0)) ? 4 : 0;
+    dx_plan_set(plan, DX_K_CONV_DK, 128, swizzle ? dx_roundup(tiles128, 8) : tiles128, co_tiles, 1, 512);
+    plan[DX_PLAN_SWIZZLE] = swizzle;
+  } else if (bf16 == 1 && d[1] == 128 && tiles128 >= ws_min_tiles) {      // short-K layers: weight-stationary persistent kernel
+    const int per_cu = conv_ws_smem(taps) * 2 <= 160 * 1024 ? 2 : 1;       // taps = 1 fits twice per CU
+    dx_plan_set(plan, DX_K_CONV_WS, 128, std::max(1, std::min(tiles128, (256 * per_cu) / co_tiles)), co_tiles, 1, 512);
+  } else {
+    // narrow outputs (Cout <= 128: conv2, out-proj, mel projection ...) launch few workgroups: in exact-f32 mode (MFMA-paced)
+    // 64-token tiles fill the chip better (measured 405 -> 354 us on the FF conv2); in bf16 mode the 128-token tile stays ahead
+    // (62 vs 79 us) because the weight tile is re-staged half as often.
+    // (bf16, k = 1, few workgroups - the phoneme-level Linear layers: 64-token tiles measured 9.6 -> 7.7 us; bf16 k = 3 stays at 128)
+    const long small_below = (bf16 != 1 || taps == 1) ? 1024 : 0;
+    const int tok = (long)tiles128 * co_tiles < small_below ? 64 : 128;
+    dx_plan_set(plan, bf16 == 2 ? DX_K_CONV_GEMM_SPLIT : bf16 ? DX_K_CONV_GEMM_H16 : DX_K_CONV_GEMM_F32, tok, B * dx_cdiv(N, tok), co_tiles, 1, 256);
+  }
+  plan[DX_PLAN_COUTP] = d[0];
+  plan[DX_PLAN_CINP] = d[1];
+  return DX_OK;
+}
+
 // Y = epilogue(conv(X, Wp) + bias).  See ConvGemmArgs for the epilogue switches.
 int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, void* Yv, int ldy,
                  int B, int N, int Cin, int Cout, int taps, int bf16,
@@ -2240,13 +2255,13 @@ int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, voi
                  int x_bf16, int y_bf16, int aux_bf16, const int* rows_exist, void* stream) {
   const float* X = (const float*)Xv; float* Y = (float*)Yv; const float* relu_aux = (const float*)relu_auxv;
   DX_REQUIRE(X && Wp && Y, "dx_conv_gemm: null pointer");
-  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_conv_gemm: bad operand mode %d", bf16);
+  int plan[DX_PLAN_INTS];
+  if (int rc = dx_conv_gemm_plan(B, N, Cin, Cout, taps, bf16, ldx, plan)) return rc;     // also: operand mode and dimensions are valid
   DX_REQUIRE(bf16 == 1 || !(x_bf16 || y_bf16 || aux_bf16), "dx_conv_gemm: bf16 storage needs bf16 operand mode");
   DX_REQUIRE(!x_bf16 || ((Cin % 8) == 0 && (ldx % 8) == 0), "dx_conv_gemm: bf16 input needs Cin, ldx multiples of 8");
   DX_REQUIRE(!y_bf16 || ((Cout % 4) == 0 && (ldy % 4) == 0 && !accumulate), "dx_conv_gemm: bf16 output needs Cout, ldy multiples of 4 and no accumulate");
   DX_REQUIRE(!aux_bf16 || ((Cout % 4) == 0 && (ld_aux % 4) == 0), "dx_conv_gemm: bf16 relu_aux needs Cout, ld_aux multiples of 4");
   DX_REQUIRE(skip_halo < 0 || lens, "dx_conv_gemm: skip_halo needs lens");
-  DX_REQUIRE(B > 0 && N > 0 && Cin > 0 && Cout > 0, "dx_conv_gemm: bad dims B=%d N=%d Cin=%d Cout=%d", B, N, Cin, Cout);
   DX_REQUIRE(taps == 1 || taps == 3, "dx_conv_gemm: taps must be 1 or 3 (got %d)", taps);
   DX_REQUIRE((Cin % 4) == 0 && (ldx % 4) == 0 && ldx >= Cin, "dx_conv_gemm: Cin (%d) and ldx (%d) must be multiples of 4, ldx >= Cin", Cin, ldx);
   DX_REQUIRE(ldy >= Cout && ((Cout % 4) != 0 || (ldy % 4) == 0), "dx_conv_gemm: bad ldy %d for Cout %d", ldy, Cout);
@@ -2254,27 +2269,64 @@ int dx_conv_gemm(const void* Xv, int ldx, const void* Wp, const float* bias, voi
   DX_REQUIRE(!relu_aux || ld_aux >= Cout, "dx_conv_gemm: bad ld_aux");
   DX_REQUIRE((post_scale == nullptr) == (post_shift == nullptr), "dx_conv_gemm: post_scale/post_shift must come together");
   DX_REQUIRE(!mask_rows || lens, "dx_conv_gemm: mask_rows needs lens");
-  int d[4];
-  dx_pack_dims(Cout, Cin, bf16 == 1, d);     // the split mode reads the f32 pack
-  ConvGemmArgs a{X, ldx, Wp, bias, Y, ldy, B, N, Cin, Cout, d[1], d[0], relu, post_scale, post_shift,
+  ConvGemmArgs a{X, ldx, Wp, bias, Y, ldy, B, N, Cin, Cout, plan[DX_PLAN_CINP], plan[DX_PLAN_COUTP], relu, post_scale, post_shift,
                  relu_aux, ld_aux, accumulate, lens, mask_rows, out_scale, skip_halo, x_bf16, y_bf16, aux_bf16, rows_exist};
   hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_CONV_GEMM, s);
-  constexpr int ws_min_tiles = 64;
-  // deep-K layers: weights straight from the fragment-major pack into registers, live tiles numbered first
-  constexpr int dk_min_cin = 256;
-  if (bf16 == 2) {
-    if constexpr (kSplitBuild) { if (taps == 3) launch_conv<dx_split3, 3>(a, s); else launch_conv<dx_split3, 1>(a, s); }
-  } else if (bf16 && d[1] >= dk_min_cin && (Cin % 64) == 0 && (long)B * N * ldx < (1L << 31)) {
-    if (x_bf16) { if (taps == 3) launch_conv_dk<3, true>(a, s); else launch_conv_dk<1, true>(a, s); }
-    else { if (taps == 3) launch_conv_dk<3, false>(a, s); else launch_conv_dk<1, false>(a, s); }
-  } else if (bf16 && d[1] == 128 && (long)B * dx_cdiv(N, 128) >= ws_min_tiles) {      // short-K layers: weight-stationary persistent kernel
-    if (x_bf16) { if (taps == 3) launch_conv_ws<3, true>(a, s); else launch_conv_ws<1, true>(a, s); }
-    else { if (taps == 3) launch_conv_ws<3, false>(a, s); else launch_conv_ws<1, false>(a, s); }
-  } else if (bf16) { if (taps == 3) launch_conv<dx_h16, 3>(a, s); else launch_conv<dx_h16, 1>(a, s); }
-  else      { if (taps == 3) launch_conv<float, 3>(a, s);  else launch_conv<float, 1>(a, s); }
-  dx_prof_end(DX_PROF_CONV_GEMM, s);
+  switch (plan[DX_PLAN_KERNEL]) {
+    case DX_K_CONV_GEMM_SPLIT:
+      if constexpr (kSplitBuild) { if (taps == 3) launch_conv<dx_split3, 3>(a, s, plan); else launch_conv<dx_split3, 1>(a, s, plan); }
+      break;
+    case DX_K_CONV_DK:
+      if (x_bf16) { if (taps == 3) launch_conv_dk<3, true>(a, s, plan); else launch_conv_dk<1, true>(a, s, plan); }
+      else { if (taps == 3) launch_conv_dk<3, false>(a, s, plan); else launch_conv_dk<1, false>(a, s, plan); }
+      break;
+    case DX_K_CONV_WS:
+      if (x_bf16) { if (taps == 3) launch_conv_ws<3, true>(a, s, plan); else launch_conv_ws<1, true>(a, s, plan); }
+      else { if (taps == 3) launch_conv_ws<3, false>(a, s, plan); else launch_conv_ws<1, false>(a, s, plan); }
+      break;
+    case DX_K_CONV_GEMM_H16: if (taps == 3) launch_conv<dx_h16, 3>(a, s, plan); else launch_conv<dx_h16, 1>(a, s, plan); break;
+    default: if (taps == 3) launch_conv<float, 3>(a, s, plan); else launch_conv<float, 1>(a, s, plan);
+  }
   DX_LAUNCH_CHECK("dx_conv_gemm");
+  return DX_OK;
+}
+
+// one launch of the 16-bit weight-gradient kernel at the operands' storage (dx_conv_wgrad and its batched form)
+#define DX_WG_LAUNCH(TAPS_, CIW_)                                                                                 \
+  if (dy_bf16 && x_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, true, true, CIW_>), grid, block, 0, s, a);   \
+  else if (dy_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, true, false, CIW_>), grid, block, 0, s, a);       \
+  else if (x_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, false, true, CIW_>), grid, block, 0, s, a);        \
+  else hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, false, false, CIW_>), grid, block, 0, s, a);
+
+// The launch plan of dx_conv_wgrad (record: include/daft_exprt_hip.h).
+int dx_conv_wgrad_plan(int B, int N, int Cin, int Cout, int taps, int bf16, int ldx, int ldy, int dy_bf16, int x_bf16, int* plan) {
+  DX_REQUIRE(plan, "dx_conv_wgrad_plan: null pointer");
+  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_conv_wgrad: bad operand mode %d", bf16);
+  DX_REQUIRE(B > 0 && N > 0 && Cin > 0 && Cout > 0 && taps > 0, "dx_conv_wgrad: bad dims");
+  const bool h16_ok = (Cin % 8) == 0 && (ldx % 8) == 0 && (Cout % 8) == 0 && (ldy % 8) == 0;
+  if (bf16 == 1 && h16_ok) {   // odd tiny shapes (speaker logits) take the exact f32 kernel below
+    // 512-thread workgroups with 128 input channels each: measured better only where the output is large enough that few token
+    // slices are needed anyway (prenet 1024 x 1024: 308 -> 239 us); the 128-wide layers stay on the narrow form (59 vs 67 us)
+    const bool wide = (Cin % 128) == 0 && dx_cdiv(Cout, TILE) * dx_cdiv(Cin, 64) >= 64;
+    const int tiles = dx_cdiv(Cout, TILE) * dx_cdiv(Cin, wide ? 128 : 64);
+    const int chunk = wb_bk(taps, dy_bf16 != 0, x_bf16 != 0);
+    const int total_chunks = B * dx_cdiv(N, chunk);
+    // split-K partials are fp32 atomics (~1.3 TB/s chip-wide), so the split is sized by atomic traffic, not by "as many as fit";
+    // per-kernel rocprof sweeps (r01-g build): k = 3 layers 192 / 256 / 320 / 384 blocks -> 50.0 / 47.6 / 48.8 / 50.2 us,
+    // k = 1 layers 96 / 128 / 160 / 192 / 256 / 384 -> 24.9 / 20.9 / 19.5 / 18.8 / 19.5 / 22.1 us
+    constexpr int target_blocks = 256;
+    constexpr int target_wide = 256;   // one per CU
+    constexpr int target_k1 = 192;
+    const int ksplit = std::max(1, std::min(total_chunks, dx_cdiv(wide ? target_wide : (taps == 1 ? target_k1 : target_blocks), tiles)));
+    dx_plan_set(plan, wide ? DX_K_WGRAD_H16_WIDE : DX_K_WGRAD_H16, 0, tiles, 1, ksplit, (wide ? 4 : 2) * 128);
+    plan[DX_PLAN_CHUNK] = chunk;
+  } else {
+    const int tiles = dx_cdiv(Cout, TILE) * dx_cdiv(Cin, TILE);
+    const int total_chunks = B * dx_cdiv(N, WG_BK);
+    dx_plan_set(plan, bf16 == 2 ? DX_K_WGRAD_SPLIT : DX_K_WGRAD_F32, 0, tiles, taps, std::max(1, std::min(total_chunks, dx_cdiv(1024, tiles * taps))), 256);
+    plan[DX_PLAN_CHUNK] = WG_BK;
+  }
+  plan[DX_PLAN_SPLIT] = plan[DX_PLAN_GRID_Z];
   return DX_OK;
 }
 
@@ -2284,123 +2336,92 @@ int dx_conv_wgrad(const void* dY, int ldy, const void* X, int ldx, float* G,
                   int B, int N, int Cin, int Cout, int taps, const int* lens, int skip_halo,
                   int bf16, int dy_bf16, int x_bf16, float* dbias, const int* rows_exist, void* stream) {
   DX_REQUIRE(dY && X && G, "dx_conv_wgrad: null pointer");
-  DX_REQUIRE(bf16 == 0 || bf16 == 1 || (bf16 == 2 && kSplitBuild), "dx_conv_wgrad: bad operand mode %d", bf16);
+  int plan[DX_PLAN_INTS];
+  if (int rc = dx_conv_wgrad_plan(B, N, Cin, Cout, taps, bf16, ldx, ldy, dy_bf16, x_bf16, plan)) return rc;     // also: operand mode and dimensions are valid
+  const int kernel = plan[DX_PLAN_KERNEL];
+  const bool h16 = kernel == DX_K_WGRAD_H16 || kernel == DX_K_WGRAD_H16_WIDE;
   DX_REQUIRE(bf16 == 1 || !(dy_bf16 || x_bf16), "dx_conv_wgrad: bf16 storage needs bf16 operand mode");
-  const bool bf16_ok = (Cin % 8) == 0 && (ldx % 8) == 0 && (Cout % 8) == 0 && (ldy % 8) == 0;
-  DX_REQUIRE(bf16_ok || !(dy_bf16 || x_bf16), "dx_conv_wgrad: bf16-stored operands need Cin/Cout/ld multiples of 8 (Cin=%d Cout=%d)", Cin, Cout);
-  if (bf16 == 1 && bf16_ok) {   // odd tiny shapes (speaker logits) take the exact f32 kernel below
-    DX_REQUIRE(B > 0 && N > 0 && Cin > 0 && Cout > 0 && (taps == 1 || taps == 3), "dx_conv_wgrad: bad dims");
-    DX_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0, "dx_conv_wgrad: pointers must be 16-byte aligned");
-    DX_REQUIRE(skip_halo < 0 || lens, "dx_conv_wgrad: skip_halo needs lens");
-    // 512-thread workgroups with 128 input channels each: measured better only where the output is large enough that few token
-    // slices are needed anyway (prenet 1024 x 1024: 308 -> 239 us); the 128-wide layers stay on the narrow form (59 vs 67 us)
-    const bool wide = (Cin % 128) == 0 && dx_cdiv(Cout, TILE) * dx_cdiv(Cin, 64) >= 64;
-    const int tiles = dx_cdiv(Cout, TILE) * dx_cdiv(Cin, wide ? 128 : 64);
-    const int total_chunks = B * dx_cdiv(N, wb_bk(taps, dy_bf16 != 0, x_bf16 != 0));
-    // split-K partials are fp32 atomics (~1.3 TB/s chip-wide), so the split is sized by atomic traffic, not by "as many as fit";
-    // per-kernel rocprof sweeps (r01-g build): k = 3 layers 192 / 256 / 320 / 384 blocks -> 50.0 / 47.6 / 48.8 / 50.2 us,
-    // k = 1 layers 96 / 128 / 160 / 192 / 256 / 384 -> 24.9 / 20.9 / 19.5 / 18.8 / 19.5 / 22.1 us
-    constexpr int target_blocks = 256;
-    constexpr int target_wide = 256;   // one per CU
-    constexpr int target_k1 = 192;
-    const int ksplit = std::max(1, std::min(total_chunks, dx_cdiv(wide ? target_wide : (taps == 1 ? target_k1 : target_blocks), tiles)));
+  DX_REQUIRE(h16 || !(dy_bf16 || x_bf16), "dx_conv_wgrad: bf16-stored operands need Cin/Cout/ld multiples of 8 (Cin=%d Cout=%d)", Cin, Cout);
+  DX_REQUIRE(taps == 1 || taps == 3, "dx_conv_wgrad: bad dims");
+  DX_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0, "dx_conv_wgrad: pointers must be 16-byte aligned");
+  DX_REQUIRE(skip_halo < 0 || lens, "dx_conv_wgrad: skip_halo needs lens");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(plan[DX_PLAN_GRID_X], plan[DX_PLAN_GRID_Y], plan[DX_PLAN_GRID_Z]), block(plan[DX_PLAN_THREADS]);
+  if (h16) {
     WgradBatchArgs a{};
     a.job[0] = WgradJobDev{dY, X, G, dbias, lens, ldy, ldx, B, N, Cin, Cout, skip_halo, 0, rows_exist};
-    a.ksplit = ksplit;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(tiles, 1, ksplit);
-    dx_prof_begin(DX_PROF_WGRAD_GEMM, s);
-#define DX_WG_LAUNCH(TAPS_, CIW_)                                                                                        \
-    if (dy_bf16 && x_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, true, true, CIW_>), grid, dim3(CIW_ * 128), 0, s, a);   \
-    else if (dy_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, true, false, CIW_>), grid, dim3(CIW_ * 128), 0, s, a);       \
-    else if (x_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, false, true, CIW_>), grid, dim3(CIW_ * 128), 0, s, a);        \
-    else hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, false, false, CIW_>), grid, dim3(CIW_ * 128), 0, s, a);
-    if (wide) { if (taps == 3) { DX_WG_LAUNCH(3, 4) } else { DX_WG_LAUNCH(1, 4) } }
+    a.ksplit = plan[DX_PLAN_SPLIT];
+    if (kernel == DX_K_WGRAD_H16_WIDE) { if (taps == 3) { DX_WG_LAUNCH(3, 4) } else { DX_WG_LAUNCH(1, 4) } }
     else { if (taps == 3) { DX_WG_LAUNCH(3, 2) } else { DX_WG_LAUNCH(1, 2) } }
-#undef DX_WG_LAUNCH
-    dx_prof_end(DX_PROF_WGRAD_GEMM, s);
     DX_LAUNCH_CHECK("dx_conv_wgrad(bf16)");
     return DX_OK;
   }
-  DX_REQUIRE(skip_halo < 0 || lens, "dx_conv_wgrad: skip_halo needs lens");
-  DX_REQUIRE(B > 0 && N > 0 && Cin > 0 && Cout > 0 && (taps == 1 || taps == 3), "dx_conv_wgrad: bad dims");
   DX_REQUIRE((Cin % 4) == 0 && (ldx % 4) == 0 && (Cout % 4) == 0 && (ldy % 4) == 0, "dx_conv_wgrad: Cin/Cout/ld must be multiples of 4 (Cin=%d Cout=%d)", Cin, Cout);
-  DX_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0, "dx_conv_wgrad: pointers must be 16-byte aligned");
-  const int tiles = dx_cdiv(Cout, TILE) * dx_cdiv(Cin, TILE);
-  const int total_chunks = B * dx_cdiv(N, WG_BK);
-  int ksplit = std::max(1, std::min(total_chunks, dx_cdiv(1024, tiles * taps)));
-  WgradArgs a{(const float*)dY, ldy, (const float*)X, ldx, G, B, N, Cin, Cout, ksplit, lens, skip_halo, dbias, rows_exist};
-  hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_WGRAD_GEMM, s);
-  if (bf16 == 2) {
+  WgradArgs a{(const float*)dY, ldy, (const float*)X, ldx, G, B, N, Cin, Cout, plan[DX_PLAN_SPLIT], lens, skip_halo, dbias, rows_exist};
+  if (kernel == DX_K_WGRAD_SPLIT) {
     if constexpr (kSplitBuild) {
-      if (taps == 3) hipLaunchKernelGGL(wgrad_split_kernel<3>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
-      else           hipLaunchKernelGGL(wgrad_split_kernel<1>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
+      if (taps == 3) hipLaunchKernelGGL(wgrad_split_kernel<3>, grid, block, 0, s, a);
+      else           hipLaunchKernelGGL(wgrad_split_kernel<1>, grid, block, 0, s, a);
     }
-  } else if (taps == 3) hipLaunchKernelGGL(wgrad_kernel<3>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
-  else           hipLaunchKernelGGL(wgrad_kernel<1>, dim3(tiles, taps, ksplit), dim3(256), 0, s, a);
-  dx_prof_end(DX_PROF_WGRAD_GEMM, s);
+  } else if (taps == 3) hipLaunchKernelGGL(wgrad_kernel<3>, grid, block, 0, s, a);
+  else           hipLaunchKernelGGL(wgrad_kernel<1>, grid, block, 0, s, a);
   DX_LAUNCH_CHECK("dx_conv_wgrad");
   return DX_OK;
 }
 
-// Several weight gradients of one kind in ONE launch (see WgradBatchArgs): bf16 operand mode, every job with Cin % 128 == 0 (the wide
-// tile), same taps and the same operand storage; B, N, lens, channels, leading dimensions and the halo rule are per job.
-struct DxWgradJob {       // mirrors include/daft_exprt_hip.h
-  const void* dY; const void* X; float* G; float* dbias; const int* lens;
-  int ldy, ldx, B, N, Cin, Cout, skip_halo, reserved;
-  const int* rows_exist;
-};
-int dx_conv_wgrad_batched(const void* jobs_, int njobs, int taps, int dy_bf16, int x_bf16, void* stream) {
+// The launch plan of dx_conv_wgrad_batched (record: include/daft_exprt_hip.h): reads the scalars of the HOST job array, no pointer in it.
+int dx_conv_wgrad_batched_plan(const void* jobs_, int njobs, int taps, int dy_bf16, int x_bf16, int* plan) {
   const DxWgradJob* jobs = reinterpret_cast<const DxWgradJob*>(jobs_);
+  DX_REQUIRE(plan, "dx_conv_wgrad_batched_plan: null pointer");
   DX_REQUIRE(jobs && njobs > 0 && njobs <= WG_MAX_JOBS, "dx_conv_wgrad_batched: 1..%d jobs per launch (got %d)", WG_MAX_JOBS, njobs);
   DX_REQUIRE(taps == 1 || taps == 3, "dx_conv_wgrad_batched: taps must be 1 or 3");
-  WgradBatchArgs a{};
+  const int chunk = wb_bk(taps, dy_bf16 != 0, x_bf16 != 0);
   int tiles = 0, tile_jobs = 0, min_chunks = 0x7fffffff;
   for (int i = 0; i < njobs; ++i) {
     const DxWgradJob& j = jobs[i];
-    DX_REQUIRE(j.dY && j.X && j.G, "dx_conv_wgrad_batched: job %d: null pointer", i);
     DX_REQUIRE(j.B > 0 && j.N > 0 && j.Cin > 0 && j.Cout > 0, "dx_conv_wgrad_batched: job %d: bad dims", i);
     DX_REQUIRE((j.Cin % 128) == 0 && (j.Cout % 8) == 0 && (j.ldx % 8) == 0 && (j.ldy % 8) == 0,
                "dx_conv_wgrad_batched: job %d: Cin must be a multiple of 128, Cout / ld* of 8 (Cin=%d Cout=%d)", i, j.Cin, j.Cout);
-    DX_REQUIRE(((uintptr_t)j.X % 16) == 0 && ((uintptr_t)j.dY % 16) == 0, "dx_conv_wgrad_batched: job %d: pointers must be 16-byte aligned", i);
-    DX_REQUIRE(j.skip_halo < 0 || j.lens, "dx_conv_wgrad_batched: job %d: skip_halo needs lens", i);
-    a.job[i] = WgradJobDev{j.dY, j.X, j.G, j.dbias, j.lens, j.ldy, j.ldx, j.B, j.N, j.Cin, j.Cout, j.skip_halo, 0, j.rows_exist};
     const int t = dx_cdiv(j.Cout, TILE) * (j.Cin / 128);
     tiles = std::max(tiles, t);
     tile_jobs += t;
-    min_chunks = std::min(min_chunks, j.B * dx_cdiv(j.N, wb_bk(taps, dy_bf16 != 0, x_bf16 != 0)));
+    min_chunks = std::min(min_chunks, j.B * dx_cdiv(j.N, chunk));
   }
   // One 512-thread workgroup per CU and round; a launch of many layers runs several rounds (24 layers: 768 workgroups at the same 4-way
   // split), so the atomic epilogues of the early finishers run under the chunk loops of the next round instead of at the end of a launch.
   constexpr int per_round = 256;
   const int rounds = std::max(1, (tile_jobs * 4 + per_round / 2) / per_round);
-  a.ksplit = std::max(1, std::min(min_chunks, rounds * per_round / tile_jobs));
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(tiles, njobs, a.ksplit);
-  a.xcd_group = tiles == 8 && (njobs * a.ksplit) % 8 == 0;
-#ifdef DX_WG_STAMPS
-  a.stamps = g_wgrad_stamps;
-#endif
-  dx_prof_begin(DX_PROF_WGRAD_GEMM, s);
-#define DX_WG_LAUNCH(TAPS_)                                                                                            \
-  if (dy_bf16 && x_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, true, true, 4>), grid, dim3(512), 0, s, a);     \
-  else if (dy_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, true, false, 4>), grid, dim3(512), 0, s, a);         \
-  else if (x_bf16) hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, false, true, 4>), grid, dim3(512), 0, s, a);          \
-  else hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS_, false, false, 4>), grid, dim3(512), 0, s, a);
-  if (taps == 3) { DX_WG_LAUNCH(3) } else { DX_WG_LAUNCH(1) }
-#undef DX_WG_LAUNCH
-  dx_prof_end(DX_PROF_WGRAD_GEMM, s);
-  DX_LAUNCH_CHECK("dx_conv_wgrad_batched");
+  dx_plan_set(plan, DX_K_WGRAD_H16_WIDE, 0, tiles, njobs, std::max(1, std::min(min_chunks, rounds * per_round / tile_jobs)), 512);
+  plan[DX_PLAN_SPLIT] = plan[DX_PLAN_GRID_Z];
+  plan[DX_PLAN_CHUNK] = chunk;
+  plan[DX_PLAN_ROUNDS] = rounds;
   return DX_OK;
 }
 
-int dx_unpack_wgrad(const float* G, float* grad, int Cout, int Cin, int taps, int accumulate, void* stream) {
-  DX_REQUIRE(G && grad && Cout > 0 && Cin > 0 && taps > 0, "dx_unpack_wgrad: bad arguments");
-  const size_t n = (size_t)Cout * Cin * taps;
-  const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, G, grad, Cout, Cin, taps, accumulate);
-  DX_LAUNCH_CHECK("dx_unpack_wgrad");
+// Several weight gradients of one kind in ONE launch (see WgradBatchArgs): bf16 operand mode, every job with Cin % 128 == 0 (the wide
+// tile), same taps and the same operand storage; B, N, lens, channels, leading dimensions and the halo rule are per job.
+int dx_conv_wgrad_batched(const void* jobs_, int njobs, int taps, int dy_bf16, int x_bf16, void* stream) {
+  const DxWgradJob* jobs = reinterpret_cast<const DxWgradJob*>(jobs_);
+  int plan[DX_PLAN_INTS];
+  if (int rc = dx_conv_wgrad_batched_plan(jobs_, njobs, taps, dy_bf16, x_bf16, plan)) return rc;     // also: job count, taps and job dimensions are valid
+  WgradBatchArgs a{};
+  for (int i = 0; i < njobs; ++i) {
+    const DxWgradJob& j = jobs[i];
+    DX_REQUIRE(j.dY && j.X && j.G, "dx_conv_wgrad_batched: job %d: null pointer", i);
+    DX_REQUIRE(((uintptr_t)j.X % 16) == 0 && ((uintptr_t)j.dY % 16) == 0, "dx_conv_wgrad_batched: job %d: pointers must be 16-byte aligned", i);
+    DX_REQUIRE(j.skip_halo < 0 || j.lens, "dx_conv_wgrad_batched: job %d: skip_halo needs lens", i);
+    a.job[i] = WgradJobDev{j.dY, j.X, j.G, j.dbias, j.lens, j.ldy, j.ldx, j.B, j.N, j.Cin, j.Cout, j.skip_halo, 0, j.rows_exist};
+  }
+  a.ksplit = plan[DX_PLAN_SPLIT];
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(plan[DX_PLAN_GRID_X], plan[DX_PLAN_GRID_Y], plan[DX_PLAN_GRID_Z]), block(plan[DX_PLAN_THREADS]);
+  a.xcd_group = grid.x == 8 && (njobs * a.ksplit) % 8 == 0;
+#ifdef DX_WG_STAMPS
+  a.stamps = g_wgrad_stamps;
+#endif
+  if (taps == 3) { DX_WG_LAUNCH(3, 4) } else { DX_WG_LAUNCH(1, 4) }
+#undef DX_WG_LAUNCH
+  DX_LAUNCH_CHECK("dx_conv_wgrad_batched");
   return DX_OK;
 }
 

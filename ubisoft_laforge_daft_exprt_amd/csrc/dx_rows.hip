@@ -639,6 +639,31 @@ inline int row_grid(long rows) { return (int)std::min<long>((rows + 3) / 4, 8192
 
 extern "C" {
 
+// The launch plan of dx_ln_fwd (backward == 0) and dx_ln_bwd (record: include/daft_exprt_hip.h).
+int dx_ln_plan(int B, int N, int C, int backward, int* plan) {
+  DX_REQUIRE(plan, "dx_ln_plan: null pointer");
+  DX_REQUIRE(C == 128 || C == 1024, "%s: C must be 128 or 1024 (got %d)", backward ? "dx_ln_bwd" : "dx_ln_fwd", C);
+  DX_REQUIRE(B > 0 && N > 0, "%s: bad dims", backward ? "dx_ln_bwd" : "dx_ln_fwd");
+  if (!backward) {
+    // one wave per RPW rows, four waves per block, a grid-stride loop over the rest: row_grid caps the grid
+    const int rpw = C == 128 ? RowVec<128>::RPW : RowVec<1024>::RPW;
+    const long rows = (long)B * N;
+    dx_plan_set(plan, DX_K_LN_FWD, 4 * rpw, dx_cdiv(row_grid(rows), rpw), 1, 1, 256);
+    plan[DX_PLAN_SWEEP] = plan[DX_PLAN_GRID_X] * plan[DX_PLAN_TOK];
+    plan[DX_PLAN_PASSES] = (int)((rows + plan[DX_PLAN_SWEEP] - 1) / plan[DX_PLAN_SWEEP]);
+    return DX_OK;
+  }
+  // every block ends in one atomic per channel on the SAME 2 C addresses (dw, dbias): same-address atomics serialise (~15 ns each), so the
+  // block count is a trade between memory parallelism in the row loop and the length of that atomic chain
+  // sixteen-wave blocks for C = 128 once there are rows enough to fill the chip with them (C = 1024 would need 64 KB of LDS per block: slower).
+  // Measured at C2 (frame axis, 43 k rows): C = 128: 4 waves x 64 rows 25.4 us, 16 waves x 256 rows 23.6, 16 x 192 21.4; C = 1024: 4 x 64 94 us, 4 x 96 78
+  const bool big = C == 128 && (long)B * N >= 16384;
+  constexpr int rpb_1024 = 32;   // 96 / 48 / 32 / 24 rows: 6.363 / 6.350 / 6.345 / 6.351 ms per step
+  const int rpb = big ? 192 : (C == 1024 ? rpb_1024 : 64);
+  dx_plan_set(plan, DX_K_LN_BWD, rpb, dx_cdiv(N, rpb), B, 1, 64 * (big ? 16 : 4));
+  return DX_OK;
+}
+
 int dx_ln_fwd(void* av, const void* resv, const float* w, const float* bias, const float* film, int ld_film,
               const int* lens, int halo, void* yv, float* mean, float* rstd, int B, int N, int C,
               uint64_t seed_pre, float p_pre, uint64_t seed_post, float p_post, const uint64_t* seed_offset, int io_bf16, void* y_bf16_copy,
@@ -647,20 +672,18 @@ int dx_ln_fwd(void* av, const void* resv, const float* w, const float* bias, con
   DX_REQUIRE(!y_bf16_copy || (C == 128 && !io_bf16), "dx_ln_fwd: the bf16 shadow output is for fp32 rows with C = 128");
   DX_REQUIRE(a && w && bias && y && mean && rstd, "dx_ln_fwd: null pointer");
   DX_REQUIRE(!io_bf16 || C == 1024, "dx_ln_fwd: bf16 rows are supported for C = 1024 only");
-  DX_REQUIRE(C == 128 || C == 1024, "dx_ln_fwd: C must be 128 or 1024 (got %d)", C);
-  DX_REQUIRE(B > 0 && N > 0, "dx_ln_fwd: bad dims");
+  int plan[DX_PLAN_INTS];
+  if (int rc = dx_ln_plan(B, N, C, 0, plan)) return rc;     // also: C and the dimensions are valid
   DX_REQUIRE(p_pre >= 0.f && p_pre < 1.f && p_post >= 0.f && p_post < 1.f, "dx_ln_fwd: dropout p out of range");
   DX_REQUIRE(!film || ld_film >= 2 * C, "dx_ln_fwd: ld_film too small");
   LnArgs k{a, res, w, bias, film, ld_film, lens, halo, y, (dx_h16*)y_bf16_copy, mean, rstd, B, N,
            seed_pre, (uint32_t)lrintf(p_pre * 65536.f), 1.f / (1.f - p_pre),
            seed_post, (uint32_t)lrintf(p_post * 65536.f), 1.f / (1.f - p_post), seed_offset};
   hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_ROWS, s);
-  const int grid = row_grid((long)B * N);
-  if (C == 128) hipLaunchKernelGGL((ln_fwd_kernel<128, float>), dim3(dx_cdiv(grid, RowVec<128>::RPW)), dim3(256), 0, s, k);
-  else if (io_bf16) hipLaunchKernelGGL((ln_fwd_kernel<1024, dx_h16>), dim3(grid), dim3(256), 0, s, k);
-  else hipLaunchKernelGGL((ln_fwd_kernel<1024, float>), dim3(grid), dim3(256), 0, s, k);
-  dx_prof_end(DX_PROF_ROWS, s);
+  const dim3 grid(plan[DX_PLAN_GRID_X]), block(plan[DX_PLAN_THREADS]);
+  if (C == 128) hipLaunchKernelGGL((ln_fwd_kernel<128, float>), grid, block, 0, s, k);
+  else if (io_bf16) hipLaunchKernelGGL((ln_fwd_kernel<1024, dx_h16>), grid, block, 0, s, k);
+  else hipLaunchKernelGGL((ln_fwd_kernel<1024, float>), grid, block, 0, s, k);
   DX_LAUNCH_CHECK("dx_ln_fwd");
   return DX_OK;
 }
@@ -679,9 +702,7 @@ int dx_proj_ln_fwd(const void* X, int ldx, const void* Wpack, const float* proj_
                LnArgs{z, res, w, bias, film, ld_film, lens, halo, y, (dx_h16*)y_bf16_copy, mean, rstd, B, N,
                       seed_pre, (uint32_t)lrintf(p_pre * 65536.f), 1.f / (1.f - p_pre), 0, 0u, 1.f, seed_offset}};
   hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_ROWS, s);
   hipLaunchKernelGGL(proj_ln_fwd_kernel, dim3((unsigned)(((long)B * N + 63) / 64)), dim3(256), 0, s, k);
-  dx_prof_end(DX_PROF_ROWS, s);
   DX_LAUNCH_CHECK("dx_proj_ln_fwd");
   return DX_OK;
 }
@@ -695,30 +716,23 @@ int dx_ln_bwd(const void* dyv, const void* zv, const float* mean, const float* r
   DX_REQUIRE(!dg_bf16_copy || (C == 128 && !io_bf16), "dx_ln_bwd: the bf16 shadow output is for fp32 rows with C = 128"); const float* z = (const float*)zv; float* dz = (float*)dzv; float* da = (float*)dav;
   DX_REQUIRE(!io_bf16 || C == 1024, "dx_ln_bwd: bf16 rows are supported for C = 1024 only");
   DX_REQUIRE(dy && z && mean && rstd && w && bias && dz && dw && dbias, "dx_ln_bwd: null pointer");
-  DX_REQUIRE(C == 128 || C == 1024, "dx_ln_bwd: C must be 128 or 1024 (got %d)", C);
+  int plan[DX_PLAN_INTS];
+  if (int rc = dx_ln_plan(B, N, C, 1, plan)) return rc;     // also: C and the dimensions are valid
   DX_REQUIRE((film == nullptr) == (dfilm == nullptr), "dx_ln_bwd: film and dfilm must come together");
-  // every block ends in one atomic per channel on the SAME 2 C addresses (dw, dbias): same-address atomics serialise (~15 ns each), so the
-  // block count is a trade between memory parallelism in the row loop and the length of that atomic chain
-  // sixteen-wave blocks for C = 128 once there are rows enough to fill the chip with them (C = 1024 would need 64 KB of LDS per block: slower).
-  // Measured at C2 (frame axis, 43 k rows): C = 128: 4 waves x 64 rows 25.4 us, 16 waves x 256 rows 23.6, 16 x 192 21.4; C = 1024: 4 x 64 94 us, 4 x 96 78
-  const bool big = C == 128 && (long)B * N >= 16384;
-  constexpr int rpb_1024 = 32;   // 96 / 48 / 32 / 24 rows: 6.363 / 6.350 / 6.345 / 6.351 ms per step
-  const int rpb = big ? 192 : (C == 1024 ? rpb_1024 : 64);
+  const int rpb = plan[DX_PLAN_TOK];
   LnBwdArgs k{dy, z, mean, rstd, w, bias, film, ld_film, lens, halo, dz, da, (dx_h16*)dg_bf16_copy, dw, dbias, dfilm, ld_dfilm, B, N, rpb, relu_mask,
               seed_pre, (uint32_t)lrintf(p_pre * 65536.f), 1.f / (1.f - p_pre),
               seed_post, (uint32_t)lrintf(p_post * 65536.f), 1.f / (1.f - p_post), seed_offset};
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(dx_cdiv(N, rpb), B);
-  dx_prof_begin(DX_PROF_ROWS, s);
+  const dim3 grid(plan[DX_PLAN_GRID_X], plan[DX_PLAN_GRID_Y]), block(plan[DX_PLAN_THREADS]);
 #define DX_LN_BWD(CC, IO, WAVES) do { \
-    if (film) hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, true, WAVES>), grid, dim3(64 * WAVES), 0, s, k); \
-    else hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, false, WAVES>), grid, dim3(64 * WAVES), 0, s, k); } while (0)
-  if (big) DX_LN_BWD(128, float, 16);
+    if (film) hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, true, WAVES>), grid, block, 0, s, k); \
+    else hipLaunchKernelGGL((ln_bwd_kernel<CC, IO, false, WAVES>), grid, block, 0, s, k); } while (0)
+  if (plan[DX_PLAN_THREADS] == 64 * 16) DX_LN_BWD(128, float, 16);
   else if (C == 128) DX_LN_BWD(128, float, 4);
   else if (io_bf16) DX_LN_BWD(1024, dx_h16, 4);
   else DX_LN_BWD(1024, float, 4);
 #undef DX_LN_BWD
-  dx_prof_end(DX_PROF_ROWS, s);
   DX_LAUNCH_CHECK("dx_ln_bwd");
   return DX_OK;
 }

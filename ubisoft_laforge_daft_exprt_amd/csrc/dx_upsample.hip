@@ -458,11 +458,9 @@ int dx_upsample_fwd(const float* xs, const float* mu, const float* sigma, const 
   DX_REQUIRE(Dm == D && B > 0 && L > 0 && T > 0, "dx_upsample_fwd: bad dims (D must be 128)");
   UpArgs a{xs, mu, sigma, lens, weights, xup, B, L, T};
   hipStream_t s = (hipStream_t)stream;
-  dx_prof_begin(DX_PROF_UPSAMPLE, s);
   // 16-frame tiles (64 / 32 / 16 frames measured 39.5 / 30.9 / 26.6 us)
   DX_REQUIRE(fwd_smem<16>(L) <= LDS_BUDGET, "dx_upsample_fwd: L=%d too long for the LDS weight tile", L);
   launch_fwd<16>(a, s);
-  dx_prof_end(DX_PROF_UPSAMPLE, s);
   DX_LAUNCH_CHECK("dx_upsample_fwd");
   return DX_OK;
 }

@@ -6,6 +6,7 @@ arithmetic on the path is done by libdaft_exprt_hip.so.  Every wrapper launches 
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
 
@@ -284,17 +285,26 @@ def conv_gemm(x, pack: PackedWeight, bias=None, *, transpose=False, relu=False, 
     return out
 
 
-_FF_FUSED_MIN_TILES = 96       # 126-token tiles (the frame axis)
-_FF_FUSED_MIN_TILES62 = 64     # 62-token tiles (short batches: the symbol axis)
+_FF_FUSED_MIN_TILES62 = 64     # the fused launch is worth it from 64 tiles of 62 tokens (short batches: the symbol axis)
+
+
+@functools.lru_cache(maxsize=None)
+def _ff_pair_tiles(B, N):
+    """(tokens per tile, tiles) of the fused feed-forward pair on a (B, N) batch: the library's own plan, kept per shape"""
+    p = _lib.plan('dx_ff_pair_plan', B, N)
+    return p.tok, p.grid_x
 
 
 def ff_pair_applies(x, pack1: PackedWeight, pack2: PackedWeight, prec) -> bool:
     """The fused feed-forward kernel serves bf16 operand mode at the reference shape (128 -> F -> 128, k = 3) when the launch has
-    enough 126-token tiles to occupy the chip: one workgroup per tile runs ~40 us whatever the grid, so the short symbol-level
-    batches (48 tiles at C2: measured 40 vs 37 us forward, 55 vs 42 us backward) stay on the two-launch path."""
-    return (prec in _H16 and x.dtype == _H16[prec] and x.dim() == 3 and x.shape[2] == 128 and pack1.taps == 3 and pack2.taps == 3
-            and pack1.cin == 128 and pack2.cout == 128 and pack2.cin == pack1.cout and pack1.cout % 128 == 0
-            and (x.shape[0] * ((x.shape[1] + 125) // 126) >= _FF_FUSED_MIN_TILES or x.shape[0] * ((x.shape[1] + 61) // 62) >= _FF_FUSED_MIN_TILES62))
+    enough tiles to occupy the chip -- the library picks 126-token tiles where they do (dx_ff_pair_plan), else 62-token ones: one
+    workgroup per tile runs ~40 us whatever the grid, so the short symbol-level batches (48 tiles at C2: measured 40 vs 37 us forward,
+    55 vs 42 us backward) stay on the two-launch path."""
+    if not (prec in _H16 and x.dtype == _H16[prec] and x.dim() == 3 and x.shape[2] == 128 and pack1.taps == 3 and pack2.taps == 3
+            and pack1.cin == 128 and pack2.cout == 128 and pack2.cin == pack1.cout and pack1.cout % 128 == 0):
+        return False
+    tok, tiles = _ff_pair_tiles(int(x.shape[0]), int(x.shape[1]))
+    return tok == 126 or tiles >= _FF_FUSED_MIN_TILES62
 
 
 def ff_pair(x, pack1: PackedWeight, pack2: PackedWeight, bias1, bias2, lens, *, backward=False, aux=None, out=None, accumulate=False,

@@ -37,18 +37,18 @@ class Geometry:
         return self.by_n.get((B, N), (B * N, B * N * N))[1]
 
 
-def _conv_route(a):
-    """Mirror of the kernel choice in csrc/dx_gemm.hip dx_conv_gemm (for labelling only)."""
-    if not a['bf16']:
-        return 'conv_gemm_kernel<f32>'
-    if a['bf16'] == 2:
-        return 'conv_gemm_kernel<bf16x3>'
-    cinp = (a['Cin'] + 63) // 64 * 64
-    if cinp >= 256 and a['Cin'] % 64 == 0:
-        return f"conv_dk_kernel<{a['taps']}>"
-    if cinp == 128 and a['B'] * ((a['N'] + 127) // 128) >= 64:
-        return f"conv_ws_kernel<{a['taps']}>"
-    return 'conv_gemm_kernel<bf16>'
+# kernel id of a launch plan (include/daft_exprt_hip.h DX_K_*, as _lib.plan names it) -> the label's text, ``{}`` = taps
+_LABELS = {'conv_gemm_f32': 'conv_gemm_kernel<f32>', 'conv_gemm_h16': 'conv_gemm_kernel<bf16>', 'conv_gemm_split': 'conv_gemm_kernel<bf16x3>',
+           'conv_dk': 'conv_dk_kernel<{}>', 'conv_ws': 'conv_ws_kernel<{}>', 'wgrad_f32': 'wgrad_kernel<{}>', 'wgrad_split': 'wgrad_split_kernel<{},bf16x3>',
+           'wgrad_h16': 'wgrad_bf16_kernel<{}>', 'wgrad_h16_wide': 'wgrad_bf16_kernel<{},wide>'}
+
+
+def _label(entry, a, *names):
+    """The label of the kernel the library's dispatcher launches for the recorded arguments ``a``: its own plan, asked with ``names``
+    (a record without a leading dimension is a dense tensor: ldx = Cin, ldy = Cout)."""
+    from ._lib import plan
+    a = dict({'ldx': a['Cin'], 'ldy': a['Cout']}, **a)
+    return _LABELS[plan(entry, *(int(a[k]) for k in names)).kernel].format(a['taps'])
 
 
 def price(name, a, geom: Geometry):
@@ -63,7 +63,7 @@ def price(name, a, geom: Geometry):
         wb = 2 if a['bf16'] == 1 else 4
         byt = rows * (a['Cin'] * xb + a['Cout'] * yb * (2 if a['accumulate'] else 1) + (a['Cout'] * ab if has('relu_aux') else 0)) \
             + a['taps'] * a['Cin'] * a['Cout'] * wb
-        return _conv_route(a), 'mfma', 2.0 * a['taps'] * a['Cin'] * a['Cout'] * rows, byt
+        return _label('dx_conv_gemm_plan', a, 'B', 'N', 'Cin', 'Cout', 'taps', 'bf16', 'ldx'), 'mfma', 2.0 * a['taps'] * a['Cin'] * a['Cout'] * rows, byt
     if name == 'dx_ff_pair':
         rows = geom.rows(a['B'], a['N'], has('lens'))
         F = a['F']
@@ -92,10 +92,7 @@ def price(name, a, geom: Geometry):
     if name == 'dx_conv_wgrad':
         rows = geom.rows(a['B'], a['N'], has('lens'))
         byt = rows * (a['Cout'] * (2 if a['dy_bf16'] else 4) + a['Cin'] * (2 if a['x_bf16'] else 4)) + a['taps'] * a['Cin'] * a['Cout'] * 4
-        wide = a['Cin'] % 128 == 0 and -(-a['Cout'] // 128) * -(-a['Cin'] // 64) >= 64      # the library's choice of the 128 x 128 tile (dx_gemm.hip)
-        label = (f"wgrad_split_kernel<{a['taps']},bf16x3>" if a['bf16'] == 2
-                 else f"wgrad_bf16_kernel<{a['taps']}{',wide' if wide else ''}>" if a['bf16'] and a['Cin'] % 8 == 0 and a['Cout'] % 8 == 0
-                 else f"wgrad_kernel<{a['taps']}>")
+        label = _label('dx_conv_wgrad_plan', a, 'B', 'N', 'Cin', 'Cout', 'taps', 'bf16', 'ldx', 'ldy', 'dy_bf16', 'x_bf16')
         return label, 'mfma', 2.0 * a['taps'] * a['Cin'] * a['Cout'] * rows, byt
     if name == 'dx_conv_wgrad_batched':
         from . import ops
