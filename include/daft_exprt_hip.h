@@ -384,8 +384,14 @@ int dx_adam_step_dyn(float* p, const float* g, float* m, float* v, long n, float
  * Activations are fp32, channels-last [B][samples][C] (conv_pre reads the (B, 80, T) mel through its strides).  frames (device int32
  * [B]) with a samples-per-frame scale gives each batch row's valid length: input rows at or past it read as the conv's zero padding,
  * output rows there are written as 0, so batch row b equals what the same row computes alone (bitwise: fixed summation order, no
- * atomics).  bf16 = 0: exact f32 (v_mfma_f32_16x16x4_f32), 1: bf16 operands (v_mfma_f32_16x16x32_bf16), fp32 accumulate and storage. */
-/* bytes of the weight pack dx_voc_pack writes for one layer (up > 1: a ConvTranspose1d in polyphase form, taps = 2) */
+ * atomics).  bf16 (operand mode) = 0: exact f32 (v_mfma_f32_16x16x4_f32), 1: bf16 operands (v_mfma_f32_16x16x32_bf16), 2: split bf16
+ * (dx_voc_pack[_size], dx_voc_conv[_win], dx_voc_pair[_win]; dx_voc_chain[_win] refuses it): every operand is x = hi + lo, hi =
+ * bf16_rne(x), lo = bf16_rne(x - hi), lo = 0 where hi is not finite, every product hi*lo + lo*hi + hi*hi in that order on three
+ * v_mfma_f32_16x16x32_bf16 (~16 mantissa bits).  Activations are split after the fp32 leaky-ReLU while they are staged, weights once
+ * by dx_voc_pack.  fp32 accumulate and storage in every mode; a pack serves the mode it was written for and no other. */
+/* bytes of the weight pack dx_voc_pack writes for one layer (up > 1: a ConvTranspose1d in polyphase form, taps = 2).  Mode 2 packs a
+ * lane's eight hi then its eight lo per k step: 32 bytes, so the pack is the f32 pack's size whenever Cin % 32 == 0 (and rounds Cin up
+ * to 32 where the f32 pack rounds it to 16). */
 int dx_voc_pack_size(int Cout, int Cin, int taps, int up, int bf16, long* bytes);
 /* folded weights -> the operand pack of dx_voc_conv / dx_voc_pair.  up == 1: W (Cout, Cin, taps) of a Conv1d; up > 1 (even): W (Cin,
  * Cout, 2 up) of ConvTranspose1d(stride up, padding up / 2), packed as up phases of 2 taps (output sample s up + r reads input

@@ -8,7 +8,10 @@
   kernels_us              the three kernels of csrc/dx_prosody.hip alone (event-bracketed means): symbol means for the batch's frames,
                           conditioning, PCM of the batch's audio
 
-    python tools/bench_synthesis.py [--precision bf16]
+    python tools/bench_synthesis.py [--precision bf16|bf16x3]
+
+--precision is the acoustic model's and the vocoder's alike: f32, bf16 or bf16x3 (any other reduced precision of the acoustic model runs
+the bf16 vocoder).
 """
 import json
 import os
@@ -81,7 +84,7 @@ def main():
     hp = helpers.golden_hparams(stats=STATS)
     model = dx.DaftExprt(hp).to(DEV)
     model.load_state_dict(helpers.golden_state_dict(), strict=True)
-    vocoder = dx.HiFiGanVocoder(vh.state_dict(), device=DEV, precision='bf16' if precision != 'f32' else 'f32')
+    vocoder = dx.HiFiGanVocoder(vh.state_dict(), device=DEV, precision=precision if precision in dx.vocoder.PRECISIONS else 'bf16')
     inputs, prosody, spk, accent = synthetic_inference_batch(batch_size=16, sym_len_range=(80, 100), seed=1238)
     lens = inputs[4].tolist()
     frames = prosody['duration_preds'] * hp.sampling_rate / hp.hop_length

@@ -1,13 +1,16 @@
 """HiFi-GAN vocoder throughput (V1, or V2 / V3 with --config): B = 16 synthetic utterances of up to 850 frames (C4-like lengths), synthetic weights.
-One JSON line: mel frames/s, seconds of 22.05 kHz audio per second and TFLOP/s against 614 MFLOP per frame, for the HIP path (f32, bf16),
-tests/vocoder_torch.py batched on the same GPU (fp32, bf16) and vocoder_torch at B = 1 per utterance (fp32: the reference's way; bf16).
+One JSON line: mel frames/s, seconds of 22.05 kHz audio per second and TFLOP/s against 614 MFLOP per frame, for the HIP path (f32, bf16,
+bf16x3), tests/vocoder_torch.py batched on the same GPU (fp32, bf16) and vocoder_torch at B = 1 per utterance (fp32: the reference's way; bf16).
 Every rate divides VALID frames by the time.  The HIP path computes valid frames only (tiles past a row's length write zeros); the batched
 torch rows compute the whole padded (B, 80, T_max) grid ('frames_computed'), the B = 1 rows exactly the valid frames, so
 'hip_bf16_over_torch_bf16_b1' compares equal work and 'hip_bf16_over_torch_bf16' what a caller with a padded batch gets.
 
-    python tools/bench_vocoder.py [--config v1|v2|v3] [--profile] [--hip-only]
+    python tools/bench_vocoder.py [--config v1|v2|v3] [--profile] [--hip-only] [--rounds N]
 
---profile: + per-kernel times of one bf16 and one f32 HIP call; --hip-only: without the torch rows (whose first calls spend minutes in
+--rounds N: + 'rounds': the three HIP modes timed alternately (f32, bf16x3, bf16; N rounds after one untimed round), per mode the
+times of every round, their median and spread (max - min), the ratio of the f32 to the bf16x3 median, and for the bf16x3 mode what
+``stream`` takes at 32 frames a chunk: the first chunk's latency (median of 3) and the workspace against ``infer_batch``'s.
+--profile: + per-kernel times of one HIP call in each mode; --hip-only: without the torch rows (whose first calls spend minutes in
 MIOpen's search over the 16 utterance lengths).
 
 --config v2 / v3: the same batch through the V2 / V3 generator (the same torch rows), FLOP per frame
@@ -15,6 +18,7 @@ counted from the configuration's own (unpadded) layer shapes; the default, v1, p
 """
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -63,6 +67,40 @@ def rates(t, frames, computed=None):
     return r
 
 
+def alternated(voc_by, mels, lens_dev, frames, n_rounds):
+    """The modes in turn, round after round, so that a drift of the clocks meets all of them alike."""
+    order = ('f32', 'bf16x3', 'bf16')
+    times = {p: [] for p in order}
+    for r in range(n_rounds + 1):                                     # round 0 warms every mode up and is not kept
+        for p in order:
+            t = timed(lambda: voc_by[p].infer_batch(mels, lens_dev), n=8, warm=1)
+            if r:
+                times[p].append(t)
+    out = {p: {'s': [round(t, 5) for t in ts], 'median_s': round(statistics.median(ts), 5), 'spread_s': round(max(ts) - min(ts), 5),
+               'tflops': round(frames * MFLOP_PER_FRAME * 1e6 / statistics.median(ts) / 1e12, 2)} for p, ts in times.items()}
+    out['f32_over_bf16x3'] = round(out['f32']['median_s'] / out['bf16x3']['median_s'], 3)
+    out['bf16x3_over_bf16'] = round(out['bf16x3']['median_s'] / out['bf16']['median_s'], 3)
+    out['bf16x3_faster_than_f32_by_more_than_the_spread'] = bool(
+        min(times['f32']) - max(times['bf16x3']) > max(out[p]['spread_s'] for p in order))
+    return out
+
+
+def stream_record(v, mels, lens_dev, F=32):
+    """first-chunk latency of ``stream`` (from its call to a synchronise after chunk 0; median of 3 after one warm-up) and workspace"""
+    def first():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        s = v.stream(mels, lens_dev, chunk_frames=F, clone=False)
+        next(s)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, s
+    first()
+    runs = [first() for _ in range(3)]
+    return {'chunk_frames': F, 'first_chunk_ms': round(statistics.median(t for t, _ in runs) * 1e3, 3),
+            'workspace': {'stream': runs[0][1].workspace_bytes, 'stream_rings_per_row': runs[0][1].plan.ring_bytes(1),
+                          'infer_batch': B * T_MAX * voc.workspace_bytes_per_frame(v.config)}}
+
+
 def main():
     global MFLOP_PER_FRAME
     dev = 'cuda'
@@ -87,7 +125,7 @@ def main():
         out['config'] = name
     voc_by = {}
     with torch.no_grad():
-        for prec in ('f32', 'bf16'):
+        for prec in ('f32', 'bf16', 'bf16x3'):
             v = voc.HiFiGanVocoder(sd, config=cfg, device=dev, precision=prec)
             voc_by[prec] = v
             out[f'hip_{prec}'] = rates(timed(lambda: v.infer_batch(mels, lens_dev)), frames)
@@ -104,9 +142,12 @@ def main():
             out['torch_bf16_b1'] = rates(timed(lambda: [torch_generator(m, w16) for m in per16], n=2, warm=1), frames, frames)
             out['hip_bf16_over_torch_bf16'] = round(out['torch_bf16_batched']['s'] / out['hip_bf16']['s'], 2)
             out['hip_bf16_over_torch_bf16_b1'] = round(out['torch_bf16_b1']['s'] / out['hip_bf16']['s'], 2)
+        if '--rounds' in sys.argv:
+            out['rounds'] = alternated(voc_by, mels, lens_dev, frames, int(sys.argv[sys.argv.index('--rounds') + 1]))
+            out['stream_bf16x3'] = stream_record(voc_by['bf16x3'], mels, lens_dev)
         if '--profile' in sys.argv:
             geom = profiling.Geometry([lengths.tolist()])
-            for prec in ('bf16', 'f32'):
+            for prec in ('bf16', 'f32', 'bf16x3'):
                 recs = []
                 old = _lib.set_timer(recs)
                 voc_by[prec].infer_batch(mels, lens_dev)

@@ -1,5 +1,5 @@
 """Streaming HiFi-GAN vocoder against the whole call, on tools/bench_vocoder.py's batch (B = 16 utterances of 425 .. 850 frames,
-synthetic weights) and on its longest row alone (B = 1), for chunks of 8, 32 and 128 mel frames in both operand modes.  One JSON line;
+synthetic weights) and on its longest row alone (B = 1), for chunks of 8, 32 and 128 mel frames in every operand mode (f32, bf16, bf16x3).  One JSON line;
 per case:
 
     first_chunk_ms       from the call of ``stream`` (rings allocated and zeroed there) to a synchronise after chunk 0; median of 3
@@ -78,7 +78,7 @@ def main():
     if name != 'v1':
         out['config'] = name
     with torch.no_grad():
-        for prec in ('f32', 'bf16'):
+        for prec in ('f32', 'bf16', 'bf16x3'):
             v = voc.HiFiGanVocoder(sd, config=cfg, device=dev, precision=prec)
             for nb in ((1,) if quick else (1, B)):
                 m, lens = mels[:nb].contiguous(), lengths[:nb].tolist()

@@ -124,6 +124,42 @@ template <> struct DxMmaOp<true> {
   }
 };
 
+// The same trait by C ABI operand mode (0 exact f32, 1 bf16, 2 split bf16), for the kernels that take all three.  An operand is IMG
+// images of T, a lane's fragment one uint4 per image: modes 0 and 1 are DxMmaOp as it stands with one image; mode 2 keeps a hi and
+// a lo bf16 image with bf16's k map (KS, VEC, PAD), so its operand bytes are the f32 mode's.
+//   put / put4(d, los, v): write fp32 values as operand elements at d (mode 2: the lo image los elements further on);
+//   mma(a, b, c): a and b the fragments of every image ([0] hi, [1] lo).
+template <int MODE> struct DxMmaMode : DxMmaOp<MODE != 0> {
+  typedef DxMmaOp<MODE != 0> Base;
+  typedef typename Base::T T;
+  static constexpr int IMG = 1;
+  __device__ static __forceinline__ void put(T* d, int, float v) { *d = Base::cvt(v); }
+  __device__ static __forceinline__ void put4(T* d, int, const float4& v) {
+    d[0] = Base::cvt(v.x); d[1] = Base::cvt(v.y); d[2] = Base::cvt(v.z); d[3] = Base::cvt(v.w);
+  }
+  __device__ static __forceinline__ f32x4 mma(const uint4 (&a)[1], const uint4 (&b)[1], f32x4 c) { return Base::mma(a[0], b[0], c); }
+};
+template <> struct DxMmaMode<2> {
+  typedef __bf16 T;
+  static constexpr int KS = 32, VEC = 8, PAD = 8, IMG = 2;
+  __device__ static __forceinline__ void put(T* d, int los, float v) {
+    unsigned h, l;
+    split_bf16x2(v, 0.f, h, l);
+    *reinterpret_cast<unsigned short*>(d) = (unsigned short)h;
+    *reinterpret_cast<unsigned short*>(d + los) = (unsigned short)l;
+  }
+  __device__ static __forceinline__ void put4(T* d, int los, const float4& v) {      // d 8-byte aligned, los % 4 == 0
+    uint2 h, l;
+    split_bf16x4(f32x4{v.x, v.y, v.z, v.w}, h, l);
+    *reinterpret_cast<uint2*>(d) = h;
+    *reinterpret_cast<uint2*>(d + los) = l;
+  }
+  __device__ static __forceinline__ f32x4 mma(const uint4 (&a)[2], const uint4 (&b)[2], f32x4 c) {
+    return dx_mma_split3(__builtin_bit_cast(dx_bf16x8, a[0]), __builtin_bit_cast(dx_bf16x8, a[1]), __builtin_bit_cast(dx_bf16x8, b[0]),
+                         __builtin_bit_cast(dx_bf16x8, b[1]), c);
+  }
+};
+
 // ---- wave64 reductions -------------------------------------------------------------------------
 __device__ __forceinline__ float dx_wave_sum(float v) {
 #pragma unroll

@@ -6,6 +6,9 @@
 // valid length read as zero), W a pack of dx_voc_pack read fragment by fragment from L2.  Exact-f32 mode: v_mfma_f32_16x16x4_f32
 // (four per 16-wide k step, each lane's float4 holds k = 4g..4g+3); bf16 mode: v_mfma_f32_16x16x32_bf16 (lane (row, g) holds
 // k = 8g..8g+7), fp32 accumulation, fp32 storage between layers.  A and B use the same k map, so any permutation inside a step cancels.
+// Split-bf16 mode (operand mode 2): bf16's k map on a hi and a lo bf16 image of every operand (x = hi + lo, dx_common.h); a product is
+// hi*lo + lo*hi + hi*hi, three bf16 MFMAs, fp32 accumulation.  Activations are split while staging (after the fp32 leaky-ReLU), the
+// pair's intermediate when it is written to LDS, the weights ONCE by dx_voc_pack: no conv kernel splits a weight.
 //
 // Valid lengths.  Every launch takes frames[b] (device int32) and the samples per frame of its input; rows of batch row b at or
 // past frames[b] * scale do not exist: they are the conv's zero padding when read and are written as 0.  Tiles start at sample 0 of
@@ -55,10 +58,11 @@ __device__ __forceinline__ void voc_window(const WinArgs& w, int len, int& lo, i
 // A[rr][cc] = lrelu?(X[b][row0 + rr][c0 + cc]) for rr < R, cc < kcw; 0 outside [0, len) x [0, Cin).  Channels-last rows (sxc == 1,
 // sxn >= Cin) are read as float4; any other layout (the (B, 80, T) mel, whose channel stride is 1 too when T == 1) element-wise.
 // WIN: row n is read from ring slot n & mask.
-template <bool BF, bool WIN>
-__device__ __forceinline__ void voc_stage(typename DxMmaOp<BF>::T* A, int lda, int R, const float* X, long sxn, long sxc,
+// Mode 2: the hi image at A, the lo image los elements further on.
+template <int MODE, bool WIN>
+__device__ __forceinline__ void voc_stage(typename DxMmaMode<MODE>::T* A, int lda, int los, int R, const float* X, long sxn, long sxc,
                                           int row0, int len, int c0, int kcw, int Cin, int pro, int mask) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<MODE> Op;
   if (sxc == 1 && sxn >= Cin) {
     const int q = kcw >> 2;
     for (int e = threadIdx.x; e < R * q; e += THREADS) {
@@ -68,8 +72,7 @@ __device__ __forceinline__ void voc_stage(typename DxMmaOp<BF>::T* A, int lda, i
         v = *reinterpret_cast<const float4*>(X + (long)(WIN ? n & mask : n) * sxn + c);
         if (pro) { v.x = lrelu(v.x); v.y = lrelu(v.y); v.z = lrelu(v.z); v.w = lrelu(v.w); }
       }
-      typename Op::T* d = A + rr * lda + cc;
-      d[0] = Op::cvt(v.x); d[1] = Op::cvt(v.y); d[2] = Op::cvt(v.z); d[3] = Op::cvt(v.w);
+      Op::put4(A + rr * lda + cc, los, v);
     }
   } else {
     for (int e = threadIdx.x; e < R * kcw; e += THREADS) {
@@ -79,28 +82,36 @@ __device__ __forceinline__ void voc_stage(typename DxMmaOp<BF>::T* A, int lda, i
         v = X[(long)(WIN ? n & mask : n) * sxn + (long)c * sxc];
         if (pro) v = lrelu(v);
       }
-      A[rr * lda + cc] = Op::cvt(v);
+      Op::put(A + rr * lda + cc, los, v);
     }
   }
 }
 
 // acc[i][j] += sum_t sum_{k step s < nks} A[(16 mb_j + row + t*dil)][s*KS ...] * W[t][nb_i][ks0 + s]
 // wave (wn, wm) owns column blocks nb_i = wn + i*WN and row blocks mb_j = wm + j*WM (< MB).
-template <bool BF, int NI, int MI>
-__device__ __forceinline__ void voc_mma(const typename DxMmaOp<BF>::T* A, int lda, int MB, int taps, int dil, const uint4* Wp,
+// Wp holds IMG 16-byte fragments per lane and step, back to back; A's lo image (mode 2) is los elements past A.  The fragments are
+// loaded by plain statements over the images, not through the trait: the one-image instantiations then compile to what they did
+// before there was a second image.
+template <int MODE, int NI, int MI>
+__device__ __forceinline__ void voc_mma(const typename DxMmaMode<MODE>::T* A, int lda, int los, int MB, int taps, int dil, const uint4* Wp,
                                         int NB, int KST, int ks0, int nks, int wn, int WN, int wm, int WM, f32x4 (&acc)[NI][MI]) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<MODE> Op;
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   for (int t = 0; t < taps; ++t) {
     for (int s = 0; s < nks; ++s) {
-      uint4 b[NI];
+      uint4 b[NI][Op::IMG];
 #pragma unroll
-      for (int i = 0; i < NI; ++i) b[i] = Wp[((long)(t * NB + wn + i * WN) * KST + ks0 + s) * 64 + lane];
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int m = 0; m < Op::IMG; ++m) b[i][m] = Wp[(((long)(t * NB + wn + i * WN) * KST + ks0 + s) * 64 + lane) * Op::IMG + m];
 #pragma unroll
       for (int j = 0; j < MI; ++j) {
         const int mb = wm + j * WM;
         if (mb < MB) {
-          const uint4 a = *reinterpret_cast<const uint4*>(A + (mb * 16 + r + t * dil) * lda + s * Op::KS + g * Op::VEC);
+          uint4 a[Op::IMG];
+#pragma unroll
+          for (int m = 0; m < Op::IMG; ++m)
+            a[m] = *reinterpret_cast<const uint4*>(A + m * los + (mb * 16 + r + t * dil) * lda + s * Op::KS + g * Op::VEC);
 #pragma unroll
           for (int i = 0; i < NI; ++i) acc[i][j] = Op::mma(a, b[i], acc[i][j]);
         }
@@ -124,9 +135,9 @@ struct ConvArgs {
 };
 
 // One conv (up == 1) or one phase of a transposed conv (up > 1, grid.z = phase) on a 64-sample tile of one batch row.
-template <bool BF, int NI, int MI, bool WIN>
+template <int MODE, int NI, int MI, bool WIN>
 __global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p, WinArgs win) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<MODE> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
   T* A = reinterpret_cast<T*>(voc_smem);
@@ -153,9 +164,9 @@ __global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p, WinArgs w
   const uint4* Wp = p.Wp;
   if (p.up > 1) {
     pad = (ph + p.up / 2 < p.up) ? 1 : 0;
-    Wp += (long)ph * 2 * NB * p.KST * 64;
+    Wp += (long)ph * 2 * NB * p.KST * 64 * Op::IMG;
   }
-  const int rows = VT + (p.taps - 1) * p.dil, lda = KC + Op::PAD;
+  const int rows = VT + (p.taps - 1) * p.dil, lda = KC + Op::PAD, los = rows * lda;
   const float* X = p.X + b * p.sxb;
   f32x4 acc[NI][MI];
 #pragma unroll
@@ -166,9 +177,9 @@ __global__ void __launch_bounds__(THREADS) voc_conv_kernel(ConvArgs p, WinArgs w
   for (int c0 = 0; c0 < KP; c0 += KC) {
     const int kcw = min(KC, KP - c0);
     __syncthreads();
-    voc_stage<BF, WIN>(A, lda, rows, X, p.sxn, p.sxc, m0 - pad, in_len, c0, kcw, p.Cin, p.pro, win.mx);
+    voc_stage<MODE, WIN>(A, lda, los, rows, X, p.sxn, p.sxc, m0 - pad, in_len, c0, kcw, p.Cin, p.pro, win.mx);
     __syncthreads();
-    voc_mma<BF, NI, MI>(A, lda, 4, p.taps, p.dil, Wp, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc);
+    voc_mma<MODE, NI, MI>(A, lda, los, 4, p.taps, p.dil, Wp, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc);
   }
   const float* R = p.R ? p.R + b * p.srb : nullptr;
 #pragma unroll
@@ -212,9 +223,10 @@ struct PairArgs {
 };
 
 // Y = acc_mode( conv2(lrelu(conv1(lrelu(X)) + b1)) + b2 + X ): one ResBlock1 pair, intermediate (80 rows with halo) in LDS.
-template <bool BF, int MI1, int MI2, bool WIN>
+// LDS: A's images, then M's (mode 2: A hi, A lo, M hi, M lo).
+template <int MODE, int MI1, int MI2, bool WIN>
 __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs win) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<MODE> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
   const int b = blockIdx.y, C = p.C;
@@ -236,11 +248,11 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs w
   const int h2 = (p.taps - 1) / 2, h1 = p.dil * h2;
   // KP: C rounded up to whole K steps (C = 16 in bf16 mode is half a step: the pack holds zeros there, so A and M must hold zeros too)
   const int KP = p.KST * Op::KS;
-  const int rows = MIDR + 2 * h1, lda = KC + Op::PAD, ldm = KP + Op::PAD;
+  const int rows = MIDR + 2 * h1, lda = KC + Op::PAD, ldm = KP + Op::PAD, los = rows * lda, mos = MIDR * ldm;
   T* A = reinterpret_cast<T*>(voc_smem);
-  T* M = A + rows * lda;
+  T* M = A + Op::IMG * los;
   if (KP > C)                                        // columns C .. KP - 1 of M are operands too: zero (the first sync below orders this)
-    for (int e = threadIdx.x; e < MIDR * ldm; e += THREADS) M[e] = Op::cvt(0.f);
+    for (int e = threadIdx.x; e < MIDR * ldm; e += THREADS) Op::put(M + e, mos, 0.f);
   const int NB = C / 16, WN = NB < 4 ? NB : 4, WM = 4 / WN, wn = w % WN, wm = w / WN;
   const float* X = p.X + b * p.sxb;
   f32x4 acc1[1][MI1];
@@ -249,9 +261,9 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs w
   for (int c0 = 0; c0 < KP; c0 += KC) {
     const int kcw = min(KC, KP - c0);
     __syncthreads();
-    voc_stage<BF, WIN>(A, lda, rows, X, C, 1, s0 - h2 - h1, len, c0, kcw, C, 1, win.mx);
+    voc_stage<MODE, WIN>(A, lda, los, rows, X, C, 1, s0 - h2 - h1, len, c0, kcw, C, 1, win.mx);
     __syncthreads();
-    voc_mma<BF, 1, MI1>(A, lda, MIDR / 16, p.taps, p.dil, p.W1, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc1);
+    voc_mma<MODE, 1, MI1>(A, lda, los, MIDR / 16, p.taps, p.dil, p.W1, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm, WM, acc1);
   }
   {
     const int n = wn * 16 + r;
@@ -263,7 +275,7 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs w
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int q = mb * 16 + 4 * g + e, s = s0 - h2 + q;
-          M[q * ldm + n] = Op::cvt((s >= 0 && s < len) ? lrelu(acc1[0][j][e] + bn) : 0.f);
+          Op::put(M + q * ldm + n, mos, (s >= 0 && s < len) ? lrelu(acc1[0][j][e] + bn) : 0.f);
         }
       }
     }
@@ -272,7 +284,7 @@ __global__ void __launch_bounds__(THREADS) voc_pair_kernel(PairArgs p, WinArgs w
   f32x4 acc2[1][MI2];
 #pragma unroll
   for (int j = 0; j < MI2; ++j) acc2[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  voc_mma<BF, 1, MI2>(M, ldm, VT / 16, p.taps, 1, p.W2, NB, p.KST, 0, p.KST, wn, WN, wm, WM, acc2);
+  voc_mma<MODE, 1, MI2>(M, ldm, mos, VT / 16, p.taps, 1, p.W2, NB, p.KST, 0, p.KST, wn, WN, wm, WM, acc2);
   const int n = wn * 16 + r;
   const float bn = p.b2[n];
 #pragma unroll
@@ -310,9 +322,10 @@ struct ChainArgs {
 // row blocks further on: conv1 hands row blocks to the waves shifted by that many (wm1), so that the wave that owns an output block
 // also owns its x1 block, and the second residual is the fp32 x1 in both precision modes.  Rows of x1 outside [0, len) are 0, as the
 // two-conv form writes them.  Each sum runs taps-outer, K-steps-inner as in voc_conv_kernel, whatever the tile's start.
+// Operand modes 0 and 1 only: the chain has no split form.
 template <bool BF, int MI1, int MI2, bool WIN>
 __global__ void __launch_bounds__(THREADS) voc_chain_kernel(ChainArgs p, WinArgs win) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<BF> Op;
   typedef typename Op::T T;
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_smem[];
   const int b = blockIdx.y, C = p.C;
@@ -346,9 +359,9 @@ __global__ void __launch_bounds__(THREADS) voc_chain_kernel(ChainArgs p, WinArgs
   for (int c0 = 0; c0 < KP; c0 += KC) {
     const int kcw = min(KC, KP - c0);
     __syncthreads();
-    voc_stage<BF, WIN>(A, lda, rows, X, C, 1, s0 - HR - h1, len, c0, kcw, C, 1, win.mx);
+    voc_stage<BF, WIN>(A, lda, 0, rows, X, C, 1, s0 - HR - h1, len, c0, kcw, C, 1, win.mx);
     __syncthreads();
-    voc_mma<BF, 1, MI1>(A, lda, MB1, p.taps, p.d1, p.W1, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm1, WM, x1);
+    voc_mma<BF, 1, MI1>(A, lda, 0, MB1, p.taps, p.d1, p.W1, NB, p.KST, c0 / Op::KS, kcw / Op::KS, wn, WN, wm1, WM, x1);
   }
   __syncthreads();                                   // every wave is done with A
   const int n = wn * 16 + r;
@@ -373,7 +386,7 @@ __global__ void __launch_bounds__(THREADS) voc_chain_kernel(ChainArgs p, WinArgs
   f32x4 acc2[1][MI2];
 #pragma unroll
   for (int j = 0; j < MI2; ++j) acc2[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  voc_mma<BF, 1, MI2>(M + (HR - h2) * ldm, ldm, VT / 16, p.taps, p.d2, p.W2, NB, p.KST, 0, p.KST, wn, WN, wm, WM, acc2);
+  voc_mma<BF, 1, MI2>(M + (HR - h2) * ldm, ldm, 0, VT / 16, p.taps, p.d2, p.W2, NB, p.KST, 0, p.KST, wn, WN, wm, WM, acc2);
   const float bn = p.b2[n];
 #pragma unroll
   for (int j2 = 0; j2 < MI2; ++j2) {
@@ -443,15 +456,18 @@ __global__ void __launch_bounds__(THREADS) voc_post_kernel(const float* X, long 
 // The chunk's last launch: the next replay of the same launches computes the next window.
 __global__ void voc_advance_kernel(int* cursor) { *cursor += 1; }
 
-// Pack: [phase][t][nb][ks][lane][VEC]; lane (n = l & 15, g = l >> 4) element v holds k = ks*KS + g*VEC + v of column nb*16 + n.
+// Pack: [phase][t][nb][ks][lane][IMG][VEC]; lane (n = l & 15, g = l >> 4) element v holds k = ks*KS + g*VEC + v of column nb*16 + n.
+// Mode 2: a lane's eight hi = bf16_rne(w), then its eight lo = bf16_rne(w - hi) (0 where hi is not finite): 32 bytes per lane and
+// step, the f32 pack's size wherever Cin is whole 32-deep steps.  The weights are split here, once.
 // up == 1: W (Cout, Cin, taps); up > 1: W (Cin, Cout, 2 up) of a ConvTranspose1d, tap t of phase r = kernel index j0(r) - t*up.
-template <bool BF>
+template <int MODE>
 __global__ void voc_pack_kernel(const float* W, void* out, int Cout, int Cin, int taps, int up, int KST, long total) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<MODE> Op;
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
   const int NB = Cout / 16, v = (int)(e % Op::VEC);
   long f = e / Op::VEC;
+  const int img = (int)(f % Op::IMG); f /= Op::IMG;
   const int lane = (int)(f % 64); f /= 64;
   const int ks = (int)(f % KST); f /= KST;
   const int nb = (int)(f % NB); f /= NB;
@@ -467,48 +483,56 @@ __global__ void voc_pack_kernel(const float* W, void* out, int Cout, int Cin, in
       val = W[((long)k * Cout + n) * (2 * up) + j];
     }
   }
-  reinterpret_cast<typename Op::T*>(out)[e] = Op::cvt(val);
+  typename Op::T o = (typename Op::T)val;
+  if (img) {                                         // the lo image: what hi leaves of val
+    const float hi = (float)o;
+    o = (typename Op::T)(__builtin_isfinite(hi) ? val - hi : 0.f);
+  }
+  reinterpret_cast<typename Op::T*>(out)[e] = o;
 }
 
-long voc_pack_elems(int Cout, int Cin, int taps, int up, int bf16) {
-  const int KS = bf16 ? 32 : 16;
-  return (long)(up > 1 ? up : 1) * taps * (Cout / 16) * dx_cdiv(Cin, KS) * 64 * (bf16 ? 8 : 4);
+// elements of a pack: 4 f32, 8 bf16 or 8 + 8 bf16 per lane and k step (mode 0, 1, 2)
+long voc_pack_elems(int Cout, int Cin, int taps, int up, int mode) {
+  const int KS = mode ? 32 : 16;
+  return (long)(up > 1 ? up : 1) * taps * (Cout / 16) * dx_cdiv(Cin, KS) * 64 * (mode == 2 ? 16 : mode ? 8 : 4);
 }
 
 // win == nullptr: the whole tensor (tiles over N rows); else the window kernels, with a grid for chunk 0's window of step + lag rows.
-template <bool BF, int NI, int MI>
+template <int MODE, int NI, int MI>
 int launch_conv(const ConvArgs& a, const WinArgs* win, int B, hipStream_t s) {
-  typedef DxMmaOp<BF> Op;
-  const size_t smem = (size_t)(VT + (a.taps - 1) * a.dil) * (KC + Op::PAD) * sizeof(typename Op::T);
+  typedef DxMmaMode<MODE> Op;
+  const size_t smem = (size_t)(VT + (a.taps - 1) * a.dil) * (KC + Op::PAD) * Op::IMG * sizeof(typename Op::T);
   if (win)
-    hipLaunchKernelGGL((voc_conv_kernel<BF, NI, MI, true>), dim3(dx_cdiv(win->step + win->lag, VT), B, a.up), dim3(THREADS), smem, s, a, *win);
+    hipLaunchKernelGGL((voc_conv_kernel<MODE, NI, MI, true>), dim3(dx_cdiv(win->step + win->lag, VT), B, a.up), dim3(THREADS), smem, s, a, *win);
   else
-    hipLaunchKernelGGL((voc_conv_kernel<BF, NI, MI, false>), dim3(dx_cdiv(a.N, VT), B, a.up), dim3(THREADS), smem, s, a, WinArgs{});
+    hipLaunchKernelGGL((voc_conv_kernel<MODE, NI, MI, false>), dim3(dx_cdiv(a.N, VT), B, a.up), dim3(THREADS), smem, s, a, WinArgs{});
   DX_LAUNCH_CHECK("dx_voc_conv");
   return DX_OK;
 }
 
-template <bool BF>
+template <int MODE>
 int dispatch_conv(const ConvArgs& a, const WinArgs* win, int B, hipStream_t s) {
   switch (a.Cout / 16) {
-    case 32: return launch_conv<BF, 8, 4>(a, win, B, s);
-    case 16: return launch_conv<BF, 4, 4>(a, win, B, s);
-    case 8: return launch_conv<BF, 2, 4>(a, win, B, s);
-    case 4: return launch_conv<BF, 1, 4>(a, win, B, s);
-    case 1: return launch_conv<BF, 1, 1>(a, win, B, s);      // 16 columns: one column block, the four waves over the four row blocks
-    default: return launch_conv<BF, 1, 2>(a, win, B, s);
+    case 32: return launch_conv<MODE, 8, 4>(a, win, B, s);
+    case 16: return launch_conv<MODE, 4, 4>(a, win, B, s);
+    case 8: return launch_conv<MODE, 2, 4>(a, win, B, s);
+    case 4: return launch_conv<MODE, 1, 4>(a, win, B, s);
+    case 1: return launch_conv<MODE, 1, 1>(a, win, B, s);      // 16 columns: one column block, the four waves over the four row blocks
+    default: return launch_conv<MODE, 1, 2>(a, win, B, s);
   }
 }
 
-template <bool BF, int MI1, int MI2>
+// LDS: 80 + 2 h1 rows of the input and 80 of the intermediate, in every image: at C = 64, taps 11, dilation 5 (130 rows) 57.1 KB in f32
+// mode, 60.5 KB in mode 2 -- the largest of any launch, inside the 64 KB a launch gets without asking for more
+template <int MODE, int MI1, int MI2>
 int launch_pair(const PairArgs& a, const WinArgs* win, int B, hipStream_t s) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<MODE> Op;
   const int h1 = a.dil * (a.taps - 1) / 2;
-  const size_t smem = ((size_t)(MIDR + 2 * h1) * (KC + Op::PAD) + (size_t)MIDR * (a.KST * Op::KS + Op::PAD)) * sizeof(typename Op::T);
+  const size_t smem = ((size_t)(MIDR + 2 * h1) * (KC + Op::PAD) + (size_t)MIDR * (a.KST * Op::KS + Op::PAD)) * Op::IMG * sizeof(typename Op::T);
   if (win)
-    hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2, true>), dim3(dx_cdiv(win->step + win->lag, VT), B), dim3(THREADS), smem, s, a, *win);
+    hipLaunchKernelGGL((voc_pair_kernel<MODE, MI1, MI2, true>), dim3(dx_cdiv(win->step + win->lag, VT), B), dim3(THREADS), smem, s, a, *win);
   else
-    hipLaunchKernelGGL((voc_pair_kernel<BF, MI1, MI2, false>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a, WinArgs{});
+    hipLaunchKernelGGL((voc_pair_kernel<MODE, MI1, MI2, false>), dim3(dx_cdiv(a.N, VT), B), dim3(THREADS), smem, s, a, WinArgs{});
   DX_LAUNCH_CHECK("dx_voc_pair");
   return DX_OK;
 }
@@ -516,7 +540,7 @@ int launch_pair(const PairArgs& a, const WinArgs* win, int B, hipStream_t s) {
 // LDS: the input window, 64 + 2 HR + 2 h1 rows of 64 channels (x1's operand copy overlays it): 178 rows = 48.4 KB at most in f32 mode
 template <bool BF, int MI1, int MI2>
 int launch_chain(const ChainArgs& a, const WinArgs* win, int B, hipStream_t s) {
-  typedef DxMmaOp<BF> Op;
+  typedef DxMmaMode<BF> Op;
   const int hk = (a.taps - 1) / 2, HR = (a.d2 * hk + 15) & ~15;
   const size_t smem = (size_t)(VT + 2 * HR + 2 * a.d1 * hk) * (KC + Op::PAD) * sizeof(typename Op::T);
   if (win)
@@ -549,11 +573,11 @@ int voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const
   DX_REQUIRE(B > 0 && N > 0 && in_scale > 0 && Cin > 0 &&
                  (Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256 || Cout == 512),
              "dx_voc_conv: bad shape (Cout in {16, 32, 64, 128, 256, 512})");
-  // the LDS window is 64 + dil (taps - 1) rows of 64 channels: at most 136 rows, 37 KB in f32 mode
+  // the LDS window is 64 + dil (taps - 1) rows of 64 channels: at most 136 rows, 37 KB in f32 mode, 39 KB in mode 2 (hi and lo images)
   DX_REQUIRE(up == 1 ? (taps >= 1 && taps % 2 == 1 && taps <= 11 && dil >= 1 && dil * (taps - 1) <= 72)
                      : (taps == 2 && dil == 1 && up >= 2 && up % 2 == 0 && up <= 8),
              "dx_voc_conv: bad taps / dilation / upsampling (odd taps <= 11 with dilation (taps - 1) <= 72, or a polyphase transposed conv: taps 2, even up <= 8)");
-  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_conv: bad acc_mode / bf16");
+  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && bf16 >= 0 && bf16 <= 2, "dx_voc_conv: bad acc_mode / bf16 (operand mode 0, 1 or 2)");
   DX_REQUIRE((const void*)X != (const void*)Y, "dx_voc_conv: Y must not alias X (tiles read their neighbours' rows); R may alias Y");
   DX_REQUIRE(sxc != 1 || sxn < Cin || (Cin % 4 == 0 && sxn % 4 == 0 && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0),
              "dx_voc_conv: channels-last input needs Cin and strides %% 4 == 0 and a 16-byte aligned X");
@@ -564,7 +588,8 @@ int voc_conv(const float* X, long sxb, long sxn, long sxc, const void* Wp, const
   a.frames = frames; a.in_scale = in_scale;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.dil = dil; a.pad = dil * (taps - 1) / 2; a.up = up;
   a.KST = dx_cdiv(Cin, bf16 ? 32 : 16); a.pro = lrelu_in; a.acc_mode = acc_mode;
-  return bf16 ? dispatch_conv<true>(a, win, B, (hipStream_t)stream) : dispatch_conv<false>(a, win, B, (hipStream_t)stream);
+  if (bf16 == 2) return dispatch_conv<2>(a, win, B, (hipStream_t)stream);
+  return bf16 ? dispatch_conv<1>(a, win, B, (hipStream_t)stream) : dispatch_conv<0>(a, win, B, (hipStream_t)stream);
 }
 
 // dx_voc_pair (win == nullptr; syb = sxb) and dx_voc_pair_win
@@ -575,16 +600,17 @@ int voc_pair(const float* X, long sxb, const void* W1, const float* b1, const vo
   DX_REQUIRE(B > 0 && N > 0 && scale > 0 && (C == 16 || C == 32 || C == 64) && sxb % 4 == 0 && ((uintptr_t)X & 15) == 0,
              "dx_voc_pair: bad shape (C in {16, 32, 64}; sxb %% 4 == 0 and a 16-byte aligned X)");
   DX_REQUIRE(voc_taps_ok(taps, dil), "dx_voc_pair: bad taps / dilation (taps 3, 7 or 11; dilation 1, 3 or 5)");
-  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_pair: bad acc_mode / bf16");
+  DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && bf16 >= 0 && bf16 <= 2, "dx_voc_pair: bad acc_mode / bf16 (operand mode 0, 1 or 2)");
   PairArgs a;
   a.X = X; a.sxb = sxb;
   a.W1 = reinterpret_cast<const uint4*>(W1); a.b1 = b1; a.W2 = reinterpret_cast<const uint4*>(W2); a.b2 = b2;
   a.Y = Y; a.syb = syb; a.frames = frames; a.scale = scale;
   a.N = N; a.C = C; a.taps = taps; a.dil = dil; a.KST = dx_cdiv(C, bf16 ? 32 : 16); a.acc_mode = acc_mode;
   hipStream_t s = (hipStream_t)stream;
-  if (C == 16) return bf16 ? launch_pair<true, 2, 1>(a, win, B, s) : launch_pair<false, 2, 1>(a, win, B, s);
-  if (C == 64) return bf16 ? launch_pair<true, 5, 4>(a, win, B, s) : launch_pair<false, 5, 4>(a, win, B, s);
-  return bf16 ? launch_pair<true, 3, 2>(a, win, B, s) : launch_pair<false, 3, 2>(a, win, B, s);
+  if (bf16 == 2) return C == 16 ? launch_pair<2, 2, 1>(a, win, B, s) : C == 64 ? launch_pair<2, 5, 4>(a, win, B, s) : launch_pair<2, 3, 2>(a, win, B, s);
+  if (C == 16) return bf16 ? launch_pair<1, 2, 1>(a, win, B, s) : launch_pair<0, 2, 1>(a, win, B, s);
+  if (C == 64) return bf16 ? launch_pair<1, 5, 4>(a, win, B, s) : launch_pair<0, 5, 4>(a, win, B, s);
+  return bf16 ? launch_pair<1, 3, 2>(a, win, B, s) : launch_pair<0, 3, 2>(a, win, B, s);
 }
 
 // dx_voc_chain (win == nullptr; syb = sxb) and dx_voc_chain_win
@@ -598,6 +624,7 @@ int voc_chain(const float* X, long sxb, const void* W1, const float* b1, const v
   // ten row blocks of x1 at most (HR <= 48), and an input window of at most 178 rows
   DX_REQUIRE((taps == 3 || taps == 5 || taps == 7) && d1 >= 1 && d2 >= 1 && d1 * (taps - 1) <= 18 && d2 * (taps - 1) <= 72,
              "dx_voc_chain: bad taps / dilation (taps 3, 5 or 7; d1 (taps - 1) <= 18, d2 (taps - 1) <= 72)");
+  DX_REQUIRE(bf16 != 2, "dx_voc_chain: no split-bf16 form (operand mode 2): run the ResBlock2 as two dx_voc_conv launches");
   DX_REQUIRE(acc_mode >= 0 && acc_mode <= 2 && (bf16 == 0 || bf16 == 1), "dx_voc_chain: bad acc_mode / bf16");
   ChainArgs a;
   a.X = X; a.sxb = sxb;
@@ -615,23 +642,25 @@ extern "C" {
 
 int dx_voc_pack_size(int Cout, int Cin, int taps, int up, int bf16, long* bytes) {
   DX_REQUIRE(bytes, "dx_voc_pack_size: null output");
-  DX_REQUIRE(Cout > 0 && Cout % 16 == 0 && Cin > 0 && taps > 0 && up >= 1 && (up == 1 || taps == 2) && (bf16 == 0 || bf16 == 1),
-             "dx_voc_pack_size: bad shape (Cout %% 16 == 0; a transposed conv (up > 1) has taps = 2 in polyphase form)");
+  DX_REQUIRE(Cout > 0 && Cout % 16 == 0 && Cin > 0 && taps > 0 && up >= 1 && (up == 1 || taps == 2) && bf16 >= 0 && bf16 <= 2,
+             "dx_voc_pack_size: bad shape (Cout %% 16 == 0; a transposed conv (up > 1) has taps = 2 in polyphase form; operand mode 0, 1 or 2)");
   *bytes = voc_pack_elems(Cout, Cin, taps, up, bf16) * (bf16 ? 2 : 4);
   return DX_OK;
 }
 
 int dx_voc_pack(const float* W, void* Wp, int Cout, int Cin, int taps, int up, int bf16, void* stream) {
   DX_REQUIRE(W && Wp, "dx_voc_pack: null pointer");
-  DX_REQUIRE(Cout > 0 && Cout % 16 == 0 && Cin > 0 && taps > 0 && up >= 1 && (up == 1 || (taps == 2 && up % 2 == 0)) && (bf16 == 0 || bf16 == 1),
-             "dx_voc_pack: bad shape (Cout %% 16 == 0; a transposed conv (up > 1, even) has taps = 2 in polyphase form)");
+  DX_REQUIRE(Cout > 0 && Cout % 16 == 0 && Cin > 0 && taps > 0 && up >= 1 && (up == 1 || (taps == 2 && up % 2 == 0)) && bf16 >= 0 && bf16 <= 2,
+             "dx_voc_pack: bad shape (Cout %% 16 == 0; a transposed conv (up > 1, even) has taps = 2 in polyphase form; operand mode 0, 1 or 2)");
   const long total = voc_pack_elems(Cout, Cin, taps, up, bf16);
   const int KST = dx_cdiv(Cin, bf16 ? 32 : 16);
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (bf16)
-    hipLaunchKernelGGL(voc_pack_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, W, Wp, Cout, Cin, taps, up, KST, total);
+  if (bf16 == 2)
+    hipLaunchKernelGGL(voc_pack_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, W, Wp, Cout, Cin, taps, up, KST, total);
+  else if (bf16)
+    hipLaunchKernelGGL(voc_pack_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, W, Wp, Cout, Cin, taps, up, KST, total);
   else
-    hipLaunchKernelGGL(voc_pack_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, W, Wp, Cout, Cin, taps, up, KST, total);
+    hipLaunchKernelGGL(voc_pack_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, W, Wp, Cout, Cin, taps, up, KST, total);
   DX_LAUNCH_CHECK("dx_voc_pack");
   return DX_OK;
 }

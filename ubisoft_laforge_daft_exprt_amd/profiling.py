@@ -182,7 +182,7 @@ def price(name, a, geom: Geometry):
     if name in ('dx_voc_conv', 'dx_voc_pair', 'dx_voc_chain', 'dx_voc_post', 'dx_voc_post_c'):   # HiFi-GAN vocoder: N rows of samples, frames * scale of them valid
         s = max(1, a['in_scale'] if name == 'dx_voc_conv' else a['scale'])
         rows = g('window_rows') or geom.rows(a['B'], a['N'] // s) * s
-        op = 'bf16' if g('bf16') else 'f32'
+        op = ('f32', 'bf16', 'bf16x3')[g('bf16') or 0]          # the operand mode; 'bf16x3>' prices against a third of the bf16 peak
         if name == 'dx_voc_conv':                        # conv (up = 1) or polyphase transposed conv: rows in, rows * up out
             out_rows = rows * a['up']
             byt = rows * a['Cin'] * 4 + out_rows * a['Cout'] * 4 * (1 + has('R') + (a['acc_mode'] > 0))
@@ -204,7 +204,7 @@ def price(name, a, geom: Geometry):
     if name == 'dx_voc_post_bwd':                        # X read, dX written, Y and dY read
         return 'voc_post_bwd', 'hbm', None, a['B'] * a['N'] * (2 * a['C'] + 2) * 4
     if name == 'dx_voc_pack':
-        return 'voc_pack', 'hbm', None, a['Cout'] * a['Cin'] * a['taps'] * max(1, a['up']) * (4 + (2 if a['bf16'] else 4))
+        return 'voc_pack', 'hbm', None, a['Cout'] * a['Cin'] * a['taps'] * max(1, a['up']) * (4 + (2 if a['bf16'] == 1 else 4))
     if name == 'dx_disc_conv':                           # HiFi-GAN discriminators: rows of N positions, no lengths
         nout = (a['N'] + 2 * a['pad'] - a['taps']) // a['stride'] + 1
         cin_g = a['Cin'] // a['groups']

@@ -55,7 +55,9 @@ def v3_config() -> dict:
 
 CONFIGS = {'v1': v1_config, 'v2': v2_config, 'v3': v3_config}     # the whitelist: the kernels are instantiated per width
 DEFAULT_CONFIG = v1_config()
-PRECISIONS = {'f32': 0, 'bf16': 1}
+# operand mode of the conv kernels (the C ABI's `bf16` argument).  'bf16x3': split bf16 -- fp32 storage, every operand hi + lo in bf16,
+# every product on three bf16 MFMAs (~16 mantissa bits); inference only, and the launch list is the f32 one (no chain launches).
+PRECISIONS = {'f32': 0, 'bf16': 1, 'bf16x3': 2}
 MIN_WIDTH = 16                               # one MFMA column block: a narrower stage (V2's last, 8 channels) runs zero-padded to it
 WORKSPACE_BYTES_PER_FRAME = 5 * 8192 * 4    # V1: five fp32 activation buffers of at most 8192 values per mel frame (C x samples per frame)
 DEFAULT_WORKSPACE_BYTES = 4 << 30            # infer_batch's default bound: larger batches run in chunks of utterances
